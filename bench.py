@@ -5,19 +5,22 @@ One "step" = patch scramble (incl. the per-image random permutation) + forward +
 + Keras-Adam (+ RCCL gradient all-reduce for N>1) on one synthetic CelebA-64 batch that is already
 resident in HBM, i.e. train_step_lg_vae (vae/trainer.py:120-144) behind the augmentation of
 vae/main.py:57-61.  Workload (BASELINE.json metric: "SPLIT-VAE CelebA-64 bs512"): H=W=64,
-beta=120, patch_size=8, latents 128+128, lr 1e-4.  The headline (`value`, `ms_per_step`, `dtype`, `roofline`) is the step at the
-REFERENCE'S precision: fp32 operands and accumulation (exact-fp32 MFMA, graded against the 157.3 TFLOP/s fp32 matrix peak); the bf16-operand
-step (BASELINE config 2's throughput mode) rides along as the named block `bf16` with its own roofline (`--dtype bf16` swaps the two).
-The metric's batch is GLOBAL: `--gpus N` splits 512 images evenly over the N ranks (strong scaling: 64 per GPU at N = 8, SURVEY 8d
-config C4) and `value` is the whole-job aggregate 512*K / t; the weak-scaling figure (512 per GPU) rides along as `weak` in the N > 1
-line, and `--batch B` makes it the headline instead.
+beta=120, patch_size=8, latents 128+128, lr 1e-4.  The headline (`value`, `ms_per_step`, `dtype`) is the step at the
+REFERENCE'S precision: fp32 operands and accumulation (exact-fp32 MFMA, graded against the 157.3 TFLOP/s fp32 matrix peak); with `--full`
+the bf16-operand step (BASELINE config 2's throughput mode) rides along as the named block `bf16` with its own roofline (`--dtype bf16`
+swaps the two).  The metric's batch is GLOBAL: `--gpus N` splits 512 images evenly over the N ranks (strong scaling: 64 per GPU at N = 8,
+SURVEY 8d config C4) and `value` is the whole-job aggregate 512*K / t; with `--full` the weak-scaling figure (512 per GPU) rides along as
+`weak` in the N > 1 line, and `--batch B` makes it the headline instead.
 
-    python bench.py                                  # N=1, 200 timed steps
+    python bench.py                                  # N=1, 200 timed steps: the headline only
     python bench.py --gpus N --steps K --warmup W    # N>1: spawns N ranks itself (one per GPU, RCCL), or runs as one
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W      # rank of a launcher that set WORLD_SIZE
+    python bench.py --full                           # + everything below
+    python bench.py --dump-outputs DIR               # + what the last timed step computed, as DIR/*.npy (dump_outputs)
 
-Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
+A plain run sets up, warms up (W steps, topped up to 30 untimed steps), times exactly K steps and prints ONE JSON line (rank 0).
+`--full` adds the measurements that take runs of their own, outside the timed region:
   roofline      dominant kernel (hipEvent-timed inside the timed region on its launch stream), the decoder conv stack
                 aggregate (north_star's >= 70 % target) and the HBM-bound ELBO kernel
   cpu_baseline  the oracle restatement timed on the host cores (N=1 only; reported baseline, not the target)
@@ -26,8 +29,8 @@ Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
   rows          the other configurations of BASELINE.md section 4 measured in the same process, outside the timed region:
                 CelebA-64 bs256 bf16 (configs[1]), SVHN-32 B=64, the 64- and 128-image shards of config 4 at both precisions, one rank
                 through the data-parallel path (dp_path_b64), SPLIT-GMVAE, SPLIT-SPAIR (Multi-Bird-Hard and -Easy flag sets)
-  rccl_ranks / allreduce_ms / weak   (N>1) the collective actually used, its per-bucket time, the 512-per-GPU (weak scaling) row
-The per-launch table goes to stderr.
+  allreduce_ms / weak   (N>1) the per-bucket all-reduce time, the 512-per-GPU (weak scaling) row
+and the per-launch table goes to stderr.  The N > 1 line always names the collective actually used (rccl_ranks, dist_backend).
 """
 import argparse
 import json
@@ -182,8 +185,9 @@ class Workload:
         # plan=: the augmentation kernel also writes the step's padded low-precision inputs (one pass over the batch less)
         images = self.aug.augment(self.x, sample_offset=self.off, plan=None if os.environ.get("SV_BENCH_NO_STAGED") else self.model.plan(self.x.shape[0]))
         # keep_recon=False: like the reference's step (returns nothing), the reconstructions die inside the fused loss
-        return trainer.train_step(self.model, images, self.opt, reducer=self.reducer, sample_offset=self.off,
-                                  keep_recon=os.environ.get("SV_BENCH_KEEP_RECON") is not None)
+        self.last_plan = trainer.train_step(self.model, images, self.opt, reducer=self.reducer, sample_offset=self.off,
+                                            keep_recon=os.environ.get("SV_BENCH_KEEP_RECON") is not None)
+        return self.last_plan
 
     def timed(self, steps, warmup, world, dev):
         """W untimed + exactly K timed steps, barrier + synchronize on both sides, MAX over ranks -> seconds."""
@@ -213,6 +217,41 @@ class Workload:
             tdist.all_reduce(tmax, op=tdist.ReduceOp.MAX)
             dt = float(tmax.item())
         return dt
+
+
+DUMP_SAMPLE = 1 << 20          # entries of a sampled output (4 MB as float32)
+DUMP_FULL_MAX = 12 << 20       # outputs up to this many entries are written whole (the CelebA-64 variables: 8.7 M, 35 MB)
+
+
+def dump_outputs(w, out_dir):
+    """--dump-outputs DIR: what the timed path computed in its LAST step, as a caller of trainer.train_step receives it, written as float32 / float64 .npy:
+      losses.npy     [6] x_recon, x_kl, x_hat_recon, x_hat_kl, total_kl, total_loss of that step (trainer.last_losses)
+      metrics.npy    [5] the running means of vae/trainer.py's five metrics over every step up to that one (trainer.StepMetrics.result)
+      variables.npy  the trainable variables after that step's Adam update, flat in trainable_variables order
+      gradients.npy  that step's gradients of the variables: a fixed sample of DUMP_SAMPLE entries (np.random.default_rng(0), sorted indices)
+    Under 64 MB in all.  The inputs are seeded (data.synthetic_images seed 0, Augmentator seed 1, model seed 3, the Philox noise keyed by
+    the step index), so two builds given the same arguments can be compared file for file."""
+    import numpy as np
+    import torch
+    from split_vae_amd import trainer
+
+    def host(t, whole_max):
+        """t as a float32 host array: whole up to whole_max entries, else the fixed sample of DUMP_SAMPLE of them."""
+        n = t.numel()
+        if n > whole_max:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        return t.detach().float().cpu().numpy()
+
+    torch.cuda.synchronize()
+    plan = w.last_plan
+    os.makedirs(out_dir, exist_ok=True)
+    losses = trainer.last_losses(plan)
+    metrics = trainer.StepMetrics(plan).result()
+    np.save(os.path.join(out_dir, "losses.npy"), np.array([losses[k] for k in trainer.METRIC_NAMES + ["total_loss"]], np.float32))
+    np.save(os.path.join(out_dir, "metrics.npy"), np.array([metrics[k] for k in trainer.METRIC_NAMES], np.float64))
+    np.save(os.path.join(out_dir, "variables.npy"), host(w.model.flat, DUMP_FULL_MAX))
+    np.save(os.path.join(out_dir, "gradients.npy"), host(w.model.grad_flat, DUMP_SAMPLE))
 
 
 TABLE_PASSES = 3
@@ -552,7 +591,12 @@ def main():
     ap.add_argument("--table-only", type=int, default=0, metavar="PASSES",
                     help="run PASSES passes of the serial per-launch table and stop (for `rocprofv3 --kernel-trace --stats`: kernel durations alone on the chip, "
                          "what `roofline.serial` and the fractions of the table quote)")
-    ap.add_argument("--profile-all", action="store_true", help="(kept for compatibility: the per-launch table always goes to stderr)")
+    ap.add_argument("--profile-all", action="store_true", help="(kept for compatibility: with --full the per-launch table always goes to stderr)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline (outside the timed region): the serial per-launch table and the roofline block, the other precision, "
+                         "the extra configurations, the CPU baseline; N > 1: the all-reduce times and the weak-scaling row.  Off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (bench.py: dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -587,30 +631,40 @@ def main():
         w.step()
     torch.cuda.synchronize()
 
-    # per-launch table + the dominant kernel family (outside the timed region)
-    plan, table = kernel_table(w, passes=args.table_only or TABLE_PASSES, prime=not args.table_only)
-    if rank == 0:
-        print_table(table, args.dtype, H, B)
-    if args.table_only:
+    if args.full or args.table_only:
+        # per-launch table + the dominant kernel family (outside the timed region)
+        plan, table = kernel_table(w, passes=args.table_only or TABLE_PASSES, prime=not args.table_only)
         if rank == 0:
-            print(json.dumps({"table_only": args.table_only, "rows": [{"kernel": r["name"], "launches": r["launches"], "ms": round(r["total_ms"] / max(r["launches"], 1), 4)} for r in table[:12]]}))
-        return
-    # the dominant kernel = the top row of the serial table, whatever it is.  In the timed region the streams of the backward pass overlap:
-    # `achieved` is what the hipEvents around the launch on ITS stream give there (co-running launches of the other streams included; `stream`
-    # names it), `serial` what the launch takes alone on the chip.
-    dom, worst = pick_rows(table, args.dtype)
-
-    plan.profile_filter(dom["name"])
-    plan.profile_enable(True)
-    # the W warm-up steps already ran (and the serial table passes after them); a short timed region (K = 20 is 37 ms) starts from whatever
+            print_table(table, args.dtype, H, B)
+        if args.table_only:
+            if rank == 0:
+                print(json.dumps({"table_only": args.table_only, "rows": [{"kernel": r["name"], "launches": r["launches"], "ms": round(r["total_ms"] / max(r["launches"], 1), 4)} for r in table[:12]]}))
+            return
+        # the dominant kernel = the top row of the serial table, whatever it is.  In the timed region the streams of the backward pass overlap:
+        # `achieved` is what the hipEvents around the launch on ITS stream give there (co-running launches of the other streams included; `stream`
+        # names it), `serial` what the launch takes alone on the chip.
+        dom, worst = pick_rows(table, args.dtype)
+        plan.profile_filter(dom["name"])
+        plan.profile_enable(True)
+    # the W warm-up steps already ran (with --full, the serial table passes after them); a short timed region (K = 20 is 37 ms) starts from whatever
     # clock / power state the table's profiling syncs left behind (+-3 % run to run), so the chip is brought back to the steady state of
     # back-to-back steps first: untimed steps, never fewer than 30 in total before the clock starts
     dt = w.timed(args.steps, max(0, 30 - args.warmup), world, dev)
-    prof = [r for r in plan.profile_read() if r["name"] == dom["name"]]
-    plan.profile_enable(False)
+    if args.full:
+        prof = [r for r in plan.profile_read() if r["name"] == dom["name"]]
+        plan.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(w, args.dump_outputs)
 
     extra = {}
     if w.reducer is not None:
+        # the collective the step used (nothing measured)
+        extra["dp_mode"] = getattr(w.reducer, "mode", None) if getattr(w.reducer, "mode", None) != "auto" else ("single" if world == 1 else "events")
+        native = os.environ.get("SV_DIST_BACKEND") == "sv_comm"
+        extra["rccl_ranks"] = world if (backend == "nccl" or native) else 0
+        extra["dist_backend"] = "sv_comm (RCCL through the C ABI)" if native else backend
+        extra["allreduce_bytes"] = {k: int(sum(e - b for b, e in v) * 4) for k, v in w.reducer.buckets.items()}
+    if w.reducer is not None and args.full:
         # per-bucket all-reduce time, alone on the chip (what the backward has to hide)
         ar = {}
         for name in w.reducer.buckets:
@@ -637,12 +691,7 @@ def main():
         w.reducer.wait_events = None
         if ev:
             extra["exposed_allreduce_ms"] = round(sum(a_.elapsed_time(b_) for a_, b_ in ev) / len(ev), 4)
-        extra["dp_mode"] = getattr(w.reducer, "mode", None) if getattr(w.reducer, "mode", None) != "auto" else ("single" if world == 1 else "events")
-        native = os.environ.get("SV_DIST_BACKEND") == "sv_comm"
-        extra["rccl_ranks"] = world if (backend == "nccl" or native) else 0
-        extra["dist_backend"] = "sv_comm (RCCL through the C ABI)" if native else backend
         extra["allreduce_ms"] = ar
-        extra["allreduce_bytes"] = {k: int(sum(e - b for b, e in v) * 4) for k, v in w.reducer.buckets.items()}
         if world > 1 and strong and H == 64 and not args.no_rows:
             # the weak-scaling row: 512 images per GPU (global 512 N), what rounds 1-3 reported as the headline
             ws = Workload(64, 512, args.dtype, dev, rank, world, svdist.make_reducer)
@@ -654,10 +703,10 @@ def main():
     rows = {}
     other = None
     other_dt = "bf16" if args.dtype == "f32" else "f32"
-    if world == 1 and not args.no_other:
+    if args.full and world == 1 and not args.no_other:
         # N = 1: the full block (own serial table + roofline), 200 timed steps for the sub-2-ms bf16 step, 40 for fp32
         other = precision_block(dev, H, B, other_dt, steps=200 if other_dt == "bf16" else 40, warmup=10 if other_dt == "bf16" else 5)
-    elif world > 1 and not args.no_other:
+    elif args.full and world > 1 and not args.no_other:
         # N > 1: the other precision's whole-job rate through the same data-parallel path (no table: the serial table is an N = 1 measurement)
         wo = Workload(H, B, other_dt, dev, rank, world, svdist.make_reducer)
         ko = max(args.steps, 60)
@@ -665,7 +714,7 @@ def main():
         other = {"value": round(world * B * ko / dto, 1), "unit": "images/s", "ms_per_step": round(1e3 * dto / ko, 4), "steps": ko, "warmup": 10,
                  "dtype": DTYPE_NOTE[other_dt], "per_gpu_batch": B, "global_batch": world * B}
         del wo
-    if world == 1 and not args.no_rows and H == 64 and B == 512:
+    if args.full and world == 1 and not args.no_rows and H == 64 and B == 512:
         def row(Hr, Br, dt_, steps, warm=10, reducer_cls=None, workload=None):
             wr = Workload(Hr, Br, dt_, dev, 0, 1, reducer_cls)
             t = wr.timed(steps, warm, 1, dev)
@@ -703,7 +752,7 @@ def main():
             try:
                 env = dict(os.environ, SV_DIST_FORCE="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--batch", "64", "--dtype", k, "--steps", "200" if k == "bf16" else "100",
-                                    "--warmup", "10", "--no-rows", "--no-other-precision", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
+                                    "--warmup", "10", "--full", "--no-rows", "--no-other-precision", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
                 c = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
                 base = rows["celeba64_b64" + ("_f32" if k == "f32" else "")]["ms_per_step"]
                 rows["dp_path_b64"][k] = {"value": c["value"], "unit": "images/s", "ms_per_step": c["ms_per_step"], "steps": c["steps"],
@@ -721,7 +770,7 @@ def main():
                 env = dict(os.environ, RANK=str(r_), LOCAL_RANK="0", WORLD_SIZE="2", LOCAL_WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                            SV_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
                 procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__), "--gpus", "2", "--dtype", "f32", "--steps", "40", "--warmup", "5",
-                                               "--no-rows", "--no-other-precision", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True))
+                                               "--full", "--no-rows", "--no-other-precision", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True))
             try:
                 outs = [p_.communicate(timeout=240)[0] for p_ in procs]
             finally:
@@ -749,7 +798,7 @@ def main():
         "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True,
         "scaling": "strong" if strong else "weak",
         "vs_baseline": None,
-        "dtype": DTYPE_NOTE[args.dtype] + ("" if args.dtype == "f32" else "; the fp32 step is the `fp32` block of this line"),
+        "dtype": DTYPE_NOTE[args.dtype] + ("" if args.dtype == "f32" or other is None else "; the fp32 step is the `fp32` block of this line"),
         "dtype_short": args.dtype, "data": "synthetic",
         "config": {"workload": "SPLIT-VAE %s %dx%d beta=%g patch_size=%d latents=128+128 lr=1e-4, full train step "
                                "(scramble+fwd+ELBO+bwd+Adam%s), per-GPU batch %d" %
@@ -759,20 +808,19 @@ def main():
                    # the step's outputs are the losses and the updated variables (vae/trainer.py:121-144 returns nothing): the
                    # reconstruction tensors are consumed by the loss inside the head conv and not written to HBM
                    "reconstructions": "stored" if os.environ.get("SV_BENCH_KEEP_RECON") is not None else "not stored (dead after the fused loss)"},
-        # untimed steps run before the clock starts: the W requested, the serial per-launch table passes, and the steady-state top-up
-        "untimed_steps_before_timing": max(args.warmup, 1) + TABLE_PASSES + 1 + max(max(0, 30 - args.warmup), 1),
+        # untimed steps run before the clock starts: the W requested, (--full) the serial per-launch table passes, and the steady-state top-up
+        "untimed_steps_before_timing": max(args.warmup, 1) + (TABLE_PASSES + 1 if args.full else 0) + max(max(0, 30 - args.warmup), 1),
         "step_tflops": round(value * TRAIN_FLOP_PER_IMAGE[H] / 1e12, 2),
         "step_frac_of_peak": round(value * TRAIN_FLOP_PER_IMAGE[H] / 1e12 / PEAK_TFLOPS[args.dtype] / world, 4),     # direct FLOP count; issued: roofline.step_frac_issued
     }
     out.update(extra)
-    rl = roofline_block(table, dom, worst, prof, args.dtype, B, world, step_ms=1e3 * dt / args.steps)
-    if rl:
-        out["roofline"] = rl
+    if args.full:
+        out["roofline"] = roofline_block(table, dom, worst, prof, args.dtype, B, world, step_ms=1e3 * dt / args.steps)
     if other is not None:
         out["bf16" if other_dt == "bf16" else "fp32"] = other
     if rows:
         out["rows"] = rows
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     print(json.dumps(out), flush=True)
     if torch.distributed.is_initialized():

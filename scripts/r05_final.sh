@@ -30,12 +30,12 @@ traffic() {   # traffic <dtype> <out.json>
 mkdir -p profiles
 traffic f32 $O/${T}_f32_traffic.json; cp $O/${T}_f32_traffic.json profiles/${T}_f32_traffic.json
 traffic bf16 $O/${T}_traffic.json; cp $O/${T}_traffic.json profiles/${T}_traffic.json
-python bench.py > $O/${T}_bench.json 2> $O/${T}_table.txt
+python bench.py --full > $O/${T}_bench.json 2> $O/${T}_table.txt
 prof $O/${T}_f32_kernel_stats.csv --dtype f32 --steps 20 --warmup 5 --no-cpu-baseline --no-rows --no-other-precision
 prof $O/${T}_f32_serial_kernel_stats.csv --dtype f32 --table-only 20
 prof $O/${T}_bf16_kernel_stats.csv --dtype bf16 --steps 50 --warmup 5 --no-cpu-baseline --no-rows --no-other-precision
 prof $O/${T}_bf16_serial_kernel_stats.csv --dtype bf16 --table-only 30
-for dt in f32 bf16; do timeout 300 python bench.py --batch 64 --dtype $dt --steps 200 --warmup 10 --no-cpu-baseline --no-rows --no-other-precision > $O/${T}_bench_b64_$dt.json 2> $O/${T}_table_b64_$dt.txt; done
+for dt in f32 bf16; do timeout 300 python bench.py --full --batch 64 --dtype $dt --steps 200 --warmup 10 --no-cpu-baseline --no-rows --no-other-precision > $O/${T}_bench_b64_$dt.json 2> $O/${T}_table_b64_$dt.txt; done
 for dt in f32 bf16; do for m in events overlap; do echo -n "dp one rank, B=64 $dt $m: "; SV_DIST_FORCE=1 SV_DP_MODE=$m timeout 300 python bench.py --batch 64 --dtype $dt --steps 200 --warmup 10 --no-cpu-baseline --no-rows --no-other-precision 2>/dev/null | python -c "import sys,json; d=[json.loads(l) for l in sys.stdin if l.startswith('{')][-1]; print(d['ms_per_step'])"; done; done > $O/${T}_dp_one_rank.txt 2>&1
 timeout 400 bash scripts/r03_spair_prof.sh $T > /dev/null 2>&1
 timeout 400 bash scripts/r03_gm_prof.sh $T > /dev/null 2>&1

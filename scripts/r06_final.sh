@@ -31,7 +31,7 @@ traffic() {   # traffic <dtype> <out.json>
 mkdir -p profiles
 traffic f32 $O/${T}_f32_traffic.json; cp $O/${T}_f32_traffic.json profiles/${T}_f32_traffic.json
 traffic bf16 $O/${T}_traffic.json; cp $O/${T}_traffic.json profiles/${T}_traffic.json
-python bench.py > $O/${T}_bench.json 2> $O/${T}_table.txt
+python bench.py --full > $O/${T}_bench.json 2> $O/${T}_table.txt
 prof $O/${T}_f32_kernel_stats.csv --dtype f32 --steps 20 --warmup 5 --no-cpu-baseline --no-rows --no-other-precision
 prof $O/${T}_f32_serial_kernel_stats.csv --dtype f32 --table-only 20
 prof $O/${T}_bf16_kernel_stats.csv --dtype bf16 --steps 50 --warmup 5 --no-cpu-baseline --no-rows --no-other-precision
@@ -40,7 +40,7 @@ bash scripts/r06_pmc_mix.sh $T f32 > /dev/null 2>&1
 bash scripts/r05_timeline.sh $T f32 512 > /dev/null 2>&1
 bash scripts/r05_timeline.sh $T f32 64 > /dev/null 2>&1
 bash scripts/r05_timeline.sh $T bf16 64 > /dev/null 2>&1
-for dt in f32 bf16; do timeout 300 python bench.py --batch 64 --dtype $dt --steps 200 --warmup 10 --no-cpu-baseline --no-rows --no-other-precision > $O/${T}_bench_b64_$dt.json 2> $O/${T}_table_b64_$dt.txt; done
+for dt in f32 bf16; do timeout 300 python bench.py --full --batch 64 --dtype $dt --steps 200 --warmup 10 --no-cpu-baseline --no-rows --no-other-precision > $O/${T}_bench_b64_$dt.json 2> $O/${T}_table_b64_$dt.txt; done
 timeout 400 bash scripts/r03_spair_prof.sh $T > /dev/null 2>&1
 GM_DTYPE=f32 timeout 400 bash scripts/r03_gm_prof.sh $T > /dev/null 2>&1
 timeout 1800 python -m pytest tests -m gpu -q > $O/${T}_gputests.log 2>&1; grep -E "passed|failed" $O/${T}_gputests.log | tail -1 > $O/${T}_gputests_tail.txt; grep -E "^FAILED" $O/${T}_gputests.log >> $O/${T}_gputests_tail.txt
