@@ -288,6 +288,12 @@ int sv_add(const void* a, const void* b, void* out, int32_t dtype, int64_t n, vo
  * One launch, fixed-order sums. */
 int sv_gm_metrics(const float* nll_x, const float* kl_x, const float* nll_xh, const float* kl_xh, const float* y_kl, int32_t B,
                   float beta, float alpha, float* out6, void* stream);
+/* Unsupervised cluster accuracy (vae/trainer.py:40-68 linear_assignment, :315-349): for each of the B rows, cluster k = argmax of
+ * logits[b, :K] and class c = argmax of labels_onehot[b, :C] (first index on ties, as tf.argmax); counts[k * C + c] += 1 (int32,
+ * integer atomics: deterministic).  counts [K][C] is accumulated into -- zero it once, call once per batch.  The accuracy of the
+ * majority-class assignment is sum_k max_c counts[k][c] / N. */
+int sv_cluster_confusion(const float* logits, int32_t ld, const float* labels_onehot, int32_t ld_lab, int32_t B, int32_t K, int32_t C,
+                         int32_t* counts, void* stream);
 /* Gumbel-softmax (vae/model.py:121-122): y = softmax((logits - log(-log u)) / tau, axis=1); u[B,K] (NULL: Philox,
  * written to u_out).  y[B,K] fp32 and y_lp[B,ld_lp] (zero padded).  K, ld_lp <= 128. */
 int sv_gumbel_softmax_fwd(const float* logits, int32_t ld_logits, const float* u, float* u_out, float tau, float* y,
@@ -370,11 +376,21 @@ typedef struct {
                                             FWD_ENCODERS and FWD_DECODERS and reads dL/dz_x from columns [0, global_latent)
                                             of `gz_x` after BWD_DECODERS.  The encoder_x slots of the parameter table stay
                                             (unused, zero gradient) so the flat layout is the same in both modes. */
+  int32_t global_only;                   /* 1: GMVae (vae/model.py:277-298): ONE branch -- the caller's encoder_x (requires
+                                            external_global_encoder = 1, else SV_E_BADARG) and decoder_x over z_x alone.  The
+                                            parameter table then holds only the 10 decoder_x arrays (d1 kernel [global_latent,
+                                            (H/8)(W/8)128]); local_latent is ignored.  Every phase skips encoder_x_hat,
+                                            decoder_x_hat and the x-hat loss; FWD_ENCODERS only zeroes gz_x and fills in8_x
+                                            (in8_xh stays, so the staged augmentation writes the same buffers); the BWD_ENC
+                                            phases do nothing.  `zcat` and `gz_x` have row pitch global_latent; the caller
+                                            reads dL/dz_x from gz_x.  The loss phase writes nll_x (per image) and losses[0]
+                                            (mean) -- the KL terms are the caller's.  Graph replay is refused
+                                            (sv_lgvae_graph_enable: SV_E_UNSUPPORTED).  0: the two-branch plan above. */
 } sv_lgvae_desc;
 
 typedef struct sv_lgvae_plan sv_lgvae_plan;
 
-/* the 40 trainable variables, Keras creation order, flat fp32 buffer */
+/* the 40 trainable variables (10 with global_only), Keras creation order, flat fp32 buffer */
 int64_t sv_lgvae_param_count(const sv_lgvae_desc* d);
 int sv_lgvae_param_info(const sv_lgvae_desc* d, int32_t index, int64_t* offset, int32_t* ndim,
                         int64_t shape[4], char name[96]);

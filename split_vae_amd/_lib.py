@@ -35,7 +35,7 @@ class ConvDesc(C.Structure):
 class LGVaeDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("global_latent", C.c_int32),
                 ("local_latent", C.c_int32), ("dtype", C.c_int32), ("beta", C.c_float),
-                ("external_global_encoder", C.c_int32)]
+                ("external_global_encoder", C.c_int32), ("global_only", C.c_int32)]
 
 
 class StepArgs(C.Structure):
@@ -102,6 +102,7 @@ SYMBOLS = {
                              _i32, _vp]),
     "sv_add": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp]),
     "sv_gm_metrics": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _f, _f, _vp, _vp]),
+    "sv_cluster_confusion": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "sv_gumbel_softmax_fwd": (C.c_int, [_vp, _i32, _vp, _vp, _f, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _u64, _i64, _vp]),
     "sv_gumbel_softmax_bwd": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _f, _f, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "sv_gm_head_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32,

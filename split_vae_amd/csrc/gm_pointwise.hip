@@ -338,3 +338,33 @@ extern "C" int sv_gm_head_bwd(const float* dz, int32_t ld_dz, const float* z_mea
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
+
+// ---------------------------------------------------------------- unsupervised cluster accuracy (vae/trainer.py:40-68, :315-349)
+// one thread per image: cluster = argmax of its y_logits row, class = argmax of its one-hot label row (first index on ties, as
+// tf.argmax), counts[cluster][class] += 1.  Integer atomics: the counts are the same whatever the order of the threads.
+static __global__ __launch_bounds__(256) void cluster_confusion_kernel(const float* __restrict__ logits, int ld, const float* __restrict__ labels,
+                                                                       int ld_lab, int B, int K, int C, int32_t* __restrict__ counts) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float* r = logits + (int64_t)b * ld;
+  int k = 0;
+  float best = r[0];
+  for (int i = 1; i < K; ++i)
+    if (r[i] > best) { best = r[i]; k = i; }
+  const float* l = labels + (int64_t)b * ld_lab;
+  int c = 0;
+  float lb = l[0];
+  for (int j = 1; j < C; ++j)
+    if (l[j] > lb) { lb = l[j]; c = j; }
+  atomicAdd(counts + (int64_t)k * C + c, 1);
+}
+
+extern "C" int sv_cluster_confusion(const float* logits, int32_t ld, const float* labels_onehot, int32_t ld_lab, int32_t B, int32_t K,
+                                    int32_t C, int32_t* counts, void* stream) {
+  if (!logits || !labels_onehot || !counts || B < 0 || K <= 0 || C <= 0 || ld < K || ld_lab < C) return SV_E_BADARG;
+  if (B == 0) return SV_OK;
+  hipLaunchKernelGGL(cluster_confusion_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, logits, ld, labels_onehot, ld_lab,
+                     B, K, C, counts);
+  SV_LAUNCH_CHECK();
+  return SV_OK;
+}

@@ -59,6 +59,10 @@ static std::vector<ParamInfo> build_params(const sv_lgvae_desc* d) {
     add(pre + "/d4/kernel", {6, 6, 64, 32}); add(pre + "/d4/bias", {32});
     add(pre + "/d5/kernel", {6, 6, 32, 6}); add(pre + "/d5/bias", {6});
   };
+  if (d->global_only) {                 // GMVae: decoder_x over z_x alone (vae/model.py:285-286)
+    dec("decoder_x", d->global_latent);
+    return v;
+  }
   enc("encoder_x", d->global_latent);
   enc("encoder_x_hat", d->local_latent);
   dec("decoder_x", d->global_latent + d->local_latent);
@@ -70,6 +74,13 @@ static int check_desc(const sv_lgvae_desc* d) {
   if (!d) return SV_E_BADARG;
   if (d->B <= 0 || d->H < 8 || d->W < 8) return SV_E_BADARG;
   if (d->H != d->W || ilog2_exact(d->H) < 0) return SV_E_UNSUPPORTED;
+  if (d->global_only && !d->external_global_encoder) return SV_E_BADARG;   // the one branch's encoder is the caller's
+  if (d->global_only) {                                                    // (local_latent is ignored)
+    if (d->global_latent <= 0) return SV_E_BADARG;
+    if (ilog2_exact(d->global_latent) < 0 || d->global_latent < 8) return SV_E_UNSUPPORTED;
+    if (d->dtype != SV_BF16 && d->dtype != SV_F32) return SV_E_BADARG;
+    return SV_OK;
+  }
   if (d->global_latent <= 0 || d->local_latent <= 0) return SV_E_BADARG;
   if (ilog2_exact(d->global_latent) < 0 || ilog2_exact(d->local_latent) < 0 || d->global_latent < 8 ||
       d->local_latent < 8 || d->global_latent != d->local_latent)
@@ -274,6 +285,8 @@ struct sv_lgvae_plan {
   std::vector<hipEvent_t> event_pool;
 
   size_t esz() const { return d.dtype == SV_BF16 ? 2 : 4; }
+  int ndec() const { return d.global_only ? 1 : 2; }                       // decoders (and x / x-hat networks) the plan runs
+  int lc() const { return d.global_only ? d.global_latent : d.global_latent + d.local_latent; }   // decoder_x's input width = zcat / gz_x pitch
   int64_t add_buf(const std::string& n, int64_t bytes) {
     Buf b;
     b.name = n; b.off = ws_bytes; b.bytes = bytes;
@@ -374,7 +387,7 @@ static void build_layers(sv_lgvae_plan* p) {
     for (int i = 0; i < 4; ++i) L.wd_off[i] = 0;
     return L;
   };
-  for (int e = 0; e < 2; ++e) {
+  for (int e = 0; e < 2 && !d.global_only; ++e) {
     const int pb = e * 10;
     const int L = e == 0 ? Lg : Ll;
     const std::string pre = e == 0 ? "enc_x." : "enc_xh.";
@@ -384,11 +397,11 @@ static void build_layers(sv_lgvae_plan* p) {
     // e4_mean | e4_sd as ONE dense GEMM with N = 2L (vae/model.py:41-42,:111-112)
     p->enc[e][3] = mk(pre + "head", 1, 1, F, 2 * L, 1, 1, SV_ACT_NONE, F, 2 * L, 1, pb + 6, true);
   }
-  for (int k = 0; k < 2; ++k) {
-    const int pb = 20 + k * 10;
-    const int Lz = k == 0 ? Lg + Ll : Ll;
+  for (int k = 0; k < p->ndec(); ++k) {
+    const int pb = d.global_only ? 0 : 20 + k * 10;
+    const int Lz = k == 0 ? p->lc() : Ll;
     const std::string pre = k == 0 ? "dec_x." : "dec_xh.";
-    p->dec[k][0] = mk(pre + "d1", 1, 1, Lz, F, 1, 1, SV_ACT_RELU, Lg + Ll, F, 0, pb + 0, true);
+    p->dec[k][0] = mk(pre + "d1", 1, 1, Lz, F, 1, 1, SV_ACT_RELU, p->lc(), F, 0, pb + 0, true);
     p->dec[k][1] = mk(pre + "d2", H / 8, W / 8, 128, 128, 4, 1, SV_ACT_RELU, 128, 128, 0, pb + 2, true);
     p->dec[k][2] = mk(pre + "d3", H / 4, W / 4, 128, 64, 4, 1, SV_ACT_RELU, 128, 64, 0, pb + 4, true);
     p->dec[k][3] = mk(pre + "d4", H / 2, W / 2, 64, 32, 6, 1, SV_ACT_RELU, 64, 32, 0, pb + 6, true);
@@ -505,10 +518,10 @@ static void build_prep_jobs(sv_lgvae_plan* p) {
       arena += (int64_t)F * L2;
     }
   };
-  for (int e = 0; e < 2; ++e)
+  for (int e = 0; e < 2 && !p->d.global_only; ++e)
     for (int l = 0; l < 4; ++l) do_layer(p->enc[e][l], l == 3);
   p->dec_block0 = blocks;
-  for (int k = 0; k < 2; ++k)
+  for (int k = 0; k < p->ndec(); ++k)
     for (int l = 0; l < 5; ++l) do_layer(p->dec[k][l], false);
   p->arena_elems = arena + 128;
   p->prep_blocks = blocks;
@@ -518,35 +531,36 @@ static void build_buffers(sv_lgvae_plan* p) {
   const sv_lgvae_desc& d = p->d;
   const int64_t B = d.B, H = d.H, W = d.W, es = (int64_t)p->esz();
   const int64_t F = (H / 8) * (W / 8) * 128;
-  const int Lg = d.global_latent, Ll = d.local_latent, Lc = Lg + Ll;
+  const int Lg = d.global_latent, Ll = d.local_latent, Lc = p->lc();
+  const bool go = d.global_only;           // GMVae: no x-hat network, no encoder of the plan's own -- none of their buffers
   p->ws_bytes = 0;
   p->add_buf("jobs", (int64_t)p->jobs.size() * sizeof(PrepJob));
   p->add_buf("warena", p->arena_elems * es);
   p->add_buf("wgrad_ws", SV_WGRAD_WS_BYTES * SV_WGRAD_MAX_MULTI * sv_lgvae_plan::SIDE_MAX);   // per side stream, per problem
   if (getenv("SV_DEFER_REDUCE")) p->add_buf("wslab", SV_WGRAD_WS_BYTES * SV_WGRAD_MAX_MULTI * 7);    // per tile-wgrad layer (e1 e2 e3 d2 d3 d4 d5) and problem: deferred reduces
   p->add_buf("polyfix_x", svk_poly_fix_ws_bytes((int)B, (int)H / 2, (int)W / 2));   // border terms of the polyphase head (poly_fix.hip)
-  p->add_buf("polyfix_xh", svk_poly_fix_ws_bytes((int)B, (int)H / 2, (int)W / 2));
+  if (!go) p->add_buf("polyfix_xh", svk_poly_fix_ws_bytes((int)B, (int)H / 2, (int)W / 2));
   {   // border terms of the per-class polyphase layers (d3, d4): one region per network, sized for the largest layer (the layers run one after the other)
     int64_t need = 256;
     for (int l = 2; l <= 4; ++l)
       if (p->dec[0][l].polyc) need = std::max<int64_t>(need, svg_polyc_fix_ws_bytes(&p->dec[0][l].d));
     p->add_buf("polycfix_x", need);
-    p->add_buf("polycfix_xh", need);
+    if (!go) p->add_buf("polycfix_xh", need);
     int64_t needd = 256;                                  // edge terms of the polyphase input gradients (d4, d5): one region per network
     for (int l = 2; l <= 4; ++l)
       if (svg_polyd(&p->dec[0][l].d)) needd = std::max<int64_t>(needd, svg_polyd_ws_bytes(&p->dec[0][l].d));
     p->add_buf("polyd_x", needd);
-    p->add_buf("polyd_xh", needd);
+    if (!go) p->add_buf("polyd_xh", needd);
     // polyphase weight gradients at fp32 (polyc_wgrad.hip): dW' + frame slabs per layer and network (the layers' launches may overlap across streams)
     for (int l = 2; l <= 4; ++l) {
       const int64_t fl = svk_polyc_wgrad_ws_floats(&p->dec[0][l].d);
       if (!fl) continue;
       p->add_buf("polycw" + std::to_string(l) + "_x", fl * 4);
-      p->add_buf("polycw" + std::to_string(l) + "_xh", fl * 4);
+      if (!go) p->add_buf("polycw" + std::to_string(l) + "_xh", fl * 4);
     }
   }
   p->add_buf("polyw_x", svk_poly_wgrad_ws_floats(32, SV_POLY_WGRAD_NWG) * 4);        // polyphase weight gradient of the head: dW', dbias', frame slabs
-  p->add_buf("polyw_xh", svk_poly_wgrad_ws_floats(32, SV_POLY_WGRAD_NWG) * 4);
+  if (!go) p->add_buf("polyw_xh", svk_poly_wgrad_ws_floats(32, SV_POLY_WGRAD_NWG) * 4);
   {   // K-slice slabs of the heads' forward and d1's input gradient (latent_gemm.hip): [S][B][N] fp32 per network
     const int64_t Fd = (H / 8) * (W / 8) * 128;
     // the four launches that write them -- heads of x / x-hat (N = 2 Lg / 2 Ll), d1's input gradient of decoder_x / decoder_x-hat (N = Lg + Ll / Ll) --
@@ -554,11 +568,13 @@ static void build_buffers(sv_lgvae_plan* p) {
     // per-problem split x N could exceed a product formed from two of them); the launch sites check the capacity again and fall back
     int64_t need = 0;
     for (const int64_t Nq : {2 * Lg, 2 * Ll, Lg + Ll, Ll}) {
+      if (go) break;
       const int64_t b = (int64_t)svk_nt_gemm_pick_splitk((int)B, (int)Nq, (int)Fd, 2) * B * Nq * 4;
       need = b > need ? b : need;
     }
+    if (go) need = (int64_t)svk_nt_gemm_pick_splitk((int)B, Lc, (int)Fd, 2) * B * Lc * 4;    // d1's input gradient only (N = Lg)
     p->add_buf("lat_ws_x", need);
-    p->add_buf("lat_ws_xh", need);
+    if (!go) p->add_buf("lat_ws_xh", need);
   }
   p->add_buf("dyn", sizeof(SvDynArgs));
   p->add_buf("losses", 8 * 4);
@@ -568,25 +584,30 @@ static void build_buffers(sv_lgvae_plan* p) {
   // when the size is a multiple of 256 B), so pointwise kernels can take both as one batch of 2B
   auto twin = [&](const char* kind, int64_t bytes_x, int64_t bytes_xh) {
     p->add_buf(std::string(kind) + "x", bytes_x);
-    p->add_buf(std::string(kind) + "xh", bytes_xh);
+    if (!go) p->add_buf(std::string(kind) + "xh", bytes_xh);
   };
   auto same = [&](const char* kind, int64_t bytes) { twin(kind, bytes, bytes); };
-  same("in8_", B * H * W * 8 * es);
-  same("a1_", B * (H / 2) * (W / 2) * 32 * es);
-  same("a2_", B * (H / 4) * (W / 4) * 64 * es);
-  same("a3_", B * F * es);
-  // zeroed every step by ONE memset (split-K / atomic accumulation targets): pre_x .. gz_xh are adjacent
-  twin("pre_", B * 2 * Lg * 4, B * 2 * Ll * 4);
-  twin("gz_", B * Lc * 4, B * Ll * 4);
-  twin("z_mean_", B * Lg * 4, B * Ll * 4);
-  twin("z_sig_", B * Lg * 4, B * Ll * 4);
-  twin("z_", B * Lg * 4, B * Ll * 4);
-  twin("eps_", B * Lg * 4, B * Ll * 4);
-  same("kl_", B * 4);
-  twin("ghead_", B * 2 * Lg * es, B * 2 * Ll * es);
-  same("ga3_", B * F * es);
-  same("ga2_", B * (H / 4) * (W / 4) * 64 * es);
-  same("ga1_", B * (H / 2) * (W / 2) * 32 * es);
+  p->add_buf("in8_x", B * H * W * 8 * es);
+  p->add_buf("in8_xh", B * H * W * 8 * es);      // (global_only too: the split pass and the staged augmentation write both halves of images6)
+  if (go) {
+    p->add_buf("gz_x", B * Lc * 4);              // dL/dz_x for the caller's encoder
+  } else {
+    same("a1_", B * (H / 2) * (W / 2) * 32 * es);
+    same("a2_", B * (H / 4) * (W / 4) * 64 * es);
+    same("a3_", B * F * es);
+    // zeroed every step by ONE memset (split-K / atomic accumulation targets): pre_x .. gz_xh are adjacent
+    twin("pre_", B * 2 * Lg * 4, B * 2 * Ll * 4);
+    twin("gz_", B * Lc * 4, B * Ll * 4);
+    twin("z_mean_", B * Lg * 4, B * Ll * 4);
+    twin("z_sig_", B * Lg * 4, B * Ll * 4);
+    twin("z_", B * Lg * 4, B * Ll * 4);
+    twin("eps_", B * Lg * 4, B * Ll * 4);
+    same("kl_", B * 4);
+    twin("ghead_", B * 2 * Lg * es, B * 2 * Ll * es);
+    same("ga3_", B * F * es);
+    same("ga2_", B * (H / 4) * (W / 4) * 64 * es);
+    same("ga1_", B * (H / 2) * (W / 2) * 32 * es);
+  }
   // decoders
   same("h1_", B * F * es);
   same("h2_", B * F * es);
@@ -912,7 +933,7 @@ static int run_wgrad_layer(sv_lgvae_plan* p, Layer& L, const void* x, const void
 static int phase_prep(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t st, hipStream_t early) {
   Scope sc(p, st, "prep_weights", 0, (double)p->nparams * (4 + 2.0 * p->esz()));
   const PrepJob* jobs = (const PrepJob*)p->bp("jobs");
-  if (!early) return svk_prep_weights(s->params, p->bp("warena"), p->d.dtype, jobs, (int)p->jobs.size(), p->prep_blocks, st);
+  if (!early || p->dec_block0 == 0) return svk_prep_weights(s->params, p->bp("warena"), p->d.dtype, jobs, (int)p->jobs.size(), p->prep_blocks, st);
   SV_TRY(svk_prep_weights(s->params, p->bp("warena"), p->d.dtype, jobs, (int)p->jobs.size(), p->prep_blocks - p->dec_block0, early, p->dec_block0));
   return svk_prep_weights(s->params, p->bp("warena"), p->d.dtype, jobs, (int)p->jobs.size(), p->dec_block0, st);
 }
@@ -928,6 +949,20 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
   bool pre_slabs = false;
   int pre_S[2] = {0, 0};
   int64_t pre_stride[2] = {0, 0};
+  const int nd = p->ndec();
+  if (do_enc && d.global_only) {
+    // GMVae: the caller's encoder_x is the only encoder -- this phase zeroes dz (split-K target of d1's input gradient) and fills in8_x
+    if (hipMemsetAsync(p->bp("gz_x"), 0, (size_t)p->bbytes("gz_x"), st) != hipSuccess) return (int)hipGetLastError();
+    p->gz_clean = true;
+    p->gz_zero_skipped = false;
+    p->dz_slabs = false;
+    p->dz_valid = false;
+    if (!(s->phases & SV_PHASE_INPUTS_STAGED)) {
+      Scope sc(p, st, "split_pad", 0, (double)B * H * W * (24 + 16.0 * p->esz()));
+      SV_TRY(svk_split_pad(s->images6, p->bp("in8_x"), p->bp("in8_xh"), dt, (int64_t)B * H * W, st));
+    }
+    do_enc = false;
+  }
   // (not needed once both split-K launches of this plan have gone through latent_gemm.hip's slabs: nothing accumulates into these buffers)
   if (do_enc && !(latent_gemm_on(p) && p->lat_head_ok && p->lat_d1_ok && !d.external_global_encoder)) {
     // the head pre-activations (split-K partial sums) and dz (split-K dgrad of d1) accumulate with atomics
@@ -1051,13 +1086,13 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
     {   // d1 differs between the twins (zcat vs local-only input): two shapes, one launch
       Layer* Ls[2] = {&p->dec[0][0], &p->dec[1][0]};
       void* ys[2] = {p->bp("h1_x"), p->bp("h1_xh")};
-      SV_TRY(run_fwd_layers(p, 2, Ls, zin, s->params, ys, st));
+      SV_TRY(run_fwd_layers(p, nd, Ls, zin, s->params, ys, st));
     }
     {
       Layer* Ls[2] = {&p->dec[0][1], &p->dec[1][1]};
       const void* xs[2] = {p->bp("h1_x"), p->bp("h1_xh")};
       void* ys[2] = {p->bp("h2_x"), p->bp("h2_xh")};
-      SV_TRY(run_fwd_layers(p, 2, Ls, xs, s->params, ys, st));
+      SV_TRY(run_fwd_layers(p, nd, Ls, xs, s->params, ys, st));
     }
     // d3..d5 consume the 2x bilinear upsample of the previous activation (vae/model.py:163-167).
     // Fused (bf16): the conv/wgrad tile staging interpolates from the low-res tensor, u2/u3/u4 are
@@ -1067,9 +1102,9 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
     static const char* out_name[3] = {"h3_", "h4_", "out6_"};
     for (int l = 0; l < 3; ++l) {
       Layer* Ls[2] = {&p->dec[0][2 + l], &p->dec[1][2 + l]};
-      const void* xs[2];
-      void* ys[2];
-      for (int k = 0; k < 2; ++k) {
+      const void* xs[2] = {nullptr, nullptr};
+      void* ys[2] = {nullptr, nullptr};
+      for (int k = 0; k < nd; ++k) {
         const std::string sfx = en[k];
         xs[k] = p->bp(lo_name[l] + sfx);
         ys[k] = p->bp(out_name[l] + sfx);
@@ -1086,11 +1121,11 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
         f.images6 = s->images6; f.gscale = 1.0f / (float)d.B; f.noout = (s->phases & SV_PHASE_NO_RECON) ? 1 : 0;
         f.grad[0] = p->bp("g5_x"); f.grad[1] = p->bp("g5_xh");
         f.part[0] = (float*)p->bp("nllpart_x"); f.part[1] = (float*)p->bp("nllpart_xh");
-        const int rc = run_fwd_layers(p, 2, Ls, xs, s->params, ys, st, &f);
+        const int rc = run_fwd_layers(p, nd, Ls, xs, s->params, ys, st, &f);
         if (rc == SV_OK) { p->nll_fused = true; continue; }
         if (rc != SV_E_UNSUPPORTED) return rc;
       }
-      SV_TRY(run_fwd_layers(p, 2, Ls, xs, s->params, ys, st));
+      SV_TRY(run_fwd_layers(p, nd, Ls, xs, s->params, ys, st));
     }
   }
   return SV_OK;
@@ -1107,15 +1142,17 @@ static int phase_loss(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool with_g
   if (from_parts) {
   } else {
     // algorithmic bytes: read x, m, log_scale (12 B/element) + write dm, dls (2 * esz B/element); both networks
-    Scope sc(p, st, "dlogistic_nll", 0, 2.0 * d.B * d.H * d.W * 3 * (12.0 + (with_grad ? 2.0 * p->esz() : 0.0)));
+    Scope sc(p, st, "dlogistic_nll", 0, p->ndec() * d.B * d.H * d.W * 3.0 * (12.0 + (with_grad ? 2.0 * p->esz() : 0.0)));
     auto zs = [&](const char* kind, int64_t esz) {
+      if (d.global_only) return (int64_t)0;          // (one network: no second record)
       return (int64_t)((char*)p->bp(std::string(kind) + "xh") - (char*)p->bp(std::string(kind) + "x")) / esz;
     };
     SV_TRY(svk_dlogistic_nll_multi(s->images6, 0, (const float*)p->bp("out6_x"), zs("out6_", 4), (float*)p->bp("nll_x"),
                                    zs("nll_", 4), with_grad ? p->bp("g5_x") : nullptr, zs("g5_", (int64_t)p->esz()), d.dtype,
-                                   1.0f / (float)d.B, d.B, d.H, d.W, (float*)p->bp("nllpart_x"), zs("nllpart_", 4), 2, st));
+                                   1.0f / (float)d.B, d.B, d.H, d.W, (float*)p->bp("nllpart_x"), zs("nllpart_", 4), p->ndec(), st));
   }
   const int HWp = d.H * d.W;
+  // (global_only: bp() of the absent x-hat / KL buffers is null -- finalize_losses reads those terms as zero)
   SV_TRY(svk_finalize_losses((const float*)p->bp("nll_x"), (const float*)p->bp("nll_xh"), (const float*)p->bp("kl_x"),
                              (const float*)p->bp("kl_xh"), d.B, d.beta, (float*)p->bp("losses"),
                              (float*)p->bp("metric_acc"), s->accumulate_metrics, st,
@@ -1125,9 +1162,10 @@ static int phase_loss(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool with_g
 }
 
 static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t st) {
+  const int nd = p->ndec();
   if (!p->gz_clean) {   // a second backward over the same forward: re-zero the split-K dz accumulators
     char* z0 = (char*)p->bp("gz_x");
-    char* z1 = (char*)p->bp("gz_xh") + p->bbytes("gz_xh");
+    char* z1 = p->d.global_only ? z0 + p->bbytes("gz_x") : (char*)p->bp("gz_xh") + p->bbytes("gz_xh");
     if (hipMemsetAsync(z0, 0, (size_t)(z1 - z0), st) != hipSuccess) return (int)hipGetLastError();
   }
   p->gz_clean = false;
@@ -1147,9 +1185,9 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
     Layer* Ls[2] = {&p->dec[0][li], &p->dec[1][li]};
     const void *gy[2], *gu[2];
     both(gy_name[l], gy); both(gu_name[l], gu);
-    const void* xin[2];
-    for (int k = 0; k < 2; ++k) xin[k] = p->bp(std::string(Ls[k]->d.ups_in ? lo_name[l] : hi_name[l]) + en[k]);
-    SV_TRY(run_wgrad_layers(p, 2, Ls, xin, gy, s->grads, st));
+    const void* xin[2] = {nullptr, nullptr};
+    for (int k = 0; k < nd; ++k) xin[k] = p->bp(std::string(Ls[k]->d.ups_in ? lo_name[l] : hi_name[l]) + en[k]);
+    SV_TRY(run_wgrad_layers(p, nd, Ls, xin, gy, s->grads, st));
     const void *lo[2], *gl[2];
     both(lo_name[l], lo); both(gl_name[l], gl);
     // the input gradient lands at the LOW-RES activation in one launch where the fused kernel exists (ResizeBilinearGrad +
@@ -1161,32 +1199,33 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
     //  default moved from 256 to 128)
     static const int adj_min = getenv("SV_RC_ADJ_MIN") ? atoi(getenv("SV_RC_ADJ_MIN")) : 128;
     int frc = SV_E_UNSUPPORTED;
-    if (Ls[0]->wdp_off >= 0 && Ls[1]->wdp_off >= 0) {
+    if (Ls[0]->wdp_off >= 0 && (nd == 1 || Ls[1]->wdp_off >= 0)) {
       // fp32: the polyphase form (polyd_dgrad.hip): conv-transpose + resize adjoint + ReLU gate as one stride-2 conv over dY, edge terms through a workspace
       const void* wp[2];
       void* ews[2] = {p->bp("polyd_x"), p->bp("polyd_xh")};
       double fl = 0, by = 0;
-      for (int k = 0; k < 2; ++k) {
+      for (int k = 0; k < nd; ++k) {
         wp[k] = (const char*)p->bp("warena") + Ls[k]->wdp_off * p->esz();
         fl += conv_flops(Ls[k]->d); by += conv_bytes(Ls[k]->d, 1, p->esz());
       }
       Scope sc(p, st, "dgrad." + Ls[0]->name.substr(Ls[0]->name.find('.') + 1), fl, by);
-      { double is = 0; for (int k = 0; k < 2; ++k) is += poly_issued(Ls[k]->d, 81, true); sc.issued(is); }
-      frc = svk_polyd_dgrad_multi(&Ls[0]->d, 2, gy, wp, lo, (void* const*)gl, ews, st);
+      { double is = 0; for (int k = 0; k < nd; ++k) is += poly_issued(Ls[k]->d, 81, true); sc.issued(is); }
+      frc = svk_polyd_dgrad_multi(&Ls[0]->d, nd, gy, wp, lo, (void* const*)gl, ews, st);
     }
-    if (frc == SV_E_UNSUPPORTED && Ls[0]->d.ups_in && Ls[1]->d.ups_in && !no_adj && 2 * B >= adj_min) frc = run_dgrad_layers(p, 2, Ls, gy, lo, (void* const*)gl, false, st, true);
+    if (frc == SV_E_UNSUPPORTED && Ls[0]->d.ups_in && (nd == 1 || Ls[1]->d.ups_in) && !no_adj && nd * B >= adj_min)
+      frc = run_dgrad_layers(p, nd, Ls, gy, lo, (void* const*)gl, false, st, true);
     if (frc != SV_E_UNSUPPORTED) { SV_TRY(frc); continue; }
     // ... else the hi-res gradient goes through HBM and a stand-alone adjoint pass
-    SV_TRY(run_dgrad_layers(p, 2, Ls, gy, none, (void* const*)gu, false, st));
+    SV_TRY(run_dgrad_layers(p, nd, Ls, gy, none, (void* const*)gu, false, st));
     {
       const int h = (H / 2) >> l, w = (W / 2) >> l, c = 32 << l;
       const int64_t lo_bytes = (int64_t)B * h * w * c * p->esz();
-      const bool contig = (const char*)gu[1] == (const char*)gu[0] + 4 * lo_bytes &&
+      const bool contig = nd == 2 && (const char*)gu[1] == (const char*)gu[0] + 4 * lo_bytes &&
                           (const char*)lo[1] == (const char*)lo[0] + lo_bytes && (const char*)gl[1] == (const char*)gl[0] + lo_bytes;
-      Scope sc(p, st, std::string("upsample_bwd.") + lo_name[l][1], 0, 2.0 * 6 * lo_bytes);   // read g_hi (4x) + mask, write g_lo; both networks
+      Scope sc(p, st, std::string("upsample_bwd.") + lo_name[l][1], 0, nd * 6.0 * lo_bytes);   // read g_hi (4x) + mask, write g_lo; both networks
       if (contig) SV_TRY(sv_upsample2x_bwd(gu[0], lo[0], (void*)gl[0], dt, 2 * B, h, w, c, st));
       else
-        for (int k = 0; k < 2; ++k) SV_TRY(sv_upsample2x_bwd(gu[k], lo[k], (void*)gl[k], dt, B, h, w, c, st));
+        for (int k = 0; k < nd; ++k) SV_TRY(sv_upsample2x_bwd(gu[k], lo[k], (void*)gl[k], dt, B, h, w, c, st));
     }
   }
   {
@@ -1194,8 +1233,8 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
     Layer* Ls[2] = {&p->dec[0][1], &p->dec[1][1]};
     const void *g2[2], *h1[2], *g1[2];
     both("g2_", g2); both("h1_", h1); both("g1_", g1);
-    SV_TRY(run_wgrad_layers(p, 2, Ls, h1, g2, s->grads, st));
-    SV_TRY(run_dgrad_layers(p, 2, Ls, g2, h1, (void* const*)g1, false, st));
+    SV_TRY(run_wgrad_layers(p, nd, Ls, h1, g2, s->grads, st));
+    SV_TRY(run_dgrad_layers(p, nd, Ls, g2, h1, (void* const*)g1, false, st));
   }
   {
     // d1 (dense): dz accumulated in fp32 over split K; the twins (different input widths) share the launches
@@ -1206,8 +1245,8 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
     const void *g1[2], *none2[2] = {nullptr, nullptr};
     void* gz[2] = {p->bp("gz_x"), p->bp("gz_xh")};
     both("g1_", g1);
-    SV_TRY(run_wgrad_layers(p, 2, Ls, zin, g1, s->grads, st));
-    for (int k = 0; k < 2; ++k) Ld[k].d.ldx = Ld[k].d.Cin;   // dz has its own row pitch (Lz), not the zcat pitch
+    SV_TRY(run_wgrad_layers(p, nd, Ls, zin, g1, s->grads, st));
+    for (int k = 0; k < nd; ++k) Ld[k].d.ldx = Ld[k].d.Cin;   // dz has its own row pitch (Lz), not the zcat pitch
     bool done = false;
     p->dz_slabs = false;
     p->dz_valid = true;
@@ -1215,7 +1254,7 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
       NtGemmProb q[2];
       float* outs[2];
       double fl = 0, by = 0;
-      for (int k = 0; k < 2; ++k) {
+      for (int k = 0; k < nd; ++k) {
         const sv_conv_desc& dd = Ld[k].d;
         NtGemmProb& g = q[k];
         memset(&g, 0, sizeof(g));
@@ -1231,7 +1270,7 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
         fl += conv_flops(dd); by += conv_bytes(dd, 1, p->esz());
       }
       Scope sc(p, st, "dgrad.d1", fl, by);
-      const int rc = svk_nt_gemm_multi(q, 2, 64, st);
+      const int rc = svk_nt_gemm_multi(q, nd, 64, st);
       if (rc == SV_OK) {
         done = true;
         p->lat_d1_ok = true;
@@ -1239,10 +1278,10 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
         if (latent_fuse_on() && !d.external_global_encoder && !no_twin && q[0].splitk <= 16 && q[1].splitk <= 16) {     // reparam_kl_bwd sums the slabs (SPLIT-GMVAE reads gz_x: summed here)
           p->dz_slabs = true;
           for (int k = 0; k < 2; ++k) { p->dz_S[k] = q[k].splitk; p->dz_stride[k] = q[k].slab_stride; }
-        } else SV_TRY(svk_nt_slab_reduce(q, outs, 2, st));
+        } else SV_TRY(svk_nt_slab_reduce(q, outs, nd, st));
       } else if (rc != SV_E_UNSUPPORTED) return rc;
     }
-    if (!done) SV_TRY(run_dgrad_layers(p, 2, Lds, g1, none2, gz, true, st));
+    if (!done) SV_TRY(run_dgrad_layers(p, nd, Lds, g1, none2, gz, true, st));
   }
   return SV_OK;
 }
@@ -1254,6 +1293,7 @@ static int phase_bwd_encoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, boo
   const char* en[2] = {"x", "xh"};
   const float kl_scale = d.beta / (float)B;
   const int e0 = d.external_global_encoder ? 1 : 0;
+  if (d.global_only) return SV_OK;            // GMVae: the only encoder is the caller's (it reads dL/dz_x from gz_x)
   if (do_heads && !p->dz_valid && p->gz_zero_skipped) {       // KL terms only (no decoder backward since the forward): dz = 0
     char* z0 = (char*)p->bp("gz_x");
     char* z1 = (char*)p->bp("gz_xh") + p->bbytes("gz_xh");
@@ -1398,14 +1438,15 @@ extern "C" int sv_lgvae_plan_create(const sv_lgvae_desc* d, sv_lgvae_plan** out)
   if (!out) return SV_E_BADARG;
   sv_lgvae_plan* p = new sv_lgvae_plan();
   p->d = *d;
+  if (p->d.global_only) p->d.local_latent = p->d.global_latent;   // (ignored in this mode: keep the derived sizes well defined)
   p->params = build_params(d);
   p->nparams = p->params.back().off + (p->params.back().count + 3) / 4 * 4;
   p->ws = nullptr; p->bound = false; p->prof_on = false;
   build_layers(p);
-  for (int e = 0; e < 2; ++e)
+  for (int e = 0; e < 2 && !p->d.global_only; ++e)
     for (int l = 0; l < 4; ++l)
       if ((rc = svg_check(&p->enc[e][l].d))) { delete p; return rc; }
-  for (int k = 0; k < 2; ++k)
+  for (int k = 0; k < p->ndec(); ++k)
     for (int l = 0; l < 5; ++l)
       if ((rc = svg_check(&p->dec[k][l].d))) { delete p; return rc; }
   build_prep_jobs(p);
@@ -1481,7 +1522,7 @@ static int run_phases(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t
     // (fp32, 256 images per network: 5.14 -> 5.09 ms; 128: 2.84 -> 2.87: from 256)
     // (round 6, with the process's fixed side streams: bf16 256 images per network 1.068-1.080 -> 1.054-1.056 ms with two: the bf16 threshold moved from 768 to 512 too;
     //  profiles/r06_sweep_bf16.txt)
-    p->side_use = forced > 0 ? forced : (whole && 2 * p->d.B >= 512) ? 2 : 1;
+    p->side_use = forced > 0 ? forced : (whole && p->ndec() * p->d.B >= 512) ? 2 : 1;
   }
   // early side work: the decoders' weight images and the gradient buffer's zero fill on side stream 0 beside the encoders' forward (see early_stream)
   const bool zero_here = (ph & SV_PHASE_LOSS) && s->grads;
@@ -1587,6 +1628,7 @@ extern "C" int sv_lgvae_step(sv_lgvae_plan* p, const sv_lgvae_step_args* s, void
 
 extern "C" int sv_lgvae_graph_enable(sv_lgvae_plan* p, int32_t enable) {
   if (!p) return SV_E_BADARG;
+  if (enable && p->d.global_only) return SV_E_UNSUPPORTED;   // GMVae steps interleave the caller's encoder between the plan's phases: no capture path
   p->graph_on = enable != 0;
   if (!enable) {
     for (auto& kv : p->graphs)

@@ -992,10 +992,12 @@ __global__ __launch_bounds__(256) void finalize_losses_kernel(float* __restrict_
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
     if (part_x) {
       float sx = 0.f, sh = 0.f;
-      for (int i = 0; i < P; ++i) { sx += part_x[(int64_t)b * P + i]; sh += part_xh[(int64_t)b * P + i]; }
-      nll_x[b] = sx; nll_xh[b] = sh;
+      for (int i = 0; i < P; ++i) { sx += part_x[(int64_t)b * P + i]; if (part_xh) sh += part_xh[(int64_t)b * P + i]; }
+      nll_x[b] = sx;
+      if (nll_xh) nll_xh[b] = sh;
     }
-    a[0] += nll_x[b]; a[1] += nll_xh[b]; a[2] += kl_x[b]; a[3] += kl_xh[b];
+    // (nll_xh / kl_x / kl_xh / part_xh null: a one-branch plan (GMVae) -- those terms are zero)
+    a[0] += nll_x[b]; a[1] += nll_xh ? nll_xh[b] : 0.f; a[2] += kl_x ? kl_x[b] : 0.f; a[3] += kl_xh ? kl_xh[b] : 0.f;
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) a[k] = wave_sum(a[k]);

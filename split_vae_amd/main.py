@@ -1,6 +1,7 @@
 """CLI mirror of vae/main.py:15-31 (same flag names and defaults) for the SPLIT-VAE path.
 
     python -m split_vae_amd.main --beta 120 --patch_size 8 --dataset celeba64 -no_label --synthetic
+    python -m split_vae_amd.main --model gmvae --beta 40 --patch_size 4       (GMVAE baseline, Table 2)
 
 Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout.
 """
@@ -40,6 +41,32 @@ def build_parser():
     return ap
 
 
+def make_model(model_name, config, input_shape):
+    """vae/main.py:63-73: the model and optimizer `--model` selects -> (model, optimizer)."""
+    from .model import LGVae
+    from .optimizer import Adam, ExponentialDecay
+    if model_name == 'lgvae':
+        model = LGVae(global_latent_dims=config.global_latent_dims, local_latent_dims=config.local_latent_dims,
+                      image_shape=input_shape, dtype=config.dtype, seed=config.seed)
+        optimizer = Adam(learning_rate=config.learning_rate)
+    elif model_name == 'lggmvae':                                       # vae/main.py:66-69
+        from .gm import LGGMVae
+        lr_schedule = ExponentialDecay(config.learning_rate, decay_steps=1000000, decay_rate=0.4, staircase=True)
+        optimizer = Adam(learning_rate=lr_schedule)
+        model = LGGMVae(global_latent_dims=config.global_latent_dims, local_latent_dims=config.local_latent_dims,
+                        image_shape=input_shape, y_size=config.y_size, tau=config.tau, dtype=config.dtype, seed=config.seed,
+                        dropout_in_training=config.gm_dropout == "tf2.1")
+    elif model_name == 'gmvae':                                         # vae/main.py:70-73
+        from .gmvae import GMVae
+        lr_schedule = ExponentialDecay(config.learning_rate, decay_steps=1000000, decay_rate=0.4, staircase=True)
+        optimizer = Adam(learning_rate=lr_schedule)
+        model = GMVae(global_latent_dims=config.global_latent_dims, image_shape=input_shape, y_size=config.y_size, tau=config.tau,
+                      dtype=config.dtype, seed=config.seed, dropout_in_training=config.gm_dropout == "tf2.1")
+    else:
+        raise ValueError("--model %s: expected lgvae, lggmvae or gmvae (vae/main.py:27)" % model_name)
+    return model, optimizer
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     from . import configure_hw_queues
@@ -49,8 +76,6 @@ def main(argv=None):
     print('Config:', config)
     from . import data, trainer
     from .augmentation import Augmentator
-    from .model import LGVae
-    from .optimizer import Adam
 
     augmentor = Augmentator(type=config.augmentation, size=config.patch_size, seed=config.seed)
     train_ds, test_ds, input_shape = data.get_dataset(config.dataset, config.batch_size, synthetic=config.synthetic,
@@ -69,20 +94,7 @@ def main(argv=None):
     else:
         train_ds = (augmentor.augment(x) for x in train_ds)             # vae/main.py:60-61
         test_batches = [augmentor.augment(x) for x in test_ds]
-    if args.model == 'lgvae':
-        model = LGVae(global_latent_dims=config.global_latent_dims, local_latent_dims=config.local_latent_dims,
-                      image_shape=input_shape, dtype=config.dtype, seed=config.seed)
-        optimizer = Adam(learning_rate=config.learning_rate)
-    elif args.model == 'lggmvae':                                       # vae/main.py:66-69
-        from .gm import LGGMVae
-        from .optimizer import ExponentialDecay
-        lr_schedule = ExponentialDecay(config.learning_rate, decay_steps=1000000, decay_rate=0.4, staircase=True)
-        optimizer = Adam(learning_rate=lr_schedule)
-        model = LGGMVae(global_latent_dims=config.global_latent_dims, local_latent_dims=config.local_latent_dims,
-                        image_shape=input_shape, y_size=config.y_size, tau=config.tau, dtype=config.dtype, seed=config.seed,
-                        dropout_in_training=config.gm_dropout == "tf2.1")
-    else:
-        raise NotImplementedError("--model %s: GMVae has no local branch and is outside the SPLIT path (SURVEY 8f)" % args.model)
+    model, optimizer = make_model(args.model, config, input_shape)
     model.summary()
     print('Training local-global autoencoder')
     return trainer.train_local_global_autoencoder(model, optimizer, config.dataset, train_ds, test_batches, config=config)

@@ -386,13 +386,14 @@ class LGVaePlan:
     """Native launch plan for LGVae.call / train_step_lg_vae (vae/model.py:189-200, vae/trainer.py:120-144)."""
 
     def __init__(self, B, H, W, global_latent=128, local_latent=128, beta=40.0, dtype=torch.bfloat16, device="cuda",
-                 external_global_encoder=False):
+                 external_global_encoder=False, global_only=False):
         lib = _lib.load()
         self.lib = lib
         self.device = torch.device(device)
         self.dtype = dtype
+        # global_only: GMVae's one branch (include/splitvae.h) -- decoder_x over the caller's z_x, no x-hat network
         self.desc = LGVaeDesc(B, H, W, global_latent, local_latent, sv_dtype(dtype), float(beta),
-                              1 if external_global_encoder else 0)
+                              1 if external_global_encoder else 0, 1 if global_only else 0)
         h = C.c_void_p()
         check(lib.sv_lgvae_plan_create(C.byref(self.desc), C.byref(h)), "sv_lgvae_plan_create")
         self.handle = h
@@ -482,10 +483,10 @@ class LGVaePlan:
 
 
 def param_table(desc):
-    """[(name, offset, shape)] of the 40 variables in Keras creation order."""
+    """[(name, offset, shape)] of the 40 variables in Keras creation order (the 10 of decoder_x for a global_only desc)."""
     lib = _lib.load()
     out = []
-    for i in range(40):
+    for i in range(10 if desc.global_only else 40):
         off, nd = C.c_int64(), C.c_int32()
         shp = (C.c_int64 * 4)()
         name = C.create_string_buffer(96)
@@ -528,6 +529,17 @@ def gm_metrics(nll_x, kl_x, nll_xh, kl_xh, y_kl, beta, alpha, out6):
     check(_lib.load().sv_gm_metrics(_p(nll_x), _p(kl_x), _p(nll_xh), _p(kl_xh), _p(y_kl), nll_x.numel(), float(beta), float(alpha),
                                     _p(out6), _stream()), "sv_gm_metrics")
     return out6
+
+
+def cluster_confusion(logits, labels_onehot, counts):
+    """counts[K, C] (int32, accumulated into) += the (argmax logits, argmax label) pairs of the rows (include/splitvae.h:
+    sv_cluster_confusion).  logits [B, >=K] / labels_onehot [B, >=C] fp32 rows."""
+    B = logits.shape[0]
+    K, C_ = counts.shape
+    assert labels_onehot.shape[0] == B and counts.dtype == torch.int32
+    check(_lib.load().sv_cluster_confusion(_p(logits), logits.shape[1], _p(labels_onehot), labels_onehot.shape[1], B, K, C_, _p(counts),
+                                           _stream()), "sv_cluster_confusion")
+    return counts
 
 
 def gumbel_softmax_fwd(logits, K, tau, y, y_lp, u=None, u_out=None, seed=0, step=0, sample_offset=0):

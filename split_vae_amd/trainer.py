@@ -70,10 +70,13 @@ def train_step(model, images, optimizer, eps=None, reducer=None, sample_offset=0
     reconstruction tensors (plan buffers out6_x / out6_xh) are dead and are not stored (SV_PHASE_NO_RECON); the training
     loop and bench.py run this way.  Losses, gradients and the update are identical either way."""
     from .gm import LGGMVae
+    from .gmvae import GMVae
     if isinstance(model, LGGMVae):
         raise TypeError("LGGMVae trains with gm.train_step_lg_gm_vae (vae/trainer.py:297-299 picks the step by model class)")
+    if isinstance(model, GMVae):
+        raise TypeError("GMVae trains with gmvae.train_step_gm_vae (vae/trainer.py:300-302 picks the step by model class)")
     if not isinstance(model, LGVae):
-        raise NotImplementedError("GMVae (no local branch) is outside the SPLIT path (SURVEY 8f)")
+        raise NotImplementedError("train_step runs LGVae models, got %s" % type(model).__name__)
     _check_images(model, images)
     B = images.shape[0]
     plan = model.plan(B)
@@ -166,9 +169,11 @@ def train_local_global_autoencoder(model, optimizer, dataset, train_dataset, tes
     """Loop of vae/trainer.py:72-421 for LGVae: train; every 10 000 steps (incl. step 0) evaluate
     on the test set and print the reference's report; stop after training_steps; save weights.
     The image grids of vae/visualizer.py are written by _write_grids (visualizer.py)."""
-    from . import gm
+    from . import gm, gmvae
     if isinstance(model, gm.LGGMVae):               # vae/trainer.py:294-302: the step functions follow the model class
         return _train_lggmvae(model, optimizer, train_dataset, test_dataset, config)
+    if isinstance(model, gmvae.GMVae):
+        return _train_gmvae(model, optimizer, train_dataset, test_dataset, config)
     RUN_NAME = datetime.now().strftime("%Y%m%d-%H%M%S")
     model.beta = float(config.beta)
     os.makedirs("models", exist_ok=True)
@@ -247,9 +252,10 @@ def _write_grids(model, test_dataset, config, run_dir, step):
 
 def _train_lggmvae(model, optimizer, train_dataset, test_dataset, config):
     """The same loop for LGGMVae (train_step_lg_gm_vae / test_step_lg_gm_vae, vae/trainer.py:146-173, :235-272): the five
-    training means + y_kl, evaluated every `log_every` steps; cluster accuracy needs labels and the probe classifier
-    (missing upstream) and is not reported."""
-    from . import gm
+    training means + y_kl, evaluated every `log_every` steps.  With labelled data the unsupervised cluster accuracy of
+    vae/trainer.py:315-349 is reported too: it needs only the labels and y_logits (linear_assignment, :40-68), not the probe
+    classifier whose weights are missing upstream (that blob blocks only the classifier metrics of test_step_lg_vae)."""
+    from . import gm, gmvae
     RUN_NAME = datetime.now().strftime("%Y%m%d-%H%M%S")
     model.beta, model.alpha = float(config.beta), float(config.alpha)
     os.makedirs("models", exist_ok=True)
@@ -266,11 +272,14 @@ def _train_lggmvae(model, optimizer, train_dataset, test_dataset, config):
             print('Training time: {:.2f}'.format(time.time() - start))
             start = time.time()
             te, n = None, 0
+            cluster = None
             for test_data in test_dataset:
                 timg = test_data[0] if config.label else test_data
                 t = gm.test_step_lg_gm_vae(model, timg)
                 te = t.clone() if te is None else te + t
                 n += 1
+                if config.label:
+                    cluster = _cluster_update(model, cluster, timg.shape[0], test_data[1])
             print('Testing time: {:.2f}'.format(time.time() - start))
             tr = (acc / n_acc).tolist()
             te = (te / max(n, 1)).tolist() if te is not None else [float('nan')] * 6
@@ -278,7 +287,63 @@ def _train_lggmvae(model, optimizer, train_dataset, test_dataset, config):
             for tag, v in (('', tr), ('Test ', te)):
                 print('            {}X Recon Loss: {:.4f}, {}X KLD loss: {:.4f}, {}X hat Recon Loss: {:.4f}, {}X hat KLD loss: {:.4f}, '
                       '{}Y KL loss: {:.4f}'.format(tag, v[0], tag, v[1], tag, v[2], tag, v[3], tag, v[4]))
+            if cluster is not None:
+                print('            Classifier cluster acc: {:.4f}'.format(cluster.result()))
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
+            acc, n_acc = None, 0
+            start = time.time()
+        if step >= config.training_steps:
+            print('Training done!')
+            break
+    return _save(model, RUN_NAME)
+
+
+def _cluster_update(model, cluster, B, labels):
+    """Add one test batch's (cluster, class) counts -- y_logits of the batch the model just evaluated -- on the device."""
+    from . import gmvae
+    if cluster is None:
+        cluster = gmvae.ClusterAccuracy(model.y_size, labels.shape[1], model.device)
+    cluster.update(model.encoder(B).buf["logits"], labels)
+    return cluster
+
+
+def _train_gmvae(model, optimizer, train_dataset, test_dataset, config):
+    """The loop for GMVae (train_step_gm_vae / test_step_gm_vae, vae/trainer.py:176-198, :277-294): x_recon, x_kl and y_kl means of
+    the training steps and of the test set every `log_every` steps, and the cluster accuracy of the test set when it is labelled
+    (vae/trainer.py:315-349).  No image grids: the reference writes none for GMVae (vae/trainer.py:386)."""
+    from . import gmvae
+    RUN_NAME = datetime.now().strftime("%Y%m%d-%H%M%S")
+    model.beta, model.alpha = float(config.beta), float(config.alpha)
+    os.makedirs("models", exist_ok=True)
+    acc, n_acc = None, 0
+    start = time.time()
+    log_every = int(config.get("log_every") or 10000)
+    for step, train_data in enumerate(train_dataset):
+        images = train_data[0] if config.label else train_data
+        m = gmvae.train_step_gm_vae(model, images, optimizer)
+        acc = m.clone() if acc is None else acc + m
+        n_acc += 1
+        if step % log_every == 0:
+            torch.cuda.synchronize()
+            print('Training time: {:.2f}'.format(time.time() - start))
+            start = time.time()
+            te, n, cluster = None, 0, None
+            for test_data in test_dataset:
+                timg = test_data[0] if config.label else test_data
+                t = gmvae.test_step_gm_vae(model, timg)
+                te = t.clone() if te is None else te + t
+                n += 1
+                if config.label:
+                    cluster = _cluster_update(model, cluster, timg.shape[0], test_data[1])
+            print('Testing time: {:.2f}'.format(time.time() - start))
+            tr = (acc / n_acc).tolist()
+            te = (te / max(n, 1)).tolist() if te is not None else [float('nan')] * 4
+            print('Training step {}'.format(step))
+            print('            X Recon Loss: {:.4f}, X KLD loss: {:.4f}, Total X loss: {:.4f}'.format(tr[0], tr[1], tr[0] + tr[1]))
+            print('            Test X Recon Loss: {:.4f}, Test X KLD loss: {:.4f}, Test Total X loss: {:.4f}'.format(te[0], te[1], te[0] + te[1]))
+            if cluster is not None:
+                print('            Classifier cluster acc: {:.4f}'.format(cluster.result()))
+            print('            Y KL train loss: {:.4f}, Y KL test loss: {:.4f}'.format(tr[2], te[2]))
             acc, n_acc = None, 0
             start = time.time()
         if step >= config.training_steps:
