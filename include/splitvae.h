@@ -182,9 +182,33 @@ int sv_spair_loss_dyn(int32_t mode, const float* a, const float* b, float* sums,
  * Replaces tf.keras.layers.Conv2D(padding='same') forward (vae/model.py:36-38,:153-156) and the
  * Conv2DBackpropInput / Conv2DBackpropFilter / BiasAddGrad / ReluGrad nodes of tape.gradient
  * (vae/trainer.py:137).  Dense layers (vae/model.py:41-42,:152) are the H=W=KH=KW=1 case.
- * Channel counts are padded to a multiple of 8 in the low-precision activation tensors. */
+ * Channel counts are padded to a multiple of 8 in the low-precision activation tensors.
+ *
+ * Accepted domain (anything else: SV_E_BADARG for malformed values, SV_E_UNSUPPORTED for valid layers without kernels):
+ *   B, H, W, Cin, Cout, KH, KW > 0; dtype SV_BF16 or SV_F32 (else SV_E_BADARG); stride 1, 2 or 3 and KH * KW <= 81 (else SV_E_UNSUPPORTED);
+ *   stride > 1: the stride divides H and W (SV_E_UNSUPPORTED); ldx >= Cin, ldx % 8 == 0 (SV_E_BADARG); r8(Cin) = Cin rounded up to 8 is a
+ *   power of two, i.e. Cin in 1..8, 9..16, 17..32, 33..64, ... (SV_E_UNSUPPORTED); ldy >= Cout, and ldy % 8 == 0 unless y_f32 (SV_E_BADARG);
+ *   ups_in: stride 1, H and W even (SV_E_UNSUPPORTED); B * H * W * ldx and B * OH * OW * r8(Cout) below 2^31 (SV_E_UNSUPPORTED).
+ *   Any extents and kernel shapes in that domain, KH != KW included: power-of-two grids run on the LDS-tile / row-ring kernels, other
+ *   extents on the im2col kernels.  The input gradients also need r8(Cout) to be a power of two (else they return SV_E_UNSUPPORTED).
+ *   ups_in forwards exist on the LDS-tile / row-ring kernels only (the im2col kernels read a materialised input): they also need
+ *   power-of-two H and W with H * W >= 16, Cout <= 16 or a multiple of 32, an 8-byte multiple of stored output bytes per pixel (y_f32 or
+ *   SV_F32 with Cout % 8 != 0: min(ldy, r8(Cout)) even) and a tile that fits the LDS; otherwise SV_E_UNSUPPORTED with nothing written --
+ *   upsample with sv_upsample2x_fwd and run the layer without ups_in.
+ * Input precondition: the pad channels [C, pitch) of every activation and gradient input (x, dy, relu masks) are zero.
+ * Output postcondition of the write-only outputs (y, the non-atomic dx, dx_lo): channels [C, min(pitch, r8(C))) are written as zeros
+ *   whatever the dtype; channels from r8(C) to the pitch are left untouched or zeroed (the split-K forwards zero the whole pitch first).
+ * Accumulators (dw, dbias, the fp32-atomic dx) are ADDED to, never assigned; the fp32-atomic dx leaves channels [Cin, ldx) untouched.
+ * A refused call (any return other than SV_OK, checked before anything is enqueued) leaves every output buffer untouched.
+ * Reproducibility under sv_set_deterministic(1): same inputs -> same bits, for the calls WITH their workspaces; without one, the polyphase
+ *   head's border terms (sv_conv2d_nhwc_fwd) and the tile weight gradients (sv_conv2d_nhwc_wgrad) are added with fp32 atomics; the weight
+ *   gradient of an x-packed thin head (stride 1, Cout <= 8, y_f32, W >= 32) folds its columns onto dw with atomics even with a workspace.
+ * SV_TRACE_DISPATCH=1 (read once per process): every successful call prints "sv_dispatch <op> <form>" to stderr, the form it launched --
+ *   fwd: row, tile, tile_packx, tile_s2d3, im2col, im2col_small, dense_splitk, conv_splitk, poly_ws, poly_atomic, polyc, polyc_direct;
+ *   dgrad: merged, multi_class, per_class, atomic_splitk; dgrad_lowres: lowres_row, lowres_polyd, lowres_unsupported (the refusal);
+ *   wgrad: wgrad_tile, wgrad_tile_f32, wgrad_roll, wgrad_e1, wgrad_e2, polyc_wgrad, poly_wgrad, wgrad_im2col; wgrad_poly: wgrad_tile, wgrad_p5. */
 typedef struct {
-  int32_t B, H, W;          /* input spatial size (power-of-two H, W) */
+  int32_t B, H, W;          /* input spatial size (see the accepted domain above) */
   int32_t Cin, Cout;        /* real channel counts (HWIO weight shape = [KH,KW,Cin,Cout]) */
   int32_t KH, KW, stride;   /* TF 'SAME' padding is implied: out=ceil(in/stride) */
   int32_t act;              /* sv_act fused into the forward epilogue */
@@ -212,6 +236,7 @@ int sv_conv2d_nhwc_fwd(const sv_conv_desc* d, const void* x, const void* w_fwd, 
  * they are added to y with atomics afterwards (same result, slower).  The fp32 upsample -> 6 x 6 conv layers with 32 output channels (d4) run per output-parity
  * class over the low-res tensor and need the workspace for their border terms; WITHOUT one the call runs the direct fused-resize form on a second
  * weight image that sv_conv2d_prep_weights keeps behind the class images (sv_conv2d_wprep_elems counts it) -- same result to fp32 rounding, 1.4x the time.
+ * A workspace smaller than sv_conv2d_fwd_workspace_bytes counts as none (never read or written): the same fallbacks.
  * Form selection is a pure function of the descriptor (and of the SV_NO_POLY* / SV_POLYC_K tuning variables, which must not change between
  * sv_conv2d_prep_weights and the calls that consume its images). */
 int64_t sv_conv2d_fwd_workspace_bytes(const sv_conv_desc* d);
@@ -236,7 +261,8 @@ int64_t sv_conv2d_dgrad_lowres_workspace_bytes(const sv_conv_desc* d);
 int sv_conv2d_nhwc_dgrad_lowres_ws(const sv_conv_desc* d, const void* dy, const void* w_dgrad, const void* relu_mask_lo, void* dx_lo,
                                    void* workspace, int64_t workspace_bytes, void* stream);
 /* dw[KH,KW,Cin,Cout] += x^T*dy, dbias[Cout] += colsum(dy) (fp32 HWIO, atomically accumulated:
- * zero them first). */
+ * zero them first).  ups_in layers off the model's decoder geometries may return SV_E_UNSUPPORTED (nothing written): upsample
+ * x with sv_upsample2x_fwd and call the plain layer instead. */
 int sv_conv2d_nhwc_wgrad(const sv_conv_desc* d, const void* x, const void* dy, float* dw,
                          float* dbias, void* stream);
 /* Same with a caller-owned partial-sum workspace (sv_conv2d_wgrad_workspace_bytes): the tile kernel
@@ -250,7 +276,9 @@ int sv_conv2d_nhwc_wgrad_ws(const sv_conv_desc* d, const void* x, const void* dy
  * weight gradient of the 5x5 low-res conv (no blend arithmetic, a quarter of the pixels staged), projected back onto the 6x6
  * kernel, minus the out-of-image taps of the five border rows / columns (tests/test_polyphase_math.py).  Same result
  * as sv_conv2d_nhwc_wgrad on the same layer to bf16 accuracy (closer to the fp64 gradient: the upsampled activations are never
- * rounded).  Workspace: sv_conv2d_wgrad_poly_workspace_bytes (0 = the layer has no polyphase form), ZEROED before its first use. */
+ * rounded).  Workspace: sv_conv2d_wgrad_poly_workspace_bytes (0 = the layer has no polyphase form), ZEROED before its first use.
+ * H and W must be multiples of 32 (the frame kernel takes border lines in 32-pixel chunks); otherwise SV_E_UNSUPPORTED and a workspace
+ * size of 0: use sv_conv2d_nhwc_wgrad_ws. */
 int64_t sv_conv2d_wgrad_poly_workspace_bytes(const sv_conv_desc* d);
 int sv_conv2d_nhwc_wgrad_poly(const sv_conv_desc* d, const void* x_lo, const void* dy, float* dw, float* dbias, void* workspace,
                               int64_t workspace_bytes, void* stream);

@@ -19,11 +19,11 @@ import torch.nn.functional as F
 from . import np_ref
 
 
-def _same_pad(x_nchw, k, s):
-    """TF SAME padding, asymmetric (extra on bottom/right) [TF-2.0 semantics]."""
+def _same_pad(x_nchw, k, s, kw=None):
+    """TF SAME padding, asymmetric (extra on bottom/right) [TF-2.0 semantics]; kw: the kernel width when it differs from k."""
     H, W = x_nchw.shape[2:]
     _, pt, pb = np_ref.same_pads(H, k, s)
-    _, pl, pr = np_ref.same_pads(W, k, s)
+    _, pl, pr = np_ref.same_pads(W, k if kw is None else kw, s)
     return F.pad(x_nchw, (pl, pr, pt, pb))
 
 
@@ -31,7 +31,7 @@ def conv2d_same(x_nhwc, w_hwio, b, stride, act=None):
     """Conv2D(padding='same') -- vae/model.py:36-38, :153-156."""
     x = x_nhwc.permute(0, 3, 1, 2)
     w = w_hwio.permute(3, 2, 0, 1)
-    y = F.conv2d(_same_pad(x, w_hwio.shape[0], stride), w, b, stride=stride)
+    y = F.conv2d(_same_pad(x, w_hwio.shape[0], stride, w_hwio.shape[1]), w, b, stride=stride)
     y = y.permute(0, 2, 3, 1)
     if act == 'relu':
         y = F.relu(y)

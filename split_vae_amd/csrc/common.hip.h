@@ -180,6 +180,21 @@ inline bool sv_deterministic() {
   return d;
 }
 
+// SV_TRACE_DISPATCH=1: every sv_conv2d_* call prints one line "sv_dispatch <op> <form>" to stderr naming the form it launched
+// (include/splitvae.h lists the names; tests/test_gpu_conv_api.py checks its cases against them).  The dispatchers record the form where
+// they launch it (sv_trace_note), the API entry prints it after a successful call.  Read once per process; unset, nothing is recorded.
+inline bool sv_trace_dispatch() {
+  static const bool on = getenv("SV_TRACE_DISPATCH") != nullptr;
+  return on;
+}
+inline const char*& sv_trace_form() {
+  static thread_local const char* f = nullptr;
+  return f;
+}
+inline void sv_trace_note(const char* form) {
+  if (sv_trace_dispatch()) sv_trace_form() = form;
+}
+
 // Timing-ablation bits (skip staging / the MFMA loop / stores: WRONG results, for profiling only) exist only in builds
 // with -DSV_DEBUG_KNOBS (SV_EXTRA_FLAGS=-DSV_DEBUG_KNOBS python split_vae_amd/build.py); the shipped library has none.
 #ifdef SV_DEBUG_KNOBS

@@ -445,7 +445,7 @@ bool svg_dgrad_merged_args(const sv_conv_desc* d, const int64_t* class_off, TapG
   return true;
 }
 
-void svg_wgrad_args(const sv_conv_desc* d, WgradArgs* a) {
+void svg_wgrad_args(const sv_conv_desc* d, WgradArgs* a, bool plain) {
   memset(a, 0, sizeof(*a));
   const int epp = svg_epp(d), cpad = svg_cin_pad(d);
   const int OH = svg_oh(d), OW = svg_ow(d);
@@ -460,7 +460,7 @@ void svg_wgrad_args(const sv_conv_desc* d, WgradArgs* a) {
   a->Cin_pad = cpad; a->Cin_real = d->Cin; a->N = d->Cout; a->ups = d->ups_in;
   a->ntaps = d->KH * d->KW;
   a->Nrows = a->ntaps * cpad;
-  if (svg_s2d3(d)) {
+  if (!plain && svg_s2d3(d)) {
     // space-to-depth form: 3 x 3 taps (y-major) over the 16-channel view; the reduce maps (tap, (py,px,c)) back to the [6][6][3][N] gradient (dw_index)
     a->IH = OH; a->IW = OW; a->lda = 16; a->S = 1; a->SX = 1; a->cl2 = 2;
     a->Cin_pad = 16; a->Cin_real = 12; a->ntaps = 9; a->Nrows = 144; a->s2d3 = 1;
@@ -469,7 +469,7 @@ void svg_wgrad_args(const sv_conv_desc* d, WgradArgs* a) {
     a->msplit = a->M;
     return;
   }
-  if (svg_packx(d)) {
+  if (!plain && svg_packx(d)) {
     // the x-packed conv's weight gradient: rows = pixel pairs, dY = the [B,H,W,8] gradient viewed as
     // [B,H,W/2,16]; the tile kernel folds dW' back into the HWIO gradient (the im2col kernel cannot)
     a->M = d->B * OH * (OW / 2);
@@ -801,14 +801,21 @@ static int svg_im2col_cfg(const TapGemmArgs& a, int cfg) {
   return tiles < 256 ? 4 : cfg;
 }
 
+// SV_TRACE_DISPATCH (common.hip.h): after a successful call, the line naming the form it launched (`form` null: the one the dispatcher recorded)
+static int svg_traced(int rc, const char* op, const char* form = nullptr) {
+  if (rc == SV_OK && sv_trace_dispatch()) fprintf(stderr, "sv_dispatch %s %s\n", op, form ? form : sv_trace_form() ? sv_trace_form() : "unknown");
+  return rc;
+}
+
 extern "C" int sv_conv2d_nhwc_fwd_ws(const sv_conv_desc* d, const void* x, const void* w_fwd, const float* bias, void* y,
                                      void* ws, int64_t ws_bytes, void* stream) {
   int rc = svg_check(d);
   if (rc != SV_OK) return rc;
   if (!x || !w_fwd || !y) return SV_E_BADARG;
+  sv_trace_note(nullptr);
   const bool polyc = svg_polyc(d);
   if (polyc && ws && ws_bytes >= svg_polyc_fix_ws_bytes(d))                    // the border terms travel through the workspace
-    return svk_polyc_fwd_multi(d, 1, &x, &w_fwd, &bias, &y, &ws, (hipStream_t)stream);
+    return svg_traced(svk_polyc_fwd_multi(d, 1, &x, &w_fwd, &bias, &y, &ws, (hipStream_t)stream), "fwd", "polyc");
   TapGemmArgs a;
   svg_fwd_args(d, &a);
   a.A = x; a.Wt = w_fwd; a.bias = bias; a.out = y;
@@ -824,7 +831,7 @@ extern "C" int sv_conv2d_nhwc_fwd_ws(const sv_conv_desc* d, const void* x, const
       if (sk > 1) {
         if (hipMemsetAsync(y, 0, (size_t)d->B * d->ldy * sizeof(float), (hipStream_t)stream) != hipSuccess) return (int)hipGetLastError();
         a.splitk = sk;
-        return svk_tap_gemm(a, d->dtype, cfg, (hipStream_t)stream);
+        return svg_traced(svk_tap_gemm(a, d->dtype, cfg, (hipStream_t)stream), "fwd", "dense_splitk");
       }
     }
     // fp32 conv layers whose output is a handful of tiles but whose K is deep (SPLIT-GMVAE's 128 -> 128 stride-2 layers at 64 images: 8 x 8 -> 4 x 4 pixels, K = 2048:
@@ -840,10 +847,11 @@ extern "C" int sv_conv2d_nhwc_fwd_ws(const sv_conv_desc* d, const void* x, const
       if (sk > 1) {
         if (hipMemsetAsync(y, 0, (size_t)a.M * d->ldy * sizeof(float), (hipStream_t)stream) != hipSuccess) return (int)hipGetLastError();
         a.splitk = sk; a.out_f32 = 1;
-        return svk_tap_gemm(a, d->dtype, cfg, (hipStream_t)stream);
+        return svg_traced(svk_tap_gemm(a, d->dtype, cfg, (hipStream_t)stream), "fwd", "conv_splitk");
       }
     }
-    return svk_conv_dispatch(a, d->dtype, svg_im2col_cfg(a, svg_pick_cfg(d->Cout)), (hipStream_t)stream);
+    rc = svk_conv_dispatch(a, d->dtype, svg_im2col_cfg(a, svg_pick_cfg(d->Cout)), (hipStream_t)stream);
+    return svg_traced(rc, "fwd", polyc ? "polyc_direct" : nullptr);
   }
   const void* wfix = (const char*)w_fwd + (int64_t)32 * 25 * svg_cin_pad(d) * (d->dtype == SV_BF16 ? 2 : 4);
   float* yf = (float*)y;
@@ -856,7 +864,7 @@ extern "C" int sv_conv2d_nhwc_fwd_ws(const sv_conv_desc* d, const void* x, const
   rc = svk_conv_dispatch(a, d->dtype, svg_pick_cfg(d->Cout), (hipStream_t)stream);
   if (rc == SV_OK && !fixbuf)
     rc = svk_poly_fix_multi(1, &x, &wfix, &yf, nullptr, d->B, d->H / 2, d->W / 2, d->ldx, d->Cout, (hipStream_t)stream, d->dtype);
-  return rc;
+  return svg_traced(rc, "fwd", fixbuf ? "poly_ws" : "poly_atomic");
 }
 
 extern "C" int sv_conv2d_nhwc_fwd(const sv_conv_desc* d, const void* x, const void* w_fwd, const float* bias,
@@ -873,6 +881,7 @@ extern "C" int sv_conv2d_nhwc_dgrad(const sv_conv_desc* d, const void* dy, const
   if (ilog2_exact(svg_gdy(d)) < 0) return SV_E_UNSUPPORTED;
   const size_t esz = d->dtype == SV_BF16 ? 2 : 4;
   int64_t off = 0;
+  sv_trace_note(nullptr);
   if (!dx_f32_atomic && svg_dgrad_classes(d) == 4) {      // classes with one shared window: one launch (cls_n)
     int64_t coff[4] = {0, 0, 0, 0};
     for (int c = 1; c < 4; ++c) coff[c] = coff[c - 1] + svg_wprep_elems_class(d, 1, c - 1);
@@ -880,7 +889,7 @@ extern "C" int sv_conv2d_nhwc_dgrad(const sv_conv_desc* d, const void* dy, const
     if (svg_dgrad_merged_args(d, coff, &a)) {
       a.A = dy; a.Wt = w_dgrad; a.out = dx; a.mask = relu_mask;
       rc = svk_conv_dispatch(a, d->dtype, svg_pick_cfg(a.N), (hipStream_t)stream);
-      if (rc != SV_E_UNSUPPORTED) return rc;
+      if (rc != SV_E_UNSUPPORTED) return svg_traced(rc, "dgrad", "merged");
     }
   }
   if (!dx_f32_atomic && svg_dgrad_classes(d) == 4) {       // (stride 2; SPLIT-SPAIR's stride-3 backbone layer has nine classes and stays on the per-class loop)
@@ -896,7 +905,7 @@ extern "C" int sv_conv2d_nhwc_dgrad(const sv_conv_desc* d, const void* dy, const
       o2 += svg_wprep_elems_class(d, 1, c);
     }
     rc = svk_conv_dispatch_multi(a, ncls, d->dtype, svg_im2col_cfg(a[0], svg_pick_cfg(d->Cin)), (hipStream_t)stream);
-    if (rc != SV_E_UNSUPPORTED) return rc;
+    if (rc != SV_E_UNSUPPORTED) return svg_traced(rc, "dgrad", "multi_class");
   }
   for (int c = 0; c < svg_dgrad_classes(d); ++c) {
     TapGemmArgs a;
@@ -913,7 +922,7 @@ extern "C" int sv_conv2d_nhwc_dgrad(const sv_conv_desc* d, const void* dy, const
     if (rc) return rc;
     off += svg_wprep_elems_class(d, 1, c);
   }
-  return SV_OK;
+  return svg_traced(SV_OK, "dgrad", dx_f32_atomic ? "atomic_splitk" : "per_class");
 }
 
 // Input gradient of a layer whose input is the 2x bilinear upsample of a low-res tensor (ups_in), delivered at the
@@ -929,7 +938,11 @@ extern "C" int sv_conv2d_nhwc_dgrad_lowres(const sv_conv_desc* d, const void* dy
   uint8_t srctap[SV_MAX_TAPS];
   svg_dgrad_args(d, 0, &a, srctap);
   a.A = dy; a.Wt = w_dgrad; a.out = dx_lo; a.mask = relu_mask_lo; a.adj = 1;
-  return svk_conv_dispatch(a, d->dtype, svg_pick_cfg(d->Cin), (hipStream_t)stream);
+  sv_trace_note(nullptr);
+  rc = svk_conv_dispatch(a, d->dtype, svg_pick_cfg(d->Cin), (hipStream_t)stream);
+  if (rc == SV_E_UNSUPPORTED && sv_trace_dispatch()) fprintf(stderr, "sv_dispatch dgrad_lowres lowres_unsupported\n");
+  // (the fused resize adjoint exists on the row-ring kernel only: tile_conv.hip)
+  return svg_traced(rc, "dgrad_lowres", sv_trace_form() && !strcmp(sv_trace_form(), "row") ? "lowres_row" : nullptr);
 }
 
 // The same with a workspace: layers with a polyphase input gradient (svg_polyd: the fp32 step's d4 / d5) deliver their edge terms through it.
@@ -944,9 +957,22 @@ extern "C" int sv_conv2d_nhwc_dgrad_lowres_ws(const sv_conv_desc* d, const void*
   if (!dy || !w_dgrad || !dx_lo) return SV_E_BADARG;
   if (svg_polyd(d) && workspace && workspace_bytes >= svg_polyd_ws_bytes(d)) {
     const void* wp = (const char*)w_dgrad + svg_polyd_base(d) * (d->dtype == SV_BF16 ? 2 : 4);
-    return svk_polyd_dgrad_multi(d, 1, &dy, &wp, &relu_mask_lo, &dx_lo, &workspace, (hipStream_t)stream);
+    return svg_traced(svk_polyd_dgrad_multi(d, 1, &dy, &wp, &relu_mask_lo, &dx_lo, &workspace, (hipStream_t)stream), "dgrad_lowres", "lowres_polyd");
   }
   return sv_conv2d_nhwc_dgrad_lowres(d, dy, w_dgrad, relu_mask_lo, dx_lo, stream);
+}
+
+// The weight gradient on the dispatcher; a space-to-depth (svg_s2d3) or x-packed (svg_packx) layer whose view has no tile kernel at this geometry
+// (or without the workspace its tile kernel needs) runs the im2col kernel on the plain form: the gradient does not depend on the forward's view
+static int svg_wgrad_launch(const sv_conv_desc* d, const WgradArgs& a, hipStream_t st) {
+  int rc = svk_wgrad_dispatch(a, d->dtype, svg_pick_cfg(d->Cout), st);
+  if (rc == SV_E_UNSUPPORTED && !d->ups_in && (a.s2d3 || a.fold_kw)) {
+    WgradArgs p;
+    svg_wgrad_args(d, &p, true);
+    p.A = a.A; p.dY = a.dY; p.dW = a.dW; p.dbias = a.dbias; p.ws = a.ws; p.ws_bytes = a.ws_bytes;
+    rc = svk_wgrad_dispatch(p, d->dtype, svg_pick_cfg(d->Cout), st);
+  }
+  return rc;
 }
 
 extern "C" int sv_conv2d_nhwc_wgrad(const sv_conv_desc* d, const void* x, const void* dy, float* dw,
@@ -957,7 +983,8 @@ extern "C" int sv_conv2d_nhwc_wgrad(const sv_conv_desc* d, const void* x, const 
   WgradArgs a;
   svg_wgrad_args(d, &a);
   a.A = x; a.dY = dy; a.dW = dw; a.dbias = dbias;
-  return svk_wgrad_dispatch(a, d->dtype, svg_pick_cfg(d->Cout), (hipStream_t)stream);
+  sv_trace_note(nullptr);
+  return svg_traced(svg_wgrad_launch(d, a, (hipStream_t)stream), "wgrad");
 }
 
 // Main term of the polyphase weight gradient of a svg_poly layer (poly_wgrad.hip, tests/test_polyphase_math.py):
@@ -980,24 +1007,26 @@ void svg_poly_wgrad_args(const sv_conv_desc* d, WgradArgs* a) {
 extern "C" int64_t sv_conv2d_wgrad_poly_workspace_bytes(const sv_conv_desc* d) {
   if (svg_check(d) != SV_OK) return -1;
   if (!svg_poly(d) || d->dtype != SV_BF16) return 0;         // (fp32: the x-packed weight gradient, sv_conv2d_nhwc_wgrad_ws)
+  if (!svk_poly_wgrad_supported(d->H / 2, d->W / 2, svg_cin_pad(d), d->Cout)) return 0;      // (its frame kernel: hi-res extents >= 32)
   return SV_WGRAD_WS_BYTES + svk_poly_wgrad_ws_floats(svg_cin_pad(d), SV_POLY_WGRAD_NWG) * 4;
 }
 extern "C" int sv_conv2d_nhwc_wgrad_poly(const sv_conv_desc* d, const void* x_lo, const void* dy, float* dw, float* dbias, void* workspace,
                                          int64_t workspace_bytes, void* stream) {
   int rc = svg_check(d);
   if (rc != SV_OK) return rc;
-  if (!svg_poly(d) || d->dtype != SV_BF16) return SV_E_UNSUPPORTED;
+  const int Cin = svg_cin_pad(d);
+  if (!svg_poly(d) || d->dtype != SV_BF16 || !svk_poly_wgrad_supported(d->H / 2, d->W / 2, Cin, d->Cout)) return SV_E_UNSUPPORTED;
   if (!x_lo || !dy || !dw || !workspace || workspace_bytes < sv_conv2d_wgrad_poly_workspace_bytes(d)) return SV_E_BADARG;
   float* pw = (float*)((char*)workspace + SV_WGRAD_WS_BYTES);
-  const int Cin = svg_cin_pad(d);
-  if (!svk_poly_wgrad_supported(d->H / 2, d->W / 2, Cin, d->Cout)) return SV_E_UNSUPPORTED;   // before anything is enqueued
   WgradArgs a;
   svg_poly_wgrad_args(d, &a);
+  sv_trace_note(nullptr);
   a.A = x_lo; a.dY = dy; a.dW = pw; a.dbias = pw + 25 * Cin * 32; a.ws = (float*)workspace; a.ws_bytes = SV_WGRAD_WS_BYTES;
   rc = svk_wgrad_tile(a, (hipStream_t)stream);
   if (rc) return rc;
-  return svk_poly_wgrad_finish(1, &x_lo, &dy, &pw, &dw, &dbias, d->B, d->H / 2, d->W / 2, d->ldx, Cin, d->Cout, SV_POLY_WGRAD_NWG,
-                               (hipStream_t)stream);
+  rc = svk_poly_wgrad_finish(1, &x_lo, &dy, &pw, &dw, &dbias, d->B, d->H / 2, d->W / 2, d->ldx, Cin, d->Cout, SV_POLY_WGRAD_NWG,
+                             (hipStream_t)stream);
+  return svg_traced(rc, "wgrad_poly");                   // (the main term's kernel: wgrad_tile or wgrad_p5)
 }
 
 // (layers with a polyphase weight gradient at fp32 -- polyc_wgrad.hip -- keep dW' and the frame slabs behind the partial-sum slabs)
@@ -1011,15 +1040,17 @@ extern "C" int sv_conv2d_nhwc_wgrad_ws(const sv_conv_desc* d, const void* x, con
   int rc = svg_check(d);
   if (rc != SV_OK) return rc;
   if (!x || !dy || !dw) return SV_E_BADARG;
+  sv_trace_note(nullptr);
   if (svg_polyc_wgrad_form(d) && workspace && workspace_bytes >= sv_conv2d_wgrad_workspace_bytes(d)) {
     float* slab = (float*)workspace;
     float* pw = (float*)((char*)workspace + SV_WGRAD_WS_BYTES);
     rc = svk_polyc_wgrad_multi(d, 1, &x, &dy, &dw, &dbias, &slab, SV_WGRAD_WS_BYTES, &pw, (hipStream_t)stream);
-    if (rc != SV_E_UNSUPPORTED) return rc;
+    if (rc != SV_E_UNSUPPORTED) return svg_traced(rc, "wgrad");      // (poly_wgrad / polyc_wgrad: recorded at the launch, polyc_wgrad.hip)
   }
   WgradArgs a;
   svg_wgrad_args(d, &a);
   a.A = x; a.dY = dy; a.dW = dw; a.dbias = dbias;
   a.ws = (float*)workspace; a.ws_bytes = workspace ? workspace_bytes : 0;
-  return svk_wgrad_dispatch(a, d->dtype, svg_pick_cfg(d->Cout), (hipStream_t)stream);
+  sv_trace_note(nullptr);
+  return svg_traced(svg_wgrad_launch(d, a, (hipStream_t)stream), "wgrad");
 }

@@ -214,9 +214,11 @@ static inline size_t poly_wgrad_frame_lds(int h, int w, int Cin) {
   const int L = 2 * (h > w ? h : w), LW = L + 5, PSL = Cin * 2 + 32;
   return (size_t)4 * LW * PSL + (size_t)6 * L * 32;
 }
-// the frame kernel's line buffers must fit the CU's LDS (160 KB on gfx950): low-res extents up to 128 at Cin = 32
+// the frame kernel's line buffers must fit the CU's LDS (160 KB on gfx950): low-res extents up to 128 at Cin = 32.  Its MFMA loop takes the
+// pixels of a border line in chunks of 32 (npos / 32) and has no remainder step: both hi-res extents must be multiples of 32 (a 16-pixel line
+// contributed nothing -- tests/test_gpu_conv_api.py, poly_16x32_bf16)
 bool svk_poly_wgrad_supported(int h, int w, int Cin, int Cout) {
-  return (Cin == 32 || Cin == 64) && Cout <= 8 && poly_wgrad_frame_lds(h, w, Cin) <= 160 * 1024;
+  return (Cin == 32 || Cin == 64) && Cout <= 8 && (2 * h) % 32 == 0 && (2 * w) % 32 == 0 && poly_wgrad_frame_lds(h, w, Cin) <= 160 * 1024;
 }
 
 // frame term + reduce + projection for n <= 2 twin problems.  ws[i] (floats, zero on first use): [dWp 25*Cin*32][dbp 32][gsum][slabs nwg]

@@ -359,6 +359,7 @@ int svk_polyc_wgrad_multi(const sv_conv_desc* d, int n, const void* const* x_lo,
     hipLaunchKernelGGL(polyc_frame_sum_kernel, dim3((per / 4 + 255) / 256, n), dim3(256), 0, st, fs, frame_groups(), per);
     SV_LAUNCH_CHECK();
   }
+  sv_trace_note(merged ? "poly_wgrad" : "polyc_wgrad");
   hipLaunchKernelGGL(polyc_wgrad_project_kernel, dim3((K * K * cin * d->Cout + 255) / 256, n), dim3(256), 0, st, pj);
   SV_LAUNCH_CHECK();
   return SV_OK;

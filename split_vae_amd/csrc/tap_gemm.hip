@@ -158,9 +158,10 @@ __global__ __launch_bounds__(256) void tap_gemm_kernel(const TapGemmMulti mg) {
 
   // ---- epilogue.  Operands swapped: D rows = channels, cols = GEMM rows, so a lane holds channels
   // n0 + j*16 + (lane>>4)*4 + {0..3} of row lane&15 of each fragment (see tile_conv.hip).
-  // columns stored: the real channels, and -- for a low-precision output whose channel count is not a multiple of 8 (SPAIR's
-  // 100-channel z3) -- the zero pad channels up to the tensor's 8-channel pitch (weight rows >= N are zero, the bias is skipped)
-  const int Nst = (!g.out_f32 && g.splitk == 1 && (g.N & 7)) ? min(g.ldo, (g.N + 7) & ~7) : g.N;
+  // columns stored: the real channels, and -- for an output whose channel count is not a multiple of 8 (SPAIR's 100-channel z3, a
+  // 6-channel fp32 head with a padded pitch) -- the zero pad channels [N, min(ldo, r8(N))) (weight rows >= N are zero, the bias is
+  // skipped).  Not for accumulating fp32 targets (their pad channels are the caller's) nor split-K (the output was zeroed first)
+  const int Nst = (!g.accum && g.splitk == 1 && (g.N & 7)) ? min(g.ldo, (g.N + 7) & ~7) : g.N;
   const int ncols = min(BN, Nst - n0);
   {
     // transposed through LDS into row-contiguous 16-B (8-B for narrow fp32 rows) stores; split-K
@@ -268,14 +269,14 @@ __global__ __launch_bounds__(256) void tap_gemm_kernel(const TapGemmMulti mg) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int n = n0 + j * 16 + lg * 4 + e;
-        if (n >= g.N) continue;
+        if (n >= Nst) continue;                          // (pad channels n >= N: zero weight rows, no bias)
         float v = acc[i][j][e];
         const int64_t o = pix * g.ldo + n;
         if (g.splitk > 1) {
           atomicAdd((float*)g.out + o, (g.bias && zi == 0) ? v + g.bias[n] : v);
           continue;
         }
-        if (g.bias) v += g.bias[n];
+        if (g.bias && n < g.N) v += g.bias[n];
         if (g.act == SV_ACT_RELU) v = fmaxf(v, 0.f);
         if (g.mask) v = to_f32(((const T*)g.mask)[o]) > 0.f ? v : 0.f;
         if (g.out_f32) ((float*)g.out)[o] = g.accum ? ((float*)g.out)[o] + v : v;

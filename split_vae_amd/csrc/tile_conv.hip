@@ -280,10 +280,10 @@ __global__ __launch_bounds__(64 * NW, tile_min_waves(BN, NW, YR, WR)) void tile_
   // 6-channel fp32 head), ReLU mask applied there.  (The first version stored 2-byte scalars and
   // re-loaded the bias per element behind a branch: 32 dependent global loads per tile, a 35 us floor.)
   const int oesz = g.out_f32 ? 4 : (int)sizeof(T);
-  // channels stored by this column tile: the real ones and -- when their bytes are not a multiple of the 8-byte store piece (a
-  // 3-channel input gradient: SPAIR's glimpse encoder) -- the zero pad channels up to the tensor's pitch (weight rows >= N are
-  // zero, the bias is skipped); the plan rejects layers whose pitch leaves no such room
-  const int Nst = (!g.d2s && !g.cls_n && ((g.N * oesz) & 7)) ? min(g.ldo, (g.N + 7) & ~7) : g.N;
+  // channels stored by this column tile: the real ones and, when N is not a multiple of 8, the pad channels [N, min(ldo, r8(N))) as
+  // zeros, at either output precision (weight rows >= N are zero, the bias is skipped): include/splitvae.h's output postcondition.
+  // The plan rejects layers whose stored bytes per pixel are not a multiple of the 8-byte store piece
+  const int Nst = (!g.d2s && !g.cls_n && (g.N & 7)) ? min(g.ldo, (g.N + 7) & ~7) : g.N;
   const int ncols = min(BN, Nst - n0);
   // x-packed conv (fp32 head): the 16 columns (px, co<8) become 2*C contiguous floats of output pixels 2*ox, 2*ox+1
   // (polyphase form, d2s_y: 32 columns (py, px, co<8) become two segments of 2*C floats: output rows 2*oy, 2*oy + 1)
@@ -544,7 +544,7 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
   if (OY * OX < 16) return false;                       // dense / tiny spatial: im2col path
   if (!t.d2s && !t.cls_n) {                             // the epilogue stores 8- / 16-byte pieces (see Nst in the kernel)
     const int oe = t.out_f32 ? 4 : (dtype == SV_BF16 ? 2 : 4);
-    const int nst = ((t.N * oe) & 7) ? (t.ldo < ((t.N + 7) & ~7) ? t.ldo : ((t.N + 7) & ~7)) : t.N;
+    const int nst = (t.N & 7) ? (t.ldo < ((t.N + 7) & ~7) ? t.ldo : ((t.N + 7) & ~7)) : t.N;
     if ((nst * oe) & 7) return false;
   }
   const int esz = dtype == SV_BF16 ? 2 : 4, epp = 16 / esz;
@@ -769,6 +769,9 @@ int svk_tile_conv_multi(const TileConvArgs* a, int n, int dtype, int cfg, hipStr
 
 int svk_tile_conv(const TileConvArgs& a, int dtype, int cfg, hipStream_t st) { return svk_tile_conv_multi(&a, 1, dtype, cfg, st); }
 
+// SV_TRACE_DISPATCH name of a problem on the LDS-tile kernel
+static const char* tile_form(const TapGemmArgs& t) { return t.s2d3 ? "tile_s2d3" : (t.d2s && !t.d2s_y) ? "tile_packx" : "tile"; }
+
 // n tap-GEMM problems of the same shape: one multi launch of the tile kernel when they all plan
 // to the same configuration, individual launches otherwise
 int svk_conv_dispatch_multi(const TapGemmArgs* t, int n, int dtype, int tap_cfg, hipStream_t st) {
@@ -779,7 +782,10 @@ int svk_conv_dispatch_multi(const TapGemmArgs* t, int n, int dtype, int tap_cfg,
   if (!force_tap && n <= 8) {                          // weights in registers, rows rolling through LDS (row_conv.hip takes one problem, the x / x-hat
                                                        // twins, or the up to eight class problems of a stride-2 layer's input gradient)
     const int rc = svk_row_conv_try(t, n, dtype, st);
-    if (rc != SV_E_UNSUPPORTED) return rc;
+    if (rc != SV_E_UNSUPPORTED) {
+      sv_trace_note("row");
+      return rc;
+    }
   }
   for (int i = 0; i < n; ++i)
     if (t[i].adj) return SV_E_UNSUPPORTED;            // the fused resize adjoint exists on the row-ring kernel only: the caller
@@ -792,7 +798,10 @@ int svk_conv_dispatch_multi(const TapGemmArgs* t, int n, int dtype, int tap_cfg,
     a[i].dbg = dbg;
     if (all_tile && i > 0 && (cfg[i] != cfg[0] || a[i].ntiles != a[0].ntiles || a[i].N != a[0].N)) all_tile = false;
   }
-  if (all_tile && !no_multi) return svk_tile_conv_multi(a, n, dtype, cfg[0], st);
+  if (all_tile && !no_multi) {
+    sv_trace_note(tile_form(t[0]));
+    return svk_tile_conv_multi(a, n, dtype, cfg[0], st);
+  }
   // none of them plans to the tile kernel (dense layers, 1x1 grids): im2col GEMMs, SV_TAP_MAX_MULTI per launch
   bool none_tile = !no_multi && n > 1;
   for (int i = 0; i < n && none_tile; ++i) {
@@ -801,6 +810,7 @@ int svk_conv_dispatch_multi(const TapGemmArgs* t, int n, int dtype, int tap_cfg,
     none_tile = !(t[i].ups || t[i].d2s || t[i].cls_n || t[i].clampin || t[i].fix_nc || t[i].s2d3) && (force_tap || !svk_tile_conv_plan(t[i], dtype, t[i].M / (t[i].OY * t[i].OX), &b, &c));
   }
   if (none_tile) {
+    sv_trace_note(tap_cfg == 4 ? "im2col_small" : "im2col");
     for (int i = 0; i < n; i += SV_TAP_MAX_MULTI) {
       const int rc = svk_tap_gemm_multi(t + i, n - i < SV_TAP_MAX_MULTI ? n - i : SV_TAP_MAX_MULTI, dtype, tap_cfg, st);
       if (rc) return rc;
@@ -813,10 +823,12 @@ int svk_conv_dispatch_multi(const TapGemmArgs* t, int n, int dtype, int tap_cfg,
     int c;
     if (!force_tap && svk_tile_conv_plan(t[i], dtype, t[i].M / (t[i].OY * t[i].OX), &b, &c)) {
       b.dbg = dbg;
+      sv_trace_note(tile_form(t[i]));
       rc = svk_tile_conv(b, dtype, c, st);
     } else if (t[i].ups || t[i].d2s || t[i].cls_n || t[i].clampin || t[i].fix_nc || t[i].s2d3) {
       rc = SV_E_UNSUPPORTED;               // the im2col kernel needs the materialised hi-res tensor / has no depth-to-space store
     } else {
+      sv_trace_note(tap_cfg == 4 ? "im2col_small" : "im2col");
       rc = svk_tap_gemm(t[i], dtype, tap_cfg, st);
     }
     if (rc) return rc;

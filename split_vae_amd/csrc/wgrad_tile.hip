@@ -786,10 +786,10 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
   static const bool force_old = getenv("SV_FORCE_IM2COL") != nullptr;
   static const char* skip = getenv("SV_WGRAD_IM2COL_IDS");    // e.g. "23": these layer ids use the im2col kernel (A/B)
   if (force_old || w.lOY < 0 || w.lOX < 0 || w.S > 2) return SV_E_UNSUPPORTED;   // power-of-two grids, stride <= 2
-  if (svk_wgrad_roll_supported(wv, n)) return svk_wgrad_roll_multi(wv, n, st);
-  if (svk_wgrad_p5_supported(wv, n)) return svk_wgrad_p5_multi(wv, n, st);
-  if (svk_wgrad_e1_supported(wv, n)) return svk_wgrad_e1_multi(wv, n, st);
-  if (svk_wgrad_e2_supported(wv, n)) return svk_wgrad_e2_multi(wv, n, st);
+  if (svk_wgrad_roll_supported(wv, n)) { sv_trace_note("wgrad_roll"); return svk_wgrad_roll_multi(wv, n, st); }
+  if (svk_wgrad_p5_supported(wv, n)) { sv_trace_note("wgrad_p5"); return svk_wgrad_p5_multi(wv, n, st); }
+  if (svk_wgrad_e1_supported(wv, n)) { sv_trace_note("wgrad_e1"); return svk_wgrad_e1_multi(wv, n, st); }
+  if (svk_wgrad_e2_supported(wv, n)) { sv_trace_note("wgrad_e2"); return svk_wgrad_e2_multi(wv, n, st); }
   const int OY = 1 << w.lOY, OX = 1 << w.lOX;
   if (OY * OX < 16 || w.ycols != w.ldy || (w.ups && w.S != 1)) return SV_E_UNSUPPORTED;
   const int cin = w.Cin_pad, cout = w.ldy, nt = w.ntaps;
@@ -883,6 +883,7 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
     av[i].ws = allow_slab ? wv[i].ws : nullptr; av[i].ws_bytes = allow_slab ? wv[i].ws_bytes : 0;
     av[i].defer = wv[i].defer; av[i].n_defer = wv[i].n_defer;
   }
+  sv_trace_note("wgrad_tile");
   // <TPW, CIF, COF, KC>
   switch (id) {
     case 0: if (KC == 8) return launch_wt<9, 2, 1, 8>(av, n, groups, st, wv[0].ev_mid); break;
@@ -951,8 +952,12 @@ int svk_wgrad_dispatch(const WgradArgs& w, int dtype, int cfg, hipStream_t st) {
   }
   if (dtype == SV_F32) {
     const int rc = svk_wgrad_tile_f32_multi(&w, 1, st);
-    if (rc != SV_E_UNSUPPORTED) return rc;
+    if (rc != SV_E_UNSUPPORTED) {
+      sv_trace_note("wgrad_tile_f32");
+      return rc;
+    }
   }
   if (w.ups || w.fold_kw || w.s2d3 || w.clampin || w.dy_os || w.dy_s2d) return SV_E_UNSUPPORTED;    // the im2col kernel needs the materialised hi-res tensor / cannot fold / reads no views
+  sv_trace_note("wgrad_im2col");
   return svk_wgrad(w, dtype, cfg, st);
 }

@@ -271,3 +271,57 @@ def test_tape_lane_schedule_without_gpu(lib_built):
     assert bwd[4] == ([], 0) and bwd[3][0] == [] and bwd[2] == ([], 1) and bwd[1] == ([2], 1) and bwd[0] == ([1], 0), bwd
     assert lib.sv_tape_schedule(h, 2, 0, None, 0, None) == _lib.STATUS_BADARG and lib.sv_tape_schedule(h, 0, 5, None, 0, None) == _lib.STATUS_BADARG
     lib.sv_tape_destroy(h)
+
+
+def _conv_domain_rule(B, H, W, Cin, Cout, KH, KW, s, dtype, ldx, ldy, y_f32, ups):
+    """include/splitvae.h's accepted domain of sv_conv_desc, as worded there: 0, SV_E_BADARG (-1) or SV_E_UNSUPPORTED (-2)"""
+    if min(B, H, W, Cin, Cout, KH, KW) <= 0 or dtype not in (0, 1):
+        return -1
+    if s not in (1, 2, 3) or KH * KW > 81:
+        return -2
+    if s > 1 and (H % s or W % s):
+        return -2
+    if ldx < Cin or ldx % 8:
+        return -1
+    r8 = (Cin + 7) // 8 * 8
+    if r8 & (r8 - 1):
+        return -2
+    if ldy < Cout or (not y_f32 and ldy % 8):
+        return -1
+    if ups and (s != 1 or H % 2 or W % 2):
+        return -2
+    OH, OW = -(-H // s), -(-W // s)
+    if B * H * W * ldx >= 1 << 31 or B * OH * OW * ((Cout + 7) // 8 * 8) >= 1 << 31:
+        return -2
+    return 0
+
+
+def test_conv_accepted_domain_matches_the_header(lib_built):
+    """host-only queries (no device work): a grid of descriptors through sv_conv2d_wprep_elems / the workspace-size queries, which answer
+    -1 exactly for the descriptors the header's rule refuses, against a Python statement of that rule"""
+    import itertools
+    from split_vae_amd import _lib
+    lib = _lib.load()
+    n = 0
+    grid = itertools.product((1, 3), ((16, 16), (16, 32), (12, 20), (24, 12), (15, 16), (1, 1)), (1, 3, 5, 12, 17, 30, 60), (1, 6, 10, 48),
+                             ((3, 3), (3, 5), (6, 6), (9, 10)), (1, 2, 3, 4), (0, 1), (0, 8, 12), (0, 1), (0, 1))
+    for B, (H, W), Cin, Cout, (KH, KW), s, dtype, ldx_over, y_f32, ups in grid:
+        ldx = (Cin + 7) // 8 * 8 + ldx_over
+        ldy = Cout if y_f32 else (Cout + 7) // 8 * 8
+        d = _lib.ConvDesc(B, H, W, Cin, Cout, KH, KW, s, 0, dtype, ldx, ldy, y_f32, ups)
+        ok = _conv_domain_rule(B, H, W, Cin, Cout, KH, KW, s, dtype, ldx, ldy, y_f32, ups) == 0
+        got = [lib.sv_conv2d_wprep_elems(C.byref(d), 0), lib.sv_conv2d_wprep_elems(C.byref(d), 1), lib.sv_conv2d_fwd_workspace_bytes(C.byref(d)),
+               lib.sv_conv2d_wgrad_workspace_bytes(C.byref(d)), lib.sv_conv2d_dgrad_lowres_workspace_bytes(C.byref(d)),
+               lib.sv_conv2d_wgrad_poly_workspace_bytes(C.byref(d))]
+        if ok:
+            assert got[0] > 0 and got[1] > 0 and min(got[2:]) >= 0, (B, H, W, Cin, Cout, KH, KW, s, dtype, ldx, ldy, y_f32, ups, got)
+        else:
+            assert got == [-1] * 6, (B, H, W, Cin, Cout, KH, KW, s, dtype, ldx, ldy, y_f32, ups, got)
+        n += ok
+    assert n > 1000
+    # malformed values the grid does not reach
+    for kw in (dict(B=0), dict(Cin=0), dict(KH=0), dict(dtype=7), dict(ldy=4), dict(ldx=4)):
+        f = dict(B=2, H=16, W=16, Cin=8, Cout=8, KH=3, KW=3, stride=1, act=0, dtype=1, ldx=8, ldy=8, y_f32=0, ups_in=0)
+        f.update(kw)
+        d = _lib.ConvDesc(*[f[k] for k in ("B", "H", "W", "Cin", "Cout", "KH", "KW", "stride", "act", "dtype", "ldx", "ldy", "y_f32", "ups_in")])
+        assert lib.sv_conv2d_wprep_elems(C.byref(d), 0) == -1, kw
