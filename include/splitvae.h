@@ -53,6 +53,48 @@ int sv_scramble_gather_staged(const float* x, const int32_t* perm, float* images
 int sv_random_perm(int32_t* perm, int32_t B, int32_t n_patch, uint64_t seed, uint64_t step,
                    int64_t sample_offset, void* stream);
 
+/* ---------------------------------------------------------------- A1b: blur, high/low pass, mixed-size scramble
+ * The other augmentations of Augmentator (augmentation.py:12-30), per image in fp32 NHWC, batched on the device.
+ * Gaussian filter (augmentation.py:33-38, :83-101): low = depthwise cross-correlation of pad(x, r, SYMMETRIC) with
+ * K = outer(v, v) / sum(outer(v, v)), v = Normal(mean, std).prob(-r..r), VALID -- run separably (row pass, column pass) in
+ * fp32 with the taps formed in fp32, every sum in one fixed order (bit-reproducible).  SYMMETRIC mirrors including the edge
+ * pixel (-1 -> 0, H -> H-1).  All filter entries: SV_E_BADARG for a null pointer or B, H, W <= 0 or a radius < 0;
+ * SV_E_UNSUPPORTED for H != W, a radius > H or > 64, or (2r+1)*W*24 bytes above the 64 KiB of LDS a workgroup stages.
+ * The _staged forms also write the plan's in8_x / in8_xh (channels 0-2 and 3-5, zero padded to 8, sv_dtype `dtype`):
+ * the contract of sv_scramble_gather_staged, passed to the step as SV_PHASE_INPUTS_STAGED. */
+/* gaussian_blur (augmentation.py:83-94): images6[B,H,W,6] = [x | blur(x)], radius[B] int32 and std[B] fp32 device arrays
+ * (sv_blur_params draws them); a radius outside [0, max_radius] is clamped to it. */
+int sv_gauss_blur(const float* x, const int32_t* radius, const float* std, float* images6, int32_t B, int32_t H, int32_t W,
+                  int32_t max_radius, void* stream);
+int sv_gauss_blur_staged(const float* x, const int32_t* radius, const float* std, float* images6, void* x8, void* xh8, int32_t dtype,
+                         int32_t B, int32_t H, int32_t W, int32_t max_radius, void* stream);
+/* high_low_pass (augmentation.py:23-28, :97-101): one fixed kernel of radius `size` (--patch_size), Normal(mean, std);
+ * images9[B,H,W,9] = [x | x - low | low].  std <= 0: SV_E_BADARG. */
+int sv_high_low_pass(const float* x, float* images9, int32_t B, int32_t H, int32_t W, int32_t size, float mean, float std,
+                     void* stream);
+int sv_high_low_pass_staged(const float* x, float* images9, void* x8, void* xh8, int32_t dtype, int32_t B, int32_t H, int32_t W,
+                            int32_t size, float mean, float std, void* stream);
+/* augmentation.py:86-87: radius[b] ~ U{3,4,5,6}, std[b] ~ U[5,10), from the Philox stream keyed by (seed, step, global sample
+ * index = sample_offset + b) like sv_random_perm: a shard at sample_offset draws the rows of the single-process batch. */
+int sv_blur_params(int32_t* radius, float* std, int32_t B, uint64_t seed, uint64_t step, int64_t sample_offset, void* stream);
+/* augmentation.py:40-41,65 (np.random.choice([1, 2, 4, 8])): sizes[b] for the per-image mixed scramble, keyed as above. */
+int sv_mix_sizes(int32_t* sizes, int32_t B, uint64_t seed, uint64_t step, int64_t sample_offset, void* stream);
+/* The same draw on the host, for (seed, step, sample): the one patch size of a whole pipeline (the reference draws it once,
+ * when Dataset.map traces mix_scramble).  Needs no device. */
+int32_t sv_mix_size_host(uint64_t seed, uint64_t step, int64_t sample);
+/* mix_scramble's tf.random.shuffle (augmentation.py:74) with a size per image: row b of perm (row stride ld) is the
+ * sv_random_perm permutation of (H/sizes[b])^2 patches, same keys.  sizes[b] must divide H with (H/sizes[b])^2 <= min(ld, 4096);
+ * a row whose size does not is left unwritten.  SV_E_BADARG for a null pointer or B, H, ld <= 0. */
+int sv_random_perm_mixed(int32_t* perm, const int32_t* sizes, int32_t B, int32_t H, int32_t ld, uint64_t seed, uint64_t step,
+                         int64_t sample_offset, void* stream);
+/* mix_scramble's gather (augmentation.py:70-81) with a size per image: images6[B,H,W,6] = [x | x_aug], the patches of image b
+ * sizes[b] square, perm as sv_random_perm_mixed writes it.  An image whose size is invalid (see above) or whose permutation
+ * entry is out of range copies x through.  SV_E_BADARG for a null pointer or sizes <= 0; SV_E_UNSUPPORTED for H != W. */
+int sv_scramble_gather_mixed(const float* x, const int32_t* perm, const int32_t* sizes, int32_t ld, float* images6, int32_t B,
+                             int32_t H, int32_t W, void* stream);
+int sv_scramble_gather_mixed_staged(const float* x, const int32_t* perm, const int32_t* sizes, int32_t ld, float* images6, void* x8,
+                                    void* xh8, int32_t dtype, int32_t B, int32_t H, int32_t W, void* stream);
+
 /* ---------------------------------------------------------------- A6: discretised logistic NLL
  * Replaces discretised_logistic_loss (vae/trainer.py:21-38) + reduce_sum[1,2,3] (:127-128) and,
  * when grad != NULL, its adjoint under tape.gradient (:137).

@@ -91,6 +91,16 @@ SYMBOLS = {
     "sv_scramble_gather": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "sv_scramble_gather_staged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "sv_random_perm": (C.c_int, [_vp, _i32, _i32, _u64, _u64, _i64, _vp]),
+    "sv_gauss_blur": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "sv_gauss_blur_staged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "sv_high_low_pass": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _f, _f, _vp]),
+    "sv_high_low_pass_staged": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f, _f, _vp]),
+    "sv_blur_params": (C.c_int, [_vp, _vp, _i32, _u64, _u64, _i64, _vp]),
+    "sv_mix_sizes": (C.c_int, [_vp, _i32, _u64, _u64, _i64, _vp]),
+    "sv_mix_size_host": (C.c_int32, [_u64, _u64, _i64]),
+    "sv_random_perm_mixed": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _u64, _u64, _i64, _vp]),
+    "sv_scramble_gather_mixed": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "sv_scramble_gather_mixed_staged": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "sv_dlogistic_nll": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _f, _i32, _i32, _i32, _vp, _vp]),
     "sv_dlogistic_nll_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "sv_reparam_kl_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32,

@@ -191,6 +191,22 @@ def _check_images(model, images):
     check(model, images)
 
 
+def _images6(images):
+    """A 9-channel high_low_pass batch (x | x - low | low, augmentation.py:97-101) as the [B,H,W,6] batch the plan reads: GMVae
+    reads channels 0-2 only (vae/model.py:289), so the first six channels carry everything it uses.  The staging marks of
+    Augmentator.high_low_pass(..., plan=) move to the copy (its in8_x holds channels 0-2 of this batch).  Any other batch is
+    returned as it is."""
+    if not torch.is_tensor(images) or images.dim() != 4 or images.shape[-1] != 9:
+        return images
+    out = images[..., :6].contiguous()
+    plan = getattr(images, "_sv_staged_plan", None)
+    if plan is not None:
+        if images._sv_staged_gen == plan.in8_gen and images._sv_staged_version == images._version:
+            out._sv_staged_plan, out._sv_staged_gen, out._sv_staged_version = plan, plan.in8_gen, out._version
+        images._sv_staged_plan = None                         # one step per staging
+    return out
+
+
 def _metrics(model, plan, enc, B):
     """x_recon, x_kl, y_kl and the total of vae/trainer.py:184-190 from the per-image terms, as a [4] fp32 device tensor."""
     z = model._zero_terms(B)
@@ -201,9 +217,11 @@ def _metrics(model, plan, enc, B):
 
 def train_step_gm_vae(model, images, optimizer, eps=None, noise=None, sample_offset=0):
     """train_step_gm_vae (vae/trainer.py:176-198): total = recon_x + beta * KL(q_x || p_y) + alpha * KL(softmax(y_logits) || uniform);
-    gradients of the 34 variables; Adam; returns [x_recon, x_kl, y_kl, total] (GM_LOSS_KEYS) as a device tensor.  `images` [B,H,W,6] fp32."""
+    gradients of the 34 variables; Adam; returns [x_recon, x_kl, y_kl, total] (GM_LOSS_KEYS) as a device tensor.  `images` [B,H,W,6] fp32
+    (or the [B,H,W,9] of high_low_pass: its first six channels)."""
     if not isinstance(model, GMVae):
         raise TypeError("train_step_gm_vae needs a GMVae")
+    images = _images6(images)
     _check_images(model, images)
     with ops.hold_stream():
         return _train_step_gm_vae(model, images, optimizer, eps, noise, sample_offset)
@@ -233,6 +251,7 @@ def _train_step_gm_vae(model, images, optimizer, eps, noise, sample_offset):
 def test_step_gm_vae(model, images, eps=None, noise=None):
     """test_step_gm_vae (vae/trainer.py:277-294): the same loss terms with training=False (no dropout), no update.  Returns the [4]
     metric tensor; the model's y_logits of this batch stay in `model.encoder(B).buf["logits"]` (cluster accuracy)."""
+    images = _images6(images)
     _check_images(model, images)
     B = images.shape[0]
     with ops.hold_stream():

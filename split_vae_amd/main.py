@@ -3,7 +3,7 @@
     python -m split_vae_amd.main --beta 120 --patch_size 8 --dataset celeba64 -no_label --synthetic
     python -m split_vae_amd.main --model gmvae --beta 40 --patch_size 4       (GMVAE baseline, Table 2)
 
-Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout.
+Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout, --mix_per_image.
 """
 import argparse
 
@@ -38,7 +38,33 @@ def build_parser():
                     help="lggmvae: whether encoder_x's Dropout layers fire in training (tf2.0 = pinned tensorflow 2.0.0: no; "
                          "tf2.1 = call-context propagation of `training`: yes); see split_vae_amd/gm.py")
     ap.add_argument("--data_dir", type=str, default="data", help="holds SVHN/*.mat and celeba/*.tfrec (vae/data.py:24,:103)")
+    ap.add_argument("--mix_per_image", action="store_true",
+                    help="--augmentation mix_scramble: draw a patch size per image (the intent of augmentation.py:60-64) instead of one "
+                         "per pipeline (what the reference runs: np.random.choice when Dataset.map traces mix_scramble)")
     return ap
+
+
+def check_augmentation(augmentation, model_name):
+    """--augmentation (augmentation.py:15-30) against --model, before any data or device work.  high_low_pass makes a 9-channel
+    batch (x | x - low | low): the split models then reconstruct a 6-channel x_hat with a 3-channel decoder mean and the reference
+    fails inside its loss; only the global-only GMVae (channels 0-2, vae/model.py:289) trains with it."""
+    from .augmentation import TYPES
+    if augmentation not in TYPES:
+        raise SystemExit("--augmentation %s: expected one of %s (augmentation.py:15-30)" % (augmentation, ", ".join(TYPES)))
+    if augmentation == 'high_low_pass' and model_name in ('lgvae', 'lggmvae', 'lg_spair'):
+        raise SystemExit("--augmentation high_low_pass gives 9-channel inputs (x | x - low | low); --model %s splits them into x and a "
+                         "6-channel x_hat its 3-channel decoder cannot reconstruct (the reference fails there too). "
+                         "Use --model gmvae, or another augmentation." % model_name)
+
+
+def make_augmentors(config):
+    """(train, test) augmentors (vae/main.py:54-61).  mix_scramble draws its one patch size per mapped pipeline, so the test
+    pipeline gets an Augmentator of its own; every other type shares one, as before."""
+    from .augmentation import ReferenceAugmentator
+    kw = dict(type=config.augmentation, size=config.patch_size, seed=config.seed, per_image=bool(config.get("mix_per_image")))
+    train = ReferenceAugmentator(pipeline=0, **kw)
+    test = ReferenceAugmentator(pipeline=1, **kw) if config.augmentation == 'mix_scramble' else train
+    return train, test
 
 
 def make_model(model_name, config, input_shape):
@@ -74,10 +100,10 @@ def main(argv=None):
     config = dotdict(vars(args))
     config.label = not config.no_label
     print('Config:', config)
+    check_augmentation(config.augmentation, args.model)
     from . import data, trainer
-    from .augmentation import Augmentator
 
-    augmentor = Augmentator(type=config.augmentation, size=config.patch_size, seed=config.seed)
+    augmentor, test_augmentor = make_augmentors(config)
     train_ds, test_ds, input_shape = data.get_dataset(config.dataset, config.batch_size, synthetic=config.synthetic,
                                                       data_dir=config.data_dir, get_label=config.label)
     if config.label and not train_ds.labelled:
@@ -90,10 +116,10 @@ def main(argv=None):
         # (.MISSING_LARGE_BLOBS:1), so the labels ride along unused and the classifier metrics are not reported
         print('Note: classifier-based test metrics are not available (svhn_classifier_weights.h5 is not in the reference repo)')
         train_ds = ((augmentor.augment(x), y) for x, y in train_ds)     # vae/main.py:57-58
-        test_batches = [(augmentor.augment(x), y) for x, y in test_ds]
+        test_batches = [(test_augmentor.augment(x), y) for x, y in test_ds]
     else:
         train_ds = (augmentor.augment(x) for x in train_ds)             # vae/main.py:60-61
-        test_batches = [augmentor.augment(x) for x in test_ds]
+        test_batches = [test_augmentor.augment(x) for x in test_ds]
     model, optimizer = make_model(args.model, config, input_shape)
     model.summary()
     print('Training local-global autoencoder')

@@ -74,6 +74,93 @@ def scramble_gather(x, perm, patch, staged=None):
     return out
 
 
+# ------------------------------------------------------------------ A1b blur / high-low pass / mixed scramble (augmentation.py:33-41,59-101)
+MIX_SIZES = (1, 2, 4, 8)           # augmentation.py:41
+BLUR_MAX_RADIUS = 6                # augmentation.py:87: tf.random.uniform(int32, minval=3, maxval=7)
+
+
+def _staged_args(staged, B, H, W):
+    x8, xh8 = staged
+    assert x8.shape == (B, H, W, 8) and xh8.shape == (B, H, W, 8) and x8.dtype == xh8.dtype
+    return _p(x8), _p(xh8), sv_dtype(x8.dtype)
+
+
+def blur_params(B, seed, step=0, sample_offset=0, device="cuda"):
+    """(radius[B] int32, std[B] fp32) of gaussian_blur (augmentation.py:86-87) from the Philox stream."""
+    radius = torch.empty((B,), dtype=torch.int32, device=device)
+    std = torch.empty((B,), dtype=torch.float32, device=device)
+    check(_lib.load().sv_blur_params(_p(radius), _p(std), B, seed, step, sample_offset, _stream()), "sv_blur_params")
+    return radius, std
+
+
+def gauss_blur(x, radius, std, max_radius=BLUR_MAX_RADIUS, staged=None):
+    """x[B,H,W,3] fp32, radius[B] int32, std[B] fp32 -> [B,H,W,6] = concat([x, blur(x)], axis=-1) (augmentation.py:83-94)."""
+    B, H, W, Cc = x.shape
+    assert Cc == 3 and x.dtype == torch.float32 and radius.dtype == torch.int32 and std.dtype == torch.float32
+    assert radius.shape == (B,) and std.shape == (B,)
+    out = torch.empty((B, H, W, 6), dtype=torch.float32, device=x.device)
+    if staged is not None:
+        x8, xh8, dt = _staged_args(staged, B, H, W)
+        check(_lib.load().sv_gauss_blur_staged(_p(x), _p(radius), _p(std), _p(out), x8, xh8, dt, B, H, W, max_radius, _stream()),
+              "sv_gauss_blur_staged")
+        return out
+    check(_lib.load().sv_gauss_blur(_p(x), _p(radius), _p(std), _p(out), B, H, W, max_radius, _stream()), "sv_gauss_blur")
+    return out
+
+
+def high_low_pass(x, size, mean=0.0, std=1.0, staged=None):
+    """x[B,H,W,3] fp32 -> [B,H,W,9] = concat([x, x - low, low], axis=-1), low the Gaussian of radius `size` (augmentation.py:97-101)."""
+    B, H, W, Cc = x.shape
+    assert Cc == 3 and x.dtype == torch.float32
+    out = torch.empty((B, H, W, 9), dtype=torch.float32, device=x.device)
+    if staged is not None:
+        x8, xh8, dt = _staged_args(staged, B, H, W)
+        check(_lib.load().sv_high_low_pass_staged(_p(x), _p(out), x8, xh8, dt, B, H, W, size, mean, std, _stream()),
+              "sv_high_low_pass_staged")
+        return out
+    check(_lib.load().sv_high_low_pass(_p(x), _p(out), B, H, W, size, mean, std, _stream()), "sv_high_low_pass")
+    return out
+
+
+def mix_sizes(B, seed, step=0, sample_offset=0, device="cuda"):
+    """sizes[B] int32 in {1, 2, 4, 8} (augmentation.py:40-41), one per image, from the Philox stream."""
+    sizes = torch.empty((B,), dtype=torch.int32, device=device)
+    check(_lib.load().sv_mix_sizes(_p(sizes), B, seed, step, sample_offset, _stream()), "sv_mix_sizes")
+    return sizes
+
+
+def mix_size_host(seed, step=0, sample=0):
+    """The same draw on the host (no device): one patch size for a whole pipeline."""
+    return int(_lib.load().sv_mix_size_host(seed, step, sample))
+
+
+def random_perm_mixed(sizes, H, seed, step=0, sample_offset=0, ld=None):
+    """perm[B, ld] int32: row b permutes the (H/sizes[b])^2 patches of image b (the rest of the row is -1); ld defaults to
+    (H / min size)^2."""
+    B = sizes.shape[0]
+    if ld is None:
+        ld = (H // min(MIX_SIZES)) ** 2
+    perm = torch.full((B, ld), -1, dtype=torch.int32, device=sizes.device)
+    check(_lib.load().sv_random_perm_mixed(_p(perm), _p(sizes), B, H, ld, seed, step, sample_offset, _stream()), "sv_random_perm_mixed")
+    return perm
+
+
+def scramble_gather_mixed(x, perm, sizes, staged=None):
+    """x[B,H,W,3] fp32, perm[B,ld] int32 (row b: a permutation of (H/sizes[b])^2 patches), sizes[B] int32 -> [B,H,W,6]."""
+    B, H, W, Cc = x.shape
+    assert Cc == 3 and x.dtype == torch.float32 and perm.dtype == torch.int32 and sizes.dtype == torch.int32
+    assert perm.dim() == 2 and perm.shape[0] == B and sizes.shape == (B,)
+    ld = perm.shape[1]
+    out = torch.empty((B, H, W, 6), dtype=torch.float32, device=x.device)
+    if staged is not None:
+        x8, xh8, dt = _staged_args(staged, B, H, W)
+        check(_lib.load().sv_scramble_gather_mixed_staged(_p(x), _p(perm), _p(sizes), ld, _p(out), x8, xh8, dt, B, H, W, _stream()),
+              "sv_scramble_gather_mixed_staged")
+        return out
+    check(_lib.load().sv_scramble_gather_mixed(_p(x), _p(perm), _p(sizes), ld, _p(out), B, H, W, _stream()), "sv_scramble_gather_mixed")
+    return out
+
+
 # ------------------------------------------------------------------ A6 discretised logistic (vae/trainer.py:21-38)
 def dlogistic_nll(images6, ch_off, out6, grad_dtype=None, grad_scale=1.0):
     B, H, W, _ = images6.shape

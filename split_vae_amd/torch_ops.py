@@ -20,6 +20,9 @@ _lib_def = torch.library.Library("split_vae", "DEF")
 _lib_impl = torch.library.Library("split_vae", "IMPL", "CUDA")        # HIP devices dispatch under the CUDA key on ROCm
 
 _lib_def.define("scramble_gather(Tensor x, Tensor perm, int patch) -> Tensor")
+_lib_def.define("gauss_blur(Tensor x, Tensor radius, Tensor std) -> Tensor")
+_lib_def.define("high_low_pass(Tensor x, int size, float mean, float std) -> Tensor")
+_lib_def.define("scramble_gather_mixed(Tensor x, Tensor perm, Tensor sizes) -> Tensor")
 _lib_def.define("conv2d_nhwc_fwd(Tensor x, Tensor w_hwio, Tensor? bias, int stride, int act, bool ups_in, bool y_f32) -> Tensor")
 _lib_def.define("conv2d_nhwc_dgrad(Tensor dy, Tensor w_hwio, Tensor? relu_mask, int H, int W, int ldx, int stride, bool ups_in) -> Tensor")
 _lib_def.define("conv2d_nhwc_wgrad(Tensor x, Tensor dy, int KH, int KW, int Cin, int Cout, int stride, bool ups_in) -> (Tensor, Tensor)")
@@ -58,6 +61,24 @@ def _impl(name):
 @_impl("scramble_gather")
 def _scramble_gather(x, perm, patch):
     return ops.scramble_gather(x.contiguous(), perm.to(torch.int32).contiguous(), patch)
+
+
+@_impl("gauss_blur")
+def _gauss_blur(x, radius, std):
+    """x[B,H,W,3] fp32, radius[B], std[B] -> [B,H,W,6] = x | blur(x) (augmentation.py:83-94)."""
+    return ops.gauss_blur(x.contiguous(), radius.to(torch.int32).contiguous(), std.to(torch.float32).contiguous())
+
+
+@_impl("high_low_pass")
+def _high_low_pass(x, size, mean, std):
+    """x[B,H,W,3] fp32 -> [B,H,W,9] = x | x - low | low (augmentation.py:97-101)."""
+    return ops.high_low_pass(x.contiguous(), size, mean, std)
+
+
+@_impl("scramble_gather_mixed")
+def _scramble_gather_mixed(x, perm, sizes):
+    """x[B,H,W,3] fp32, perm[B,ld], sizes[B] -> [B,H,W,6] = x | x scrambled in sizes[b]-square patches (augmentation.py:59-81)."""
+    return ops.scramble_gather_mixed(x.contiguous(), perm.to(torch.int32).contiguous(), sizes.to(torch.int32).contiguous())
 
 
 @_impl("conv2d_nhwc_fwd")
