@@ -220,6 +220,33 @@ int sv_spair_loss(int32_t mode, const float* a, const float* b, float* sums, flo
 int sv_spair_loss_dyn(int32_t mode, const float* a, const float* b, float* sums, float* ga, float* gb, int32_t B, int32_t n,
                       float prior_mean, const float* prior_mean_dev, float prior_sig, void* stream);
 
+/* SPLIT-SPAIR evaluation (spair_eval.hip), fp32, plain loads and stores, no atomics (same inputs -> same bits).  Every argument is
+ * checked before anything is enqueued: SV_E_BADARG leaves all outputs untouched.
+ *
+ * tf.image.draw_bounding_boxes as spair/visualizer.py:107-111 calls it (boxes = obj_bbox_mask * z_pres, one white colour).
+ * images / out [B,H,W,C], C in {1,3,4}; out may alias images.  boxes [B,NB,4] = (ymin, xmin, ymax, xmax) in [0,1] coordinates
+ * (obj_bbox_mask's layout); gate [B,NB] (may be NULL) multiplies each box first.  colors [NC,ldc], ldc >= C: box bb takes row
+ * bb % NC and its first C components are written as they are (no blending).  TF's rules: in fp32, r0 = (int64)(ymin * (H-1)),
+ * r1 = (int64)(ymax * (H-1)), c0 / c1 the same with xmin / xmax and W (truncation toward zero; NaN or beyond the int64 range ->
+ * INT64_MIN, as on x86); a box with r0 > r1 or c0 > c1 (inverted) or r0 >= H, r1 < 0, c0 >= W or c1 < 0 (outside) is skipped;
+ * the top edge (row r0) is drawn if r0 >= 0, the bottom (row r1) if r1 < H, both over the columns [c0, c1] clamped to the image;
+ * the left (column c0) if c0 >= 0, the right (column c1) if c1 < W, both over the clamped rows.  Boxes are drawn in index order:
+ * where outlines overlap, the highest-index box wins.  As in TF, a gated-off box becomes (0,0,0,0) and colours pixel (0,0).
+ * Every other pixel of out is a copy of images.  SV_E_BADARG: a null images / boxes / colors / out, B, H, W, NB or NC <= 0, C not in
+ * {1,3,4}, ldc < C; SV_E_UNSUPPORTED: H * W >= 2^31 - 256 or B > 65535. */
+int sv_draw_bounding_boxes(const float* images, const float* boxes, const float* gate, const float* colors, float* out, int32_t B,
+                           int32_t H, int32_t W, int32_t C, int32_t NB, int32_t NC, int32_t ldc, void* stream);
+
+/* The object-count metrics of test_step (spair/trainer.py:292-301), one launch, no host synchronisation.  z_pres_logits [B,ncell]
+ * with row pitch ld >= ncell, labels [B] -> pred[b] = sum over the cells, in cell order, of rint(sigmoid(logit)) (fp32 sigmoid, round
+ * half to even as tf.round: a logit of exactly 0 is not counted), written when pred != NULL; metrics[2] = (MAE, MAPE) of the batch:
+ * mean |label - pred| (tf.metrics.mean_absolute_error) and 100 * mean(|label - pred| / max(|label|, 1e-7))
+ * (mean_absolute_percentage_error, Keras epsilon); acc (may be NULL) int32[2] += (number of images with pred == label, B): the
+ * state of tf.keras.metrics.Accuracy (count_acc_test, :132, :301), result = acc[0] / acc[1] (0 when acc[1] == 0).  Zero acc once per
+ * test set.  SV_E_BADARG: a null z_pres_logits / labels / metrics, B or ncell <= 0, ld < ncell. */
+int sv_spair_count_metrics(const float* z_pres_logits, int32_t ld, const float* labels, float* pred, float* metrics, int32_t* acc,
+                           int32_t B, int32_t ncell, void* stream);
+
 /* ---------------------------------------------------------------- K3-K10: NHWC conv (implicit GEMM on MFMA)
  * Replaces tf.keras.layers.Conv2D(padding='same') forward (vae/model.py:36-38,:153-156) and the
  * Conv2DBackpropInput / Conv2DBackpropFilter / BiasAddGrad / ReluGrad nodes of tape.gradient

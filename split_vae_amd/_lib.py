@@ -123,6 +123,8 @@ SYMBOLS = {
     "sv_upsample2x_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "sv_stn_sample_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "sv_spair_loss_dyn": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp, C.c_float, _vp]),
+    "sv_draw_bounding_boxes": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "sv_spair_count_metrics": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "sv_spair_zpres_kl_dyn": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp, C.c_float, C.c_float, _vp]),
     "sv_adam_step_clipnorm_dyn": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                             _i64, _vp, C.c_float, _vp]),

@@ -335,6 +335,40 @@ def spair_loss(mode, a, b, prior_mean=0.0, prior_sig=1.0, grads=True):
     return sums, (None if ga is None else ga.reshape(a.shape)), (None if gb is None else gb.reshape(b.shape))
 
 
+# ------------------------------------------------------------------ SPAIR evaluation (spair/trainer.py:294-301, spair/visualizer.py:107-111)
+def draw_bounding_boxes(images, boxes, colors, gate=None, out=None):
+    """tf.image.draw_bounding_boxes: images [B,H,W,C] fp32 (C in 1, 3, 4), boxes [B,NB,4] = (ymin, xmin, ymax, xmax) in [0,1],
+    colors [NC,ldc] fp32 with ldc >= C, gate [B,NB] (optional: the boxes are multiplied by it) -> out [B,H,W,C]: a new tensor, or
+    `out` (which may be `images` itself)."""
+    B, H, W, Cc = images.shape
+    NB = boxes.shape[1]
+    assert images.dtype == boxes.dtype == colors.dtype == torch.float32 and colors.dim() == 2
+    assert tuple(boxes.shape) == (B, NB, 4) and (gate is None or (gate.dtype == torch.float32 and gate.numel() == B * NB))
+    if out is None:
+        out = torch.empty_like(images)
+    assert out.shape == images.shape and out.dtype == torch.float32
+    check(_lib.load().sv_draw_bounding_boxes(_p(images), _p(boxes), _p(gate), _p(colors), _p(out), B, H, W, Cc, NB, colors.shape[0],
+                                             colors.shape[1], _stream()), "sv_draw_bounding_boxes")
+    return out
+
+
+def spair_count_metrics(z_pres_logits, labels, acc=None, want_pred=False):
+    """The count metrics of test_step: z_pres_logits [B, ...] (an image's cells contiguous, images at any row pitch), labels [B] ->
+    (metrics [2] = (MAE, MAPE) of the batch, pred [B] | None).  acc: int32 [2] device counters (matches, images seen) to add to."""
+    B = z_pres_logits.shape[0]
+    lg = z_pres_logits.reshape(B, -1)
+    if lg.stride(1) != 1 or lg.data_ptr() % 4:
+        lg = lg.contiguous()
+    assert lg.dtype == torch.float32 and lg.is_cuda
+    lab = labels.reshape(-1).to(device=lg.device, dtype=torch.float32).contiguous()
+    assert lab.numel() == B and (acc is None or (acc.dtype == torch.int32 and acc.numel() == 2))
+    metrics = torch.empty((2,), dtype=torch.float32, device=lg.device)
+    pred = torch.empty((B,), dtype=torch.float32, device=lg.device) if want_pred else None
+    check(_lib.load().sv_spair_count_metrics(C.c_void_p(lg.data_ptr()), lg.stride(0), _p(lab), _p(pred), _p(metrics), _p(acc), B,
+                                             lg.shape[1], _stream()), "sv_spair_count_metrics")
+    return metrics, pred
+
+
 def adam_alpha(lr, beta1, beta2, t):
     """Keras Adam's bias-corrected step size of iteration t (what sv_adam_step* computes from lr and t)."""
     return float(_lib.load().sv_adam_alpha(float(lr), float(beta1), float(beta2), int(t)))

@@ -6,7 +6,7 @@
 The Multi-Bird canvases are synthesised by the reference from CUB mask blobs that are not in its repository (spair/data.py:14-15),
 so the only data source here is --synthetic: 48x48x3 canvases in [0,1] (the shape get_cub_dataset reports, spair/data.py:258-278)
 with 0-5 soft-edged blobs on a solid background and the blob count as the label.
-Extra flags (not in the reference): --synthetic, --seed, --log_every, --graph, --dtype.
+Extra flags (not in the reference): --synthetic, --seed, --log_every, --graph, --dtype, -viz.
 """
 import argparse
 
@@ -44,6 +44,9 @@ def build_parser():
     ap.add_argument("--graph", action="store_true", help="capture the train step into a hipGraph and replay it (spair_trainer.GraphedTrainStep)")
     ap.add_argument("--mix_per_image", action="store_true",
                     help="--augmentation mix_scramble: a patch size per image instead of one per pipeline (see split_vae_amd/main.py)")
+    ap.add_argument("-viz", action="store_true",
+                    help="write the reference's figures (train_recon_it_<step>.png, spair/visualizer.py's test figures) under "
+                         "output/<RUN_NAME>/ at every log step (spair_visualizer.py)")
     return ap
 
 

@@ -283,10 +283,32 @@ class GraphedTrainStep:
         return self.outputs, self.losses
 
 
+class CountAccuracy:
+    """tf.keras.metrics.Accuracy over the predicted object counts (count_acc_test, spair/trainer.py:132, :301): int32 device counters
+    (matches, images seen) that sv_spair_count_metrics adds to on the caller's stream; result() reads them once on the host."""
+
+    def __init__(self, device="cuda"):
+        self.acc = torch.zeros((2,), dtype=torch.int32, device=device)
+
+    def update(self, labels, z_pres_logits):
+        """update_state(labels, pred_count) with pred_count = sum(round(sigmoid(z_pres_logits))) per image."""
+        ops.spair_count_metrics(z_pres_logits, labels, acc=self.acc)
+
+    def result(self):
+        """matches / images in fp32 as Keras divides (0.0 when nothing was counted: div_no_nan)."""
+        import numpy as np
+        m, n = self.acc.tolist()
+        return np.float32(m) / np.float32(n) if n else np.float32(0.0)
+
+    def reset_states(self):
+        self.acc.zero_()
+
+
 @torch.no_grad()
-def test_step(model, images, config, labels=None, noise=None):
-    """spair/trainer.py:236-308 (the reference evaluates with model(images, training=True) too)."""
-    if _native_ok(model) and labels is None:
+def test_step(model, images, config, labels=None, noise=None, count_acc=None):
+    """spair/trainer.py:236-308 (the reference evaluates with model(images, training=True) too).  labels [B]: the MAE / MAPE of the
+    predicted object counts are appended (:294-300) and `count_acc` (CountAccuracy) counts the exact matches (:301)."""
+    if _native_ok(model):
         ns = model.native(images.shape[0], config, training=True)
         lo = ns.run(images, step_scalars(config, 0.0, False), noise=noise, backward=False)
         names = _return_names(config)
@@ -298,6 +320,10 @@ def test_step(model, images, config, labels=None, noise=None):
         elif config.model == "bg_spair":
             z = torch.zeros((), device=images.device)
             losses = losses + [means[6], z, z]
+        if labels is not None:                                          # :294-301 as one launch on the tape's z_pres_logits
+            metrics, _ = ops.spair_count_metrics(ns.output("z_pres_logits"), labels,
+                                                 acc=None if count_acc is None else count_acc.acc)
+            losses = losses + [metrics[0], metrics[1]]
         return ns.outputs(names), losses
     out = model(images, training=True, noise=noise)
     _, losses = compute_losses(config, images, out, 0.0, training=False)
@@ -306,23 +332,35 @@ def test_step(model, images, config, labels=None, noise=None):
         lab = labels.to(pred_count)
         losses.append((lab - pred_count).abs().mean())
         losses.append(100.0 * ((lab - pred_count).abs() / lab.abs().clamp_min(1e-7)).mean())
+        if count_acc is not None:
+            count_acc.update(labels, out[11])
     return out[:17] + out[18:], losses
 
 
 def train_spair(model, optimizer, dataset, train_dataset, test_dataset, config, log=print):
-    """spair/trainer.py:112-424 without the matplotlib grids: the step loop, the 1000-step metric logs, save_weights at the end."""
+    """spair/trainer.py:112-424: the step loop, the metric logs and the count accuracy of every test set at each log step, save_weights
+    at the end.  config.viz: the reference's figures (train_recon_it_<step>.png, :331-378, and spair_visualizer's four test figures,
+    :403-414) under output/<RUN_NAME>/."""
     sums, n = None, 0
     start = time.time()
     history = []
     every = int(config.log_every or 1000)
     graphed = None
+    viz = bool(getattr(config, "viz", False))
+    run_dir = None
+    if viz:
+        import os
+        from datetime import datetime
+        run_dir = os.path.join("output", datetime.now().strftime("%Y%m%d-%H%M%S")) + "/"
+        os.makedirs(run_dir, exist_ok=True)
+    count_acc = None
     for step, images in enumerate(train_dataset):
         if config.graph:                                                  # one hipGraph replay per step (GraphedTrainStep)
             if graphed is None:
                 graphed = GraphedTrainStep(model, optimizer, config, images)
-            _, losses = graphed(images, step)
+            step_out, losses = graphed(images, step)
         else:
-            _, losses = train_step(model, images, optimizer, step, config)
+            step_out, losses = train_step(model, images, optimizer, step, config)
         vals = torch.stack([l.float() for l in losses])
         sums = vals if sums is None else sums + vals
         n += 1
@@ -334,18 +372,29 @@ def train_spair(model, optimizer, dataset, train_dataset, test_dataset, config, 
             log(tr)
             sums, n = None, 0
             rec = {"step": step, "train": tr}
+            if viz:
+                from . import spair_visualizer
+                spair_visualizer.train_reconstruction(images, step_out, step=step, filepath=run_dir)
             for test_num, test_ds in enumerate(test_dataset or []):
+                if count_acc is None:
+                    count_acc = CountAccuracy(model.device)
                 ts, tn = None, 0
                 for batch in test_ds:
                     imgs, labels = batch if isinstance(batch, (tuple, list)) else (batch, None)
-                    _, tl = test_step(model, imgs, config, labels)
+                    _, tl = test_step(model, imgs, config, labels, count_acc=count_acc)
                     tv = torch.stack([l.float() for l in tl])
                     ts = tv if ts is None else ts + tv
                     tn += 1
+                acc = count_acc.result()                                  # an unlabelled set leaves the counters at 0: 0.0 (:394)
+                log('Count accuracy' + str(test_num) + ': ' + str(acc))
+                rec["count_acc" + str(test_num)] = float(acc)
+                count_acc.reset_states()
                 if tn:
                     te = dict(zip([nm + str(test_num) for nm in TEST_METRIC_NAMES], (ts / tn).tolist()))
                     log(te)
                     rec["test" + str(test_num)] = te
+                if viz:
+                    spair_visualizer.write_test_figures(model, test_ds, config, step, test_num, run_dir)
             history.append(rec)
             start = time.time()
         if step >= config.training_steps:

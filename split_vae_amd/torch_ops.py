@@ -40,6 +40,9 @@ _lib_def.define("spair_render_bwd(Tensor obj, Tensor bg, Tensor z_depth, Tensor 
 _lib_def.define("spair_zpres_kl(Tensor z_pres, Tensor z_pres_logits, Tensor z_pres_pre_sigmoid, float prior_prob, float temperature, Tensor? prior_prob_dev=None) -> (Tensor, Tensor, Tensor)")
 
 _lib_def.define("spair_loss(str mode, Tensor a, Tensor b, float prior_mean, float prior_sig, Tensor? prior_mean_dev=None) -> (Tensor, Tensor, Tensor)")
+# SPAIR evaluation (spair/visualizer.py:107-111, spair/trainer.py:294-301): not differentiable
+_lib_def.define("draw_bounding_boxes(Tensor images, Tensor boxes, Tensor colors, Tensor? gate=None) -> Tensor")
+_lib_def.define("spair_count_metrics(Tensor z_pres_logits, Tensor labels, Tensor(a!)? acc=None) -> (Tensor, Tensor)")
 
 ACT = {None: 0, "none": 0, "relu": 1}
 
@@ -284,6 +287,19 @@ def _render_bwd(obj, bg, z_depth, z_pres, noise, g_out):
 def _zpres_kl(z_pres, z_pres_logits, z_pres_pre_sigmoid, prior_prob, temperature, prior_prob_dev=None):
     return ops.spair_zpres_kl(z_pres, z_pres_logits, z_pres_pre_sigmoid, prior_prob if prior_prob_dev is None else prior_prob_dev,
                               temperature, grad_scale=1.0)
+
+
+@_impl("draw_bounding_boxes")
+def _draw_bounding_boxes(images, boxes, colors, gate=None):
+    """tf.image.draw_bounding_boxes(images, boxes * gate, colors) -> a new [B,H,W,C] tensor."""
+    return ops.draw_bounding_boxes(images.contiguous(), boxes.contiguous(), colors.contiguous(),
+                                   gate=None if gate is None else gate.contiguous())
+
+
+@_impl("spair_count_metrics")
+def _spair_count_metrics(z_pres_logits, labels, acc=None):
+    """-> (metrics [2] = (MAE, MAPE), pred_count [B]); acc: int32 [2] counters (matches, images seen), added to in place."""
+    return ops.spair_count_metrics(z_pres_logits, labels, acc=acc, want_pred=True)
 
 
 class _StnFn(torch.autograd.Function):
