@@ -95,6 +95,41 @@ int sv_scramble_gather_mixed(const float* x, const int32_t* perm, const int32_t*
 int sv_scramble_gather_mixed_staged(const float* x, const int32_t* perm, const int32_t* sizes, int32_t ld, float* images6, void* x8,
                                     void* xh8, int32_t dtype, int32_t B, int32_t H, int32_t W, void* stream);
 
+/* ---------------------------------------------------------------- A1c: Multi-Bird canvas synthesis
+ * Replaces MultiCUB.create_dataset / create_sample (spair/data.py:39-174) for the two datasets create_cub_tfrec builds
+ * (:229-255): 48 x 48 x 3 canvases in [0,1] with 0..5 hard-masked 14 x 14 sprites on a solid colour or on a rotated
+ * 6-pixel checkerboard.  Canvas `sample` of `split` is a pure function of (seed, split, sample): every draw is one
+ * Philox4x32-10 block with counter (sample, split, kind | object | try), so nothing is stored and shards agree.
+ * `bg` names the background AND its colour table (spair/data.py:52-57). */
+typedef enum { SV_MB_SOLID_FIXED = 0, SV_MB_UNSEEN_SOLID_FIXED = 1, SV_MB_CKB_ROT_6 = 2, SV_MB_UNSEEN_CKB_ROT_6 = 3 } sv_multibird_bg;
+/* Everything random about one canvas.  count: objects placed, 0..5 (uniform; :166).  row[k], col[k] in 0..33 (np.random.randint(0, 34),
+ * :127-131; rand_x indexes axis 0 = rows), redrawn until no earlier box is overlapped by more than 15 % -- for 14-wide boxes:
+ * ix = max(0, 14 - |row_a - row_b|), iy likewise, reject iff ix * iy >= 30.  sprite[k] in 0..n_sprites-1.  colour[0..1]: indices
+ * into the table of `bg` (solid: colour[1] == colour[0]; checkerboard: an ordered pair of distinct colours).  angle: fp32 in
+ * [-pi/2, pi/2), 0 on the solid backgrounds.  Entries k >= count are -1.
+ * The rejection loop is capped at 4096 tries per object: on reaching the cap that object and all later ones are dropped, count
+ * is the number actually placed and max_tries is 4096; otherwise max_tries is the largest (0-based) try number accepted. */
+typedef struct { int32_t count, row[5], col[5], sprite[5], colour[2], max_tries; float angle; } sv_multibird_layout;
+/* The plain sequential loop on the host; needs no device.  SV_E_BADARG: out NULL or n_sprites <= 0; SV_E_UNSUPPORTED: a bg
+ * outside sv_multibird_bg or n_sprites > 2^20.  (The same two rules hold for the device entries below.) */
+int sv_multibird_layout_host(sv_multibird_layout* out, int32_t bg, int32_t n_sprites, uint64_t seed, int32_t split, int64_t sample);
+/* out[B] on the device, one wave per canvas: lane l tests try 64 r + l and the ballot's lowest bit picks the first accepted try,
+ * the one the host loop accepts -- bit for bit the host's layouts.  index[B] int64 device sample numbers, or NULL: sample_offset + b.
+ * SV_E_BADARG: out NULL or B <= 0. */
+int sv_multibird_layouts(sv_multibird_layout* out, const int64_t* index, int32_t bg, int32_t n_sprites, int32_t B, uint64_t seed,
+                         int32_t split, int64_t sample_offset, void* stream);
+/* x[B,48,48,3] fp32 canvases (16-byte aligned) and, unless NULL, count[B] fp32 = the layouts' counts (the label test_step takes).
+ * sprites[n_sprites,14,14,3] uint8 on the device (4-byte aligned), zero outside the object.  layouts NULL: drawn in the same
+ * launch as sv_multibird_layouts draws them; a pointer pins them (counts are clamped to 0..5, a sprite id outside the bank pastes
+ * nothing).  Background: colour / 255, or the 192 x 192 board of 6-pixel cells rotated by `angle` about its centre with bilinear
+ * interpolation (tfa.image.rotate's transform) and cropped to its central quarter (:89-105), sampled analytically.  Sprites in
+ * object order, later ones on top; a sprite pixel replaces the canvas iff max(r,g,b) > 0, value v / 255 in correctly rounded
+ * fp32 (= np.float32(v / 255.0)).  Every output element is written exactly once; no workspace.
+ * SV_E_BADARG: x or sprites NULL or misaligned, B <= 0. */
+int sv_multibird_canvases(float* x, float* count, const uint8_t* sprites, int32_t n_sprites, const int64_t* index,
+                          const sv_multibird_layout* layouts, int32_t bg, int32_t B, uint64_t seed, int32_t split,
+                          int64_t sample_offset, void* stream);
+
 /* ---------------------------------------------------------------- A6: discretised logistic NLL
  * Replaces discretised_logistic_loss (vae/trainer.py:21-38) + reduce_sum[1,2,3] (:127-128) and,
  * when grad != NULL, its adjoint under tape.gradient (:137).

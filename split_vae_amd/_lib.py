@@ -70,6 +70,15 @@ TAPE_PHASE_FORWARD, TAPE_PHASE_BACKWARD, TAPE_PHASE_ADAM = 1, 2, 4
 TAPE_MAX_LOSS = 16
 
 
+SV_MB_SOLID_FIXED, SV_MB_UNSEEN_SOLID_FIXED, SV_MB_CKB_ROT_6, SV_MB_UNSEEN_CKB_ROT_6 = range(4)
+
+
+class MultibirdLayout(C.Structure):
+    """sv_multibird_layout (include/splitvae.h): 20 32-bit words."""
+    _fields_ = [("count", C.c_int32), ("row", C.c_int32 * 5), ("col", C.c_int32 * 5), ("sprite", C.c_int32 * 5),
+                ("colour", C.c_int32 * 2), ("max_tries", C.c_int32), ("angle", C.c_float)]
+
+
 class GmDesc(C.Structure):
     _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("latent", C.c_int32), ("y_size", C.c_int32),
                 ("tau", C.c_float), ("dtype", C.c_int32)]
@@ -101,6 +110,9 @@ SYMBOLS = {
     "sv_random_perm_mixed": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _u64, _u64, _i64, _vp]),
     "sv_scramble_gather_mixed": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "sv_scramble_gather_mixed_staged": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "sv_multibird_layout_host": (C.c_int, [_vp, _i32, _i32, _u64, _i32, _i64]),
+    "sv_multibird_layouts": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _u64, _i32, _i64, _vp]),
+    "sv_multibird_canvases": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _u64, _i32, _i64, _vp]),
     "sv_dlogistic_nll": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _f, _i32, _i32, _i32, _vp, _vp]),
     "sv_dlogistic_nll_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "sv_reparam_kl_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32,

@@ -161,6 +161,46 @@ def scramble_gather_mixed(x, perm, sizes, staged=None):
     return out
 
 
+# ------------------------------------------------------------------ A1c Multi-Bird canvases (spair/data.py:39-174)
+MULTIBIRD_LAYOUT_WORDS = C.sizeof(_lib.MultibirdLayout) // 4
+
+
+def multibird_layout_host(bg, n_sprites, seed, split, sample, out=None):
+    """The layout of canvas `sample` of `split` by the sequential host loop (no device) -> _lib.MultibirdLayout."""
+    L = _lib.MultibirdLayout() if out is None else out
+    check(_lib.load().sv_multibird_layout_host(C.addressof(L), bg, n_sprites, seed, split, sample), "sv_multibird_layout_host")
+    return L
+
+
+def _mb_index(index, B):
+    if index is not None:
+        assert index.dtype == torch.int64 and index.shape == (B,)
+    return _p(index)
+
+
+def multibird_layouts(B, bg, n_sprites, seed, split, sample_offset=0, index=None, device="cuda"):
+    """int32 [B, 20]: sv_multibird_layout records (word 19 is the fp32 angle) of samples index[b] or sample_offset + b."""
+    out = torch.empty((B, MULTIBIRD_LAYOUT_WORDS), dtype=torch.int32, device=device)
+    check(_lib.load().sv_multibird_layouts(_p(out), _mb_index(index, B), bg, n_sprites, B, seed, split, sample_offset, _stream()),
+          "sv_multibird_layouts")
+    return out
+
+
+def multibird_canvases(sprites, bg, B, seed, split, sample_offset=0, index=None, layouts=None, x=None, count=None):
+    """sprites uint8 [n,14,14,3] on the device -> (x [B,48,48,3] fp32, count [B] fp32).  layouts (int32 [B,20]) pins the draws."""
+    assert sprites.dtype == torch.uint8 and sprites.shape[1:] == (14, 14, 3)
+    if x is None:
+        x = torch.empty((B, 48, 48, 3), dtype=torch.float32, device=sprites.device)
+    if count is None:
+        count = torch.empty((B,), dtype=torch.float32, device=sprites.device)
+    assert x.shape == (B, 48, 48, 3) and x.dtype == torch.float32 and count.shape == (B,) and count.dtype == torch.float32
+    if layouts is not None:
+        assert layouts.dtype == torch.int32 and layouts.shape == (B, MULTIBIRD_LAYOUT_WORDS)
+    check(_lib.load().sv_multibird_canvases(_p(x), _p(count), _p(sprites), sprites.shape[0], _mb_index(index, B), _p(layouts), bg, B,
+                                            seed, split, sample_offset, _stream()), "sv_multibird_canvases")
+    return x, count
+
+
 # ------------------------------------------------------------------ A6 discretised logistic (vae/trainer.py:21-38)
 def dlogistic_nll(images6, ch_off, out6, grad_dtype=None, grad_scale=1.0):
     B, H, W, _ = images6.shape

@@ -3,10 +3,11 @@
     python -m split_vae_amd.spair_main --dataset cub_solid_fixed --z_bg_beta 10 --patch_size 8 --latent_size 64 --bg_latent_size 4 \\
         --local_latent_size 4 --model lg_spair -split_z_l -concat_z_what -dense_local -dense_bg --training_steps 200 --synthetic
 
-The Multi-Bird canvases are synthesised by the reference from CUB mask blobs that are not in its repository (spair/data.py:14-15),
-so the only data source here is --synthetic: 48x48x3 canvases in [0,1] (the shape get_cub_dataset reports, spair/data.py:258-278)
-with 0-5 soft-edged blobs on a solid background and the blob count as the label.
-Extra flags (not in the reference): --synthetic, --seed, --log_every, --graph, --dtype, -viz.
+--dataset cub_solid_fixed | cub_ckb_rot_6: the Multi-Bird canvases of spair/data.py, synthesised on the device (multibird.py,
+csrc/multibird.hip) with the reference's two test sets (seen / unseen colours).  The CUB sprite blobs are not in the reference's
+repository (spair/data.py:14-15): they are read from --data_dir when present, a procedural stand-in bank is used otherwise.
+--synthetic: 48x48x3 canvases in [0,1] with 0-5 soft-edged blobs on a solid background and the blob count as the label.
+Extra flags (not in the reference): --synthetic, --data_dir, --seed, --log_every, --graph, --dtype, -viz.
 """
 import argparse
 
@@ -33,6 +34,9 @@ def build_parser():
     for flag, ty, default in REFERENCE_OPTIONS:
         ap.add_argument(flag, type=ty, nargs="?", default=default)
     ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--data_dir", type=str, default="data",
+                    help="where the Multi-Bird sprite banks (cub_{train,test}_seg_14x14_pad_20_masked.npy) or multi_cub/*.tfrec are looked for; "
+                         "without them the canvases use a procedural stand-in bank (split_vae_amd/multibird.py)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log_every", type=int, default=1000)
     ap.add_argument("--dtype", type=str, default="f32", choices=["f32", "bf16"],
@@ -83,8 +87,6 @@ def main(argv=None):
     config = dotdict(vars(args))
     config.label = not config.no_label
     print('Config:', config)
-    if not config.synthetic:
-        raise SystemExit("the Multi-Bird source blobs are not in the reference repository (spair/data.py:14-15): pass --synthetic")
     from .main import check_augmentation, make_augmentors
     check_augmentation(config.augmentation, config.model)
     from . import spair, spair_trainer
@@ -92,15 +94,27 @@ def main(argv=None):
     augmentor, test_augmentor = make_augmentors(config)
     lg = config.model == 'lg_spair'
 
-    def batches():
-        i = 0
-        while True:
-            x, _ = synthetic_canvases(config.batch_size, seed=config.seed + 1 + i)
-            yield augmentor.augment(x) if lg else x                     # spair/main.py:71-72
-            i += 1
+    if config.synthetic:
+        def batches():
+            i = 0
+            while True:
+                x, _ = synthetic_canvases(config.batch_size, seed=config.seed + 1 + i)
+                yield augmentor.augment(x) if lg else x                     # spair/main.py:71-72
+                i += 1
 
-    tx, ty = synthetic_canvases(config.batch_size, seed=config.seed + 10 ** 6)
-    test_batches = [[(test_augmentor.augment(tx) if lg else tx, ty) if config.label else (test_augmentor.augment(tx) if lg else tx)]]
+        tx, ty = synthetic_canvases(config.batch_size, seed=config.seed + 10 ** 6)
+        test_batches = [[(test_augmentor.augment(tx) if lg else tx, ty) if config.label else (test_augmentor.augment(tx) if lg else tx)]]
+    else:                                                                   # spair/main.py:71-93 on the device generator
+        from . import multibird
+        train_ds, test_batches, _, _ = multibird.get_cub_dataset(config.dataset, channel=config.channel, batch_size=config.batch_size,
+                                                                  data_dir=config.data_dir, seed=config.seed)
+
+        def batches():
+            for x in train_ds:
+                yield augmentor.augment(x) if lg else x
+
+        for t in test_batches:
+            t.augment, t.label = (test_augmentor.augment if lg else None), bool(config.label)
     history = None
     for _ in range(args.runs):
         print('Creating model...')

@@ -183,6 +183,61 @@ def serialize_tensor(a):
     return b"\x08" + _enc_varint(DT_FLOAT) + b"\x12" + _enc_varint(len(shape)) + shape + b"\x22" + _enc_varint(len(content)) + content
 
 
+def _ld(num, payload):
+    """One length-delimited field."""
+    return _enc_varint((num << 3) | 2) + _enc_varint(len(payload)) + payload
+
+
+def encode_example(features):
+    """tf.train.Example(features=Features(feature={...})).SerializeToString() (tensorflow/core/example/{example,feature}.proto) for
+    one value per feature: bytes -> bytes_list (Feature field 1), float -> float_list (2, packed), int -> int64_list (3, packed).
+    Example.features = 1, Features.feature = 1 (a map: entries of key = 1, value = 2).  Keys in sorted order."""
+    entries = b""
+    for key in sorted(features):
+        v = features[key]
+        if isinstance(v, (bytes, bytearray, memoryview)):
+            feat = _ld(1, _ld(1, bytes(v)))
+        elif isinstance(v, (int, np.integer)):
+            feat = _ld(3, _ld(1, _enc_varint(int(v) & 0xFFFFFFFFFFFFFFFF)))
+        else:
+            feat = _ld(2, _ld(1, struct.pack("<f", float(v))))
+        entries += _ld(1, _ld(1, key.encode()) + _ld(2, feat))
+    return _ld(1, entries)
+
+
+def parse_example(payload):
+    """A serialized tf.train.Example -> {name: [values]} (bytes, floats or ints; packed and unpacked lists)."""
+    out = {}
+    for n1, w1, features in _fields(memoryview(payload)):
+        if n1 != 1 or w1 != 2:
+            continue
+        for n2, w2, entry in _fields(features):
+            if n2 != 1 or w2 != 2:
+                continue
+            key, vals = None, []
+            for n3, w3, v3 in _fields(entry):
+                if n3 == 1 and w3 == 2:
+                    key = bytes(v3).decode()
+                elif n3 == 2 and w3 == 2:
+                    for kind, wk, lst in _fields(v3):
+                        for n5, w5, v5 in _fields(lst):
+                            if n5 != 1:
+                                continue
+                            if kind == 1:
+                                vals.append(bytes(v5))
+                            elif kind == 2:
+                                vals.extend(np.frombuffer(bytes(v5), "<f4").tolist())
+                            elif kind == 3:
+                                ints, i = ([v5], 0) if w5 == 0 else ([], 0)
+                                while w5 == 2 and i < len(v5):
+                                    x, i = _varint(v5, i)
+                                    ints.append(x)
+                                vals.extend(x - (1 << 64) if x >> 63 else x for x in ints)
+            if key is not None:
+                out[key] = vals
+    return out
+
+
 def read_celeba_tfrec_array(path, size):
     """The whole file as one [N, size, size, 3] float32 array without a per-record Python loop: the records of these
     files all have the same length (one serialize_tensor of a fixed-shape float image), so after parsing the first
