@@ -341,7 +341,7 @@ int sv_conv2d_nhwc_fwd(const sv_conv_desc* d, const void* x, const void* w_fwd, 
  * class over the low-res tensor and need the workspace for their border terms; WITHOUT one the call runs the direct fused-resize form on a second
  * weight image that sv_conv2d_prep_weights keeps behind the class images (sv_conv2d_wprep_elems counts it) -- same result to fp32 rounding, 1.4x the time.
  * A workspace smaller than sv_conv2d_fwd_workspace_bytes counts as none (never read or written): the same fallbacks.
- * Form selection is a pure function of the descriptor (and of the SV_NO_POLY* / SV_POLYC_K tuning variables, which must not change between
+ * Form selection is a pure function of the descriptor (and of the SV_POLYC_K switch, which must not change between
  * sv_conv2d_prep_weights and the calls that consume its images). */
 int64_t sv_conv2d_fwd_workspace_bytes(const sv_conv_desc* d);
 int sv_conv2d_nhwc_fwd_ws(const sv_conv_desc* d, const void* x, const void* w_fwd, const float* bias, void* y,
@@ -590,8 +590,8 @@ int sv_lgvae_graph_enable(sv_lgvae_plan* plan, int32_t enable);
  * SV_PHASE_BUCKET_EVENTS is complete: 0 decoders, 1 encoder heads, 2 encoder convs, 3 = 1 and 2 (the whole encoders' range).  The gradient
  * all-reduce of that bucket (RCCL over xGMI) is then enqueued on `stream`.  SV_E_STATE: no such events were recorded.
  * Every call that runs a backward phase invalidates the events of the steps before it; a captured (hipGraph) step records none -- callers then order the
- * collective behind the compute stream instead (split_vae_amd/trainer.py falls back to one all-reduce after the backward).  Weight-gradient slab reduces
- * are never deferred past the events of a call that records them (SV_DEFER_REDUCE is ignored for that call). */
+ * collective behind the compute stream instead (split_vae_amd/trainer.py falls back to one all-reduce after the backward).  Every layer's weight-gradient slab reduce
+ * runs on the layer's own stream right behind its main kernel, so it is in front of the events. */
 int sv_lgvae_bucket_wait(sv_lgvae_plan* plan, int32_t bucket, void* stream);
 /* Test hooks of ONE plan (tests/test_gpu_dist.py); an explicit call, never an environment variable, so nothing a training job inherits can switch them on:
  *   "side_delay_us" = n    the first weight-gradient side-stream launch of every step is held back n microseconds (a consumer that misses the side

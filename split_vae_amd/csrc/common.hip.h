@@ -167,7 +167,7 @@ inline void sv_ensure_dynamic_lds(const void* kernel, size_t bytes) {
 // atomics.  The environment is read once per process.
 // sv_set_deterministic(1 / 0) overrides the environment for the launches that FOLLOW (-1: back to the environment); the choice is made per
 // launch on the host, nothing about a plan or its workspace depends on it (tests flip it around individual comparisons).
-#include <stdlib.h>
+#include "knobs.h"
 #include <atomic>
 inline std::atomic<int>& sv_deterministic_override() {
   static std::atomic<int> v{-1};
@@ -176,17 +176,13 @@ inline std::atomic<int>& sv_deterministic_override() {
 inline bool sv_deterministic() {
   const int o = sv_deterministic_override().load(std::memory_order_relaxed);
   if (o >= 0) return o != 0;
-  static const bool d = getenv("SV_DETERMINISTIC") != nullptr && atoi(getenv("SV_DETERMINISTIC")) != 0;
-  return d;
+  return sv_knob_deterministic();
 }
 
 // SV_TRACE_DISPATCH=1: every sv_conv2d_* call prints one line "sv_dispatch <op> <form>" to stderr naming the form it launched
 // (include/splitvae.h lists the names; tests/test_gpu_conv_api.py checks its cases against them).  The dispatchers record the form where
 // they launch it (sv_trace_note), the API entry prints it after a successful call.  Read once per process; unset, nothing is recorded.
-inline bool sv_trace_dispatch() {
-  static const bool on = getenv("SV_TRACE_DISPATCH") != nullptr;
-  return on;
-}
+inline bool sv_trace_dispatch() { return sv_knob_trace_dispatch(); }
 inline const char*& sv_trace_form() {
   static thread_local const char* f = nullptr;
   return f;
@@ -196,7 +192,8 @@ inline void sv_trace_note(const char* form) {
 }
 
 // Timing-ablation bits (skip staging / the MFMA loop / stores: WRONG results, for profiling only) exist only in builds
-// with -DSV_DEBUG_KNOBS (SV_EXTRA_FLAGS=-DSV_DEBUG_KNOBS python split_vae_amd/build.py); the shipped library has none.
+// with -DSV_DEBUG_KNOBS (SV_EXTRA_FLAGS=-DSV_DEBUG_KNOBS python split_vae_amd/build.py); the shipped library has none.  The host reads
+// them as SV_TUNE_INT knobs (knobs.h); SV_DBG keeps the tests on them out of the shipped kernels.
 #ifdef SV_DEBUG_KNOBS
 #define SV_DBG(x) (x)
 #else

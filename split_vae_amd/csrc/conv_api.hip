@@ -431,7 +431,7 @@ void svg_dgrad_args(const sv_conv_desc* d, int cls, TapGemmArgs* a, uint8_t srct
 // -> false when the classes differ (k = 4: windows {0,-1} and {1,0}), the widths do not fit a 128-column tile, or the
 // caller's images are not contiguous (class_stride = elements between consecutive class images).
 bool svg_dgrad_merged_args(const sv_conv_desc* d, const int64_t* class_off, TapGemmArgs* a) {
-  static const bool off = getenv("SV_NO_CLS_MERGE") != nullptr;        // A/B: one problem per parity class
+  const bool off = sv_knob_no_cls_merge();        // A/B: one problem per parity class
   if (off || d->stride != 2 || (d->Cin & 7) || 4 * d->Cin > 128 || (4 * d->Cin) % 32) return false;
   uint8_t srctap[SV_MAX_TAPS];
   svg_dgrad_args(d, 0, a, srctap);
@@ -491,7 +491,7 @@ void svg_wgrad_args(const sv_conv_desc* d, WgradArgs* a, bool plain) {
       a->dy[kh * d->KW + kw] = (int8_t)(kh - pt);
       a->dx[kh * d->KW + kw] = (int8_t)(kw - pl);
     }
-  static const int target_wgs = getenv("SV_WGRAD_WGS") ? atoi(getenv("SV_WGRAD_WGS")) : 512;
+  static const int target_wgs = SV_TUNE_INT("SV_WGRAD_WGS", 512);
   svg_wgrad_set_msplit(a, svg_pick_cfg(d->Cout), d->dtype, target_wgs);
 }
 
@@ -794,7 +794,7 @@ bool svk_polyc_fwd_plannable(const sv_conv_desc* d) {
 // im2col tile for a layer the tile kernel does not plan (non-power-of-two grids, stride 3: SPAIR's backbone): when the
 // 128-row tiles of svg_pick_cfg leave most of the 256 CUs idle, 64 x 32 tiles (tap-GEMM cfg 4) give 8x the workgroups.
 static int svg_im2col_cfg(const TapGemmArgs& a, int cfg) {
-  static const bool off = getenv("SV_NO_SMALL_IM2COL") != nullptr;
+  static const bool off = SV_TUNE_FLAG("SV_NO_SMALL_IM2COL");
   static const int BMt[4] = {128, 128, 256, 256}, BNt[4] = {128, 64, 32, 16};
   if (off || cfg > 2 || (a.N % 32) || a.splitk > 1) return cfg;
   const int64_t tiles = (int64_t)((a.M + BMt[cfg] - 1) / BMt[cfg]) * ((a.N + BNt[cfg] - 1) / BNt[cfg]);
@@ -824,7 +824,7 @@ extern "C" int sv_conv2d_nhwc_fwd_ws(const sv_conv_desc* d, const void* x, const
   if (!svg_poly(d)) {
     // dense layers (1x1 on a 1x1 grid) with an fp32 pre-activation output: a [B, Cin] x [Cin, Cout] GEMM whose tile grid is a
     // handful of workgroups (SPLIT-GMVAE's y_block / prior / posterior layers, vae/model.py:54-75) -- split K into the zeroed output
-    static const bool no_sk = getenv("SV_NO_DENSE_SPLITK") != nullptr;
+    static const bool no_sk = SV_TUNE_FLAG("SV_NO_DENSE_SPLITK");
     if (!no_sk && d->y_f32 && d->act == SV_ACT_NONE && d->H == 1 && d->W == 1 && d->KH == 1 && d->KW == 1 && !d->ups_in) {
       int cfg = svg_pick_cfg(d->Cout);
       const int sk = svg_choose_splitk(a.M, a.N, (a.P + 7) / 8, &cfg);
@@ -839,7 +839,7 @@ extern "C" int sv_conv2d_nhwc_fwd_ws(const sv_conv_desc* d, const void* x, const
     // Only without an activation (atomics cannot apply one), never under SV_DETERMINISTIC (svg_choose_splitk returns 1).  SV_CONV_SPLITK_TILES: the largest 128 x 128-tile
     // count that takes the form (0: off).  Measured: profiles/r06_gm_streams.txt
     // (SPLIT-GMVAE fp32, 64 images: off 1.708 ms per step, 8 tiles -- the 4 x 4 layer -- 1.656, 32 tiles -- the 8 x 8 layer too -- 1.633)
-    static const int sk_tiles = getenv("SV_CONV_SPLITK_TILES") ? atoi(getenv("SV_CONV_SPLITK_TILES")) : 32;
+    const int sk_tiles = sv_knob_conv_splitk_tiles();
     if (sk_tiles > 0 && d->dtype == SV_F32 && d->act == SV_ACT_NONE && !d->ups_in && !polyc && !svg_s2d3(d) && !svg_packx(d) && d->KH > 1 && d->ldy == d->Cout &&
         (int64_t)((a.M + 127) / 128) * ((a.N + 127) / 128) <= sk_tiles && a.P >= 256) {
       int cfg = svg_pick_cfg(d->Cout);

@@ -29,7 +29,7 @@ static inline void svg_pads(const sv_conv_desc* d, int* pt, int* pl) {
 // Its dY is the ordinary [B,H,W,8] gradient viewed as [B,H,W/2,16].  Forward (tile_conv.hip, depth-to-
 // space stores) and wgrad (wgrad_tile.hip / wgrad_tile_f32.hip, folded reduce) use it, at both precisions; the dgrad keeps the direct form.
 static inline int svg_packx(const sv_conv_desc* d) {
-  static const bool off = getenv("SV_NO_PACKX") != nullptr;
+  static const bool off = SV_TUNE_FLAG("SV_NO_PACKX");
   return !off && d->stride == 1 && d->Cout <= 8 && !(d->Cout & 1) && d->y_f32 &&
          d->ldy == d->Cout && d->KH * (d->KW + 1) <= SV_MAX_TAPS && d->W >= 32 && d->H >= 16 &&
          svg_cin_pad(d) >= 16 && svg_cin_pad(d) <= 64;
@@ -44,8 +44,8 @@ static inline int svg_packx(const sv_conv_desc* d) {
 // along the edges, subtracted by svk_poly_fix (poly_fix.hip).  bf16 only: the fp32 parity path keeps the direct form.
 // (fp32 since round 5: the composite weights are formed in fp32 from the fp32 masters -- the result differs from the direct form by fp32 rounding only)
 static inline int svg_poly(const sv_conv_desc* d) {
-  static const bool off = getenv("SV_NO_POLY") != nullptr;           // A/B: the fused-upsample x-packed conv
-  static const bool off32 = getenv("SV_NO_POLY_F32") != nullptr;     // A/B: fp32 keeps the x-packed form
+  static const bool off = SV_TUNE_FLAG("SV_NO_POLY");           // A/B: the fused-upsample x-packed conv
+  static const bool off32 = SV_TUNE_FLAG("SV_NO_POLY_F32");     // A/B: fp32 keeps the x-packed form
   return !off && (d->dtype == SV_BF16 || !off32) && svg_packx(d) && d->ups_in && d->KH == 6 && d->KW == 6 && d->Cin == svg_cin_pad(d) && d->Cin == 32 &&
          d->H >= 16 && d->W >= 16 && !(d->H & (d->H - 1)) && !(d->W & (d->W - 1)) && d->act == SV_ACT_NONE;
 }
@@ -58,10 +58,10 @@ static inline int svg_poly(const sv_conv_desc* d) {
 // scattering to its sub-pixel (OS = 2, ooy / oox); the border terms (poly_fix.hip: polyc_fix_kernel) are added by the epilogue BEFORE the activation.
 // tests/test_polyphase_math.py pins the algebra for both kernel sizes.
 static inline int svg_polyc(const sv_conv_desc* d) {
-  static const bool off = getenv("SV_NO_POLYC") != nullptr;
+  static const bool off = SV_TUNE_FLAG("SV_NO_POLYC");
   // kernel sizes that take the form.  Measured (fp32, 2 x 512 images): d4 (k 6) forward 1.182 -> 0.88 ms; d3 (k 4: 49 of 64 tap products, four launches' worth of
   // staging and a border pass) 0.549 -> 0.567 ms: k 4 stays on the fused-resize direct form (SV_POLYC_K=64 enables it)
-  const char* ks = getenv("SV_POLYC_K") ? getenv("SV_POLYC_K") : "6";       // (read per call: tests/test_gpu_kernels.py switches it for the k = 4 case)
+  const char* ks = sv_knob_polyc_k();       // (read per call: tests/test_gpu_kernels.py switches it for the k = 4 case)
   if (off || d->dtype != SV_F32 || !d->ups_in || d->stride != 1 || d->KH != d->KW || (d->KH != 6 && d->KH != 4)) return 0;
   if (!strchr(ks, d->KH == 6 ? '6' : '4')) return 0;
   if (d->y_f32 || d->ldy != d->Cout || d->ldx != d->Cin) return 0;
@@ -99,7 +99,7 @@ static inline __host__ __device__ bool svg_polyc_excl(int K, int c, int k) {
 // [B, H/2, W/2, (py, px, c)] the layer is a 3 x 3 stride-1 SAME conv with 12 (padded to 16) channels: K = 9 x 16 = 144, half the MFMAs, and the stride-1 tile path.  The
 // view is formed while the tile is staged (tile_stage.hip.h: stage_tile_s2d3) from the unchanged 8-channel tensor; weights / gradients map by dw_index's s2d3 rule.
 static inline int svg_s2d3(const sv_conv_desc* d) {
-  static const bool off = getenv("SV_NO_S2D3") != nullptr;
+  static const bool off = SV_TUNE_FLAG("SV_NO_S2D3");
   return !off && d->dtype == SV_F32 && d->Cin == 3 && d->ldx == 8 && d->KH == 6 && d->KW == 6 && d->stride == 2 && !d->ups_in && !d->y_f32 &&
          d->H >= 16 && d->W >= 16 && !(d->H & (d->H - 1)) && !(d->W & (d->W - 1)) && d->Cout % 16 == 0;
 }
@@ -121,14 +121,14 @@ static inline int svg_fwd_tap(const sv_conv_desc* d, int kh, int kw) {
 // the same number of atomic passes; prepared weight rows are padded to 128, so either tile fits).
 static inline int svg_choose_splitk(int M, int N, int nk, int* cfg_io = nullptr) {
   static const int BMt[4] = {128, 128, 256, 256}, BNt[4] = {128, 64, 32, 16};
-  static const bool narrow = getenv("SV_SPLITK_NO_NARROW") == nullptr;
+  static const bool narrow = !SV_TUNE_FLAG("SV_SPLITK_NO_NARROW");
   int cfg = svg_pick_cfg(N);
   int tiles = ((M + BMt[cfg] - 1) / BMt[cfg]) * ((N + BNt[cfg] - 1) / BNt[cfg]);
   if (tiles >= 128) return 1;
   if (sv_deterministic()) return 1;        // one workgroup per output tile: a single add per element, whatever the launch order
-  static const bool small = getenv("SV_SPLITK_NO_SMALL") == nullptr;   // 64 x 32 tiles (tap-GEMM cfg 4): +0.8 % on the step; knob restores 128 x 64
+  static const bool small = !SV_TUNE_FLAG("SV_SPLITK_NO_SMALL");   // 64 x 32 tiles (tap-GEMM cfg 4): +0.8 % on the step; knob restores 128 x 64
   if (small && cfg_io && (N % 32) == 0) {
-    static const int tgt_small = getenv("SV_SPLITK_WGS") ? atoi(getenv("SV_SPLITK_WGS")) : 512;
+    static const int tgt_small = SV_TUNE_INT("SV_SPLITK_WGS", 512);
     const int t2 = ((M + 63) / 64) * (N / 32);
     *cfg_io = 4;
     int s2 = (tgt_small + t2 - 1) / t2;
@@ -137,7 +137,7 @@ static inline int svg_choose_splitk(int M, int N, int nk, int* cfg_io = nullptr)
   }
   if (cfg == 0 && cfg_io && narrow) { cfg = 1; tiles *= 2; }
   if (cfg_io) *cfg_io = cfg;
-  static const int target = getenv("SV_SPLITK_WGS") ? atoi(getenv("SV_SPLITK_WGS")) : 128;   // measured best of 64/128/256/512 on the heads and d1
+  static const int target = SV_TUNE_INT("SV_SPLITK_WGS", 128);   // measured best of 64/128/256/512 on the heads and d1
   const int tgt = cfg_io && narrow && cfg == 1 && svg_pick_cfg(N) == 0 ? 2 * target : target;
   int s = (tgt + tiles - 1) / tiles;
   if (s > nk / 2) s = nk / 2;
@@ -192,9 +192,10 @@ int64_t svg_polyc_fix_ws_bytes(const sv_conv_desc* d);
 //   pixels += .0625 sum_{qr,qs} (w[k+r,k+s] - w[k+r,k-s] - w[k-r,k+s] + w[k-r,k-s])^T dy[row qr, column qs].
 // The main term runs on the tile kernel (S = 2); the edge terms come from polyd_edge_kernel through the epilogue's border-term path (TapGemmArgs::fix).
 static inline int svg_polyd(const sv_conv_desc* d) {
-  static const bool off = getenv("SV_NO_POLYD") != nullptr;
-  static const bool bf = getenv("SV_POLYD_BF16") && atoi(getenv("SV_POLYD_BF16")) != 0;     // bf16: opt-in (A/B against the row-ring kernel's fused adjoint)
-  if (off || (d->dtype != SV_F32 && !bf) || !d->ups_in || d->stride != 1 || d->KH != 6 || d->KW != 6 || d->ldx != d->Cin) return 0;
+  static const bool off = SV_TUNE_FLAG("SV_NO_POLYD");
+  // (fp32 only.  At bf16 the form was measured against the row-ring kernel's fused adjoint and removed: dgrad.d4 0.119 -> 0.190 ms, the step 1.654 -> 1.805 ms,
+  //  profiles/r05_polyd_bf16_ab.txt)
+  if (off || d->dtype != SV_F32 || !d->ups_in || d->stride != 1 || d->KH != 6 || d->KW != 6 || d->ldx != d->Cin) return 0;
   if (d->H < 32 || d->W < 32 || (d->H & (d->H - 1)) || (d->W & (d->W - 1))) return 0;      // (the edge kernel works on 16-pixel fragments of the low-res lines)
   // (the edge kernel's instantiations: d4 = 64 -> 32, its 32-channel variant, the head 32 -> 6)
   return (d->Cout == 32 && (d->Cin == 64 || d->Cin == 32)) || (d->Cout <= 8 && d->Cin == 32);

@@ -311,7 +311,7 @@ extern "C" int sv_gm_encoder_backward(sv_gm_encoder* e, const sv_gm_args* a, voi
   // The weight gradients feed only Adam: they go to the library's shared side stream 0 behind a "dY is ready" event, the input-gradient chain (the critical
   // path: 12 layers, one after the other) continues at once; joined at the end of the call.  Every dY buffer is written once per call, the forward activations
   // are read-only here, each layer's variable gradients have one writer.  SV_GM_WGRAD_SIDE=0: everything on `stream` (A/B).  profiles/r06_gm_streams.txt
-  static const bool wside = !(getenv("SV_GM_WGRAD_SIDE") && atoi(getenv("SV_GM_WGRAD_SIDE")) == 0);
+  static const bool wside = SV_TUNE_INT("SV_GM_WGRAD_SIDE", 1) != 0;
   hipStream_t ws2 = wside ? sv_shared_stream(0) : nullptr;
   if (ws2 == st) ws2 = nullptr;
   bool forked = false;

@@ -137,8 +137,8 @@ struct WgradArgs {
   float* ws;          // optional partial-sum workspace for the two-stage (deterministic) flush of the tile kernel
   int64_t ws_bytes;
   hipEvent_t ev_mid[2];   // profiling: when set, both are recorded after the main kernel, before the slab reduce
-  struct WgradReduceDesc* defer; int* n_defer;   // slab path: do NOT launch the reduce, append its descriptor here (svk_wgrad_reduce_all later;
-                                                 // the slab workspace must stay untouched until then)
+  struct WgradReduceDesc* defer; int* n_defer;   // fp32 tile kernel, slab path (polyc_wgrad.hip): do NOT launch the reduce, append its descriptor here
+                                                 // (svk_wgrad_reduce_all later; the slab workspace must stay untouched until then)
   int8_t dy[SV_MAX_TAPS];
   int8_t dx[SV_MAX_TAPS];
 };
@@ -159,7 +159,7 @@ struct WgradTileArgs {
   const void* A; const void* dY; float* dW; float* dbias;
   float* slab; float* ws; int64_t ws_bytes;   // slab = ws when the two-stage flush is used
   float* bslab;                               // with slab: [msplit][128] bias partials behind the dW slabs (summed by the reduce kernel)
-  struct WgradReduceDesc* defer; int* n_defer;   // see WgradArgs
+  struct WgradReduceDesc* defer; int* n_defer;   // unused (the bf16 launch reduces at once); kept: the kernels take this struct by value, the offsets are theirs
   int B, IH, IW, lda, cl2, S, SX, fold_kw, fold_c;
   int layer_id;             // instantiation id (tuning table of svk_wgrad_tile_multi)
   int contig;               // tiles of a workgroup: contiguous run (1) or strided by the grid (0)

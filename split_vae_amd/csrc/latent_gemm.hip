@@ -261,7 +261,7 @@ template <typename T, int BM>
 int launch_nt(const NtGemmMulti& m, hipStream_t st) {
   int gx = 0, gy = 0;
   bool ring = BM == 64;                 // slab launches whose slices span several phases: the ring form
-  static const bool no_ring = getenv("SV_NO_NT_RING") != nullptr;
+  const bool no_ring = sv_knob_no_nt_ring();
   for (int i = 0; i < m.n; ++i) {
     gx = max(gx, (m.p[i].M + BM - 1) / BM);
     gy = max(gy, m.p[i].N / BN);
@@ -302,7 +302,7 @@ int svk_nt_gemm_pick_splitk(int M, int N, int K, int nprob) {
   const int tiles = ((M + bm - 1) / bm) * (N / BN) * (nprob < 1 ? 1 : nprob);
   int s = (256 + tiles - 1) / tiles;
   int maxs = K / BK;
-  static const int cap = getenv("SV_NT_MAXS") ? atoi(getenv("SV_NT_MAXS")) : 0;       // (experiments)
+  static const int cap = SV_TUNE_INT("SV_NT_MAXS", 0);       // (experiments)
   if (cap > 0 && maxs > cap) maxs = cap;
   if (s > maxs) s = maxs;
   if (s < 1) s = 1;
@@ -323,7 +323,7 @@ int svk_nt_gemm_multi(NtGemmProb* p, int n, int bm, hipStream_t st) {
     m.p[i] = p[i];
   }
   if (n == 1) m.p[1] = m.p[0];
-  static const int bm32 = getenv("SV_NT_F32_BM") ? atoi(getenv("SV_NT_F32_BM")) : 0;
+  static const int bm32 = SV_TUNE_INT("SV_NT_F32_BM", 0);
   if (p[0].f32 && bm32) bm = bm32;
   if (p[0].f32) return bm == 64 ? launch_nt<float, 64>(m, st) : launch_nt<float, 128>(m, st);
   return bm == 64 ? launch_nt<bf16_t, 64>(m, st) : launch_nt<bf16_t, 128>(m, st);

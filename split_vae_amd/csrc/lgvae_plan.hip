@@ -123,10 +123,6 @@ struct sv_lgvae_plan {
   int prep_blocks;
   int dec_block0 = 0;           // first block of the decoders' jobs in the table (the encoders' jobs come first): the step prepares the two halves on two streams
   int64_t arena_elems;
-  // slab reduces of the tile weight gradients, deferred: every layer keeps its partial sums in its own workspace region and ONE launch
-  // sums them all after the backward pass (after the side stream has joined).  Opt-in (SV_DEFER_REDUCE=1): see run_wgrad_layers for the measurement
-  WgradReduceDesc red_pending[64];
-  int n_pending = 0;
   bool nll_fused = false;  // the last decoder forward evaluated the loss in the head's epilogue (nllpart_*, g5_* are valid)
   bool gz_clean = false;   // dz accumulators zeroed by the last encoder-forward phase and not yet used
   // the K-slice slabs of d1's input gradient are still unsummed in lat_ws_x / lat_ws_xh: reparam_kl_bwd sums them itself (one launch less)
@@ -154,9 +150,9 @@ struct sv_lgvae_plan {
   bool early_pending = false;
   // captured steps: SV_GRAPH_SIDE=1 lets the capture fork to the side streams too (every fork / join on its OWN event and only the streams a call really used are
   // joined: round 3's capture, which re-recorded one fork event and joined every stream, replayed wrongly on ROCm 7.2).  Off by default: see DESIGN.md section 7.
-  static bool graph_side() { static const bool on = getenv("SV_GRAPH_SIDE") && atoi(getenv("SV_GRAPH_SIDE")) != 0; return on; }
+  static bool graph_side() { return sv_knob_graph_side(); }
   bool side_allowed() const {
-    static const bool off = getenv("SV_NO_SIDE") != nullptr;
+    static const bool off = SV_TUNE_FLAG("SV_NO_SIDE");
     return !(off || (prof_on && prof_filter.empty()) || ((graph_on || dyn) && !graph_side()));
   }
   // fork / join events: one per use while graph replay is on (a captured event node per dependency), the two fixed ones otherwise
@@ -173,7 +169,7 @@ struct sv_lgvae_plan {
     // OPT-IN (SV_EARLY_SIDE=1).  Measured (profiles/r06_ab.txt): the step is no shorter for it at any shard size -- fp32 512 images 9.152 against 9.138 ms without,
     // 64 images 1.690 / 1.689, bf16 512 images 1.661 / 1.646: the encoders' first layers are HBM-bound themselves (e1 reads the whole batch), the weight images' 165 MB
     // beside them slow them by what the overlap saves (fwd.e1 25 -> 52 us at 64 images).  Same finding as round 3's early optimizer tail: no idle resource to hide it in.
-    static const bool on = getenv("SV_EARLY_SIDE") && atoi(getenv("SV_EARLY_SIDE")) != 0;
+    const bool on = sv_knob_early_side();
     if (!on || !side_allowed() || !ensure_side()) return nullptr;
     if (!ev_early && hipEventCreateWithFlags(&ev_early, hipEventDisableTiming) != hipSuccess) return nullptr;
     hipEvent_t ef = fresh_event(ev_fork);
@@ -197,7 +193,7 @@ struct sv_lgvae_plan {
     if (nside) return true;
     {
       // (priority: streams.hip creates the shared streams at the lowest priority; SV_SIDE_PRIO_NORMAL is read there)
-      static const int want = getenv("SV_SIDE_STREAMS") ? atoi(getenv("SV_SIDE_STREAMS")) : 2;      // taken; `side_use` of them are used per call
+      const int want = sv_knob_side_streams(2);      // taken; `side_use` of them are used per call
       const int k = want < 1 ? 1 : want > SIDE_MAX - 1 ? SIDE_MAX - 1 : want;   // the last workspace slot belongs to the main stream
       if (!ev_fork && hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess) return false;
       for (int i = 0; i < k && i < SV_SHARED_STREAMS; ++i) {
@@ -214,7 +210,7 @@ struct sv_lgvae_plan {
     if (!side_allowed()) return st;     // the full per-kernel table wants serial launches; a captured fork/join replayed wrongly on ROCm 7.2 (corrupt gradients, then a crash): captures stay single-stream
     if (!ensure_side()) return st;
     const int use = side_use < nside ? side_use : nside;
-    static const char* order = getenv("SV_SIDE_ORDER");        // experiment: stream per forked layer in launch order, e.g. "0110" (repeats)
+    static const char* order = SV_TUNE_STR("SV_SIDE_ORDER", nullptr);        // experiment: stream per forked layer in launch order, e.g. "0110" (repeats)
     int slot = side_next % use;
     if (order && order[0]) { const int c = order[side_count % (int)strlen(order)] - '0'; if (c >= 0 && c < use) slot = c; }
     ++side_count;
@@ -248,7 +244,6 @@ struct sv_lgvae_plan {
   // gradient-bucket events (SV_PHASE_BUCKET_EVENTS): [bucket][0 = compute stream, 1 + i = side stream i]
   hipEvent_t ev_bucket[3][1 + SIDE_MAX] = {};
   bool bucket_rec[3][1 + SIDE_MAX] = {};
-  bool buckets_now = false;   // the running call records bucket events: weight-gradient reduces must not be deferred past them
   void clear_buckets() {
     for (auto& row : bucket_rec)
       for (auto& b : row) b = false;
@@ -304,6 +299,9 @@ struct sv_lgvae_plan {
 
 namespace {
 
+// A/B: one launch per network for the small pointwise kernels (Sampling + KL and their adjoints) instead of one for the x / x-hat twins
+static bool no_twin_pointwise() { static const bool v = SV_TUNE_FLAG("SV_NO_TWIN_POINTWISE"); return v; }
+
 // SV_ROCTX=1: every plan scope ("fwd.d4", "wgrad.d4", "adam_step" ...) is also a roctx range, so a `rocprofv3 --marker-trace
 // --kernel-trace` timeline names the layers directly.  libroctx64 is bound at run time (no link dependency); off by default.
 #include <dlfcn.h>
@@ -311,8 +309,7 @@ struct Roctx {
   int (*push)(const char*) = nullptr;
   int (*pop)() = nullptr;
   Roctx() {
-    const char* e = getenv("SV_ROCTX");
-    if (!e || !atoi(e)) return;
+    if (!sv_knob_roctx()) return;
     void* h = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
     if (!h) h = dlopen("/opt/rocm/lib/libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
     if (!h) return;
@@ -408,8 +405,8 @@ static void build_layers(sv_lgvae_plan* p) {
     p->dec[k][4] = mk(pre + "d5", H, W, 32, 6, 6, 1, SV_ACT_NONE, 32, 6, 1, pb + 8, true);
     // the three bilinear resizes are fused into the staging of d3/d4/d5's forward and wgrad tiles (needs >= 16 output pixels per image for
     // the tile kernels: any H >= 16 here); fp32 since round 4 too (wgrad_tile_f32.hip; SV_F32_MATERIALISE_UPSAMPLE=1: u2 / u3 / u4 written out)
-    static const bool no_fuse = getenv("SV_NO_FUSED_UPSAMPLE") != nullptr;
-    static const bool f32_mat = getenv("SV_F32_MATERIALISE_UPSAMPLE") != nullptr;
+    static const bool no_fuse = SV_TUNE_FLAG("SV_NO_FUSED_UPSAMPLE");
+    static const bool f32_mat = SV_TUNE_FLAG("SV_F32_MATERIALISE_UPSAMPLE");
     if ((d.dtype == SV_BF16 || !f32_mat) && !no_fuse && H >= 16)
       for (int l = 2; l <= 4; ++l) p->dec[k][l].d.ups_in = 1;
   }
@@ -537,7 +534,6 @@ static void build_buffers(sv_lgvae_plan* p) {
   p->add_buf("jobs", (int64_t)p->jobs.size() * sizeof(PrepJob));
   p->add_buf("warena", p->arena_elems * es);
   p->add_buf("wgrad_ws", SV_WGRAD_WS_BYTES * SV_WGRAD_MAX_MULTI * sv_lgvae_plan::SIDE_MAX);   // per side stream, per problem
-  if (getenv("SV_DEFER_REDUCE")) p->add_buf("wslab", SV_WGRAD_WS_BYTES * SV_WGRAD_MAX_MULTI * 7);    // per tile-wgrad layer (e1 e2 e3 d2 d3 d4 d5) and problem: deferred reduces
   p->add_buf("polyfix_x", svk_poly_fix_ws_bytes((int)B, (int)H / 2, (int)W / 2));   // border terms of the polyphase head (poly_fix.hip)
   if (!go) p->add_buf("polyfix_xh", svk_poly_fix_ws_bytes((int)B, (int)H / 2, (int)W / 2));
   {   // border terms of the per-class polyphase layers (d3, d4): one region per network, sized for the largest layer (the layers run one after the other)
@@ -633,12 +629,12 @@ static void build_buffers(sv_lgvae_plan* p) {
 // kernel's split-K atomics; SV_NO_LATENT_GEMM restores the old launches (A/B)
 // the slab sums of the two split-K launches live in their consumers (Sampling + KL forward / backward) instead of nt_slab_reduce_kernel
 static bool latent_fuse_on() {
-  static const bool off = getenv("SV_NO_LATENT_FUSE") != nullptr;
+  const bool off = sv_knob_no_latent_fuse();
   return !off;
 }
 static bool latent_gemm_on(const sv_lgvae_plan* p) {
-  static const bool off = getenv("SV_NO_LATENT_GEMM") != nullptr;
-  static const bool off32 = getenv("SV_NO_LATENT_GEMM_F32") != nullptr;       // (A/B: the fp32 forms of latent_gemm.hip)
+  static const bool off = SV_TUNE_FLAG("SV_NO_LATENT_GEMM");
+  const bool off32 = sv_knob_no_latent_gemm_f32();       // (A/B: the fp32 forms of latent_gemm.hip)
   return !off && (p->d.dtype == SV_BF16 || !off32);
 }
 
@@ -823,8 +819,8 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
   // register file: nothing co-resides with it, so beside the input-gradient chain it only gets the CUs that chain leaves (0.147 ms alone,
   // 0.27 live).  From 768 images per launch it stays on the main stream instead of d5's (re-measured, B = 512: "e1,e2,d5" 2.073 / 2.078 ms,
   // "e1,e2,d4" 2.056 / 2.063, "e1,e2,d5,d4" 2.072, "e1,e2,d4,d3" 2.076; B = 256 +-0, B = 128 / 64: +2.5 %, so not below the threshold)
-  static const char* on_main_env = getenv("SV_WGRAD_MAIN");
-  static const bool roll_off = getenv("SV_NO_WGRAD_ROLL") != nullptr;
+  const char* const on_main_env = sv_knob_wgrad_main();
+  const bool roll_off = sv_knob_no_wgrad_roll();
   const bool big = n * L[0]->d.B >= 768;
   // With TWO side streams (whole bf16 steps at this size, see run_phases) only the two tail layers stay: "e1,e2" 2.004 / 2.006 ms,
   // "e1,e2,d1" 2.008, "e1" / "e2" 2.03, "" 2.039, "e1,e2,d4" 2.061, "e1,e2,d5" 2.119.
@@ -856,10 +852,10 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
   }
   // the decoder head's weight gradient in polyphase form (poly_wgrad.hip) from ~768 images per launch (its three small
   // kernels cost more than they save below that: 16 images 42 vs 20 us; 1024 images 132 vs 184 us)
-  static const bool no_pw = getenv("SV_NO_POLY_WGRAD") != nullptr;
+  static const bool no_pw = SV_TUNE_FLAG("SV_NO_POLY_WGRAD");
   // (round 2, tile-kernel main term: 512 images per launch +0.4 %, 1024 -1.0 % -> 768; round 4, rolling-window main term (wgrad_p5.hip): 512 images per
   //  launch -0.7 %, 256 +2.5 % -> 512: profiles/r04_poly_wgrad_min_sweep.txt)
-  static const int pw_min = getenv("SV_POLY_WGRAD_MIN") ? atoi(getenv("SV_POLY_WGRAD_MIN")) : 512;
+  static const int pw_min = SV_TUNE_INT("SV_POLY_WGRAD_MIN", 512);
   if (!no_pw && L[0]->d.dtype == SV_BF16 && svg_poly(&L[0]->d) && n * L[0]->d.B >= pw_min && n <= 2 &&
       svk_poly_wgrad_supported(L[0]->d.H / 2, L[0]->d.W / 2, svg_cin_pad(&L[0]->d), L[0]->d.Cout)) {   // else: the direct form below
     static const char* pw_name[2] = {"polyw_x", "polyw_xh"};
@@ -881,7 +877,7 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
     return svk_poly_wgrad_finish(n, x, dy, pw, dwv, dbv, d.B, d.H / 2, d.W / 2, d.ldx, Cin, d.Cout, SV_POLY_WGRAD_NWG, st);
   }
   // fp32: the polyphase weight gradient of the upsample -> conv layers (polyc_wgrad.hip: d4 per parity class, the head merged)
-  static const int pcw_min = getenv("SV_POLYC_WGRAD_MIN") ? atoi(getenv("SV_POLYC_WGRAD_MIN")) : 0;
+  static const int pcw_min = SV_TUNE_INT("SV_POLYC_WGRAD_MIN", 0);
   if (L[0]->d.dtype == SV_F32 && n <= 2 && n * L[0]->d.B >= pcw_min && svg_polyc_wgrad_form(&L[0]->d) && !(p->polycw_bad >> (ln[1] - '0' - 1) & 1) &&
       p->bufidx.count("polycw" + std::to_string(ln[1] - '0' - 1) + "_x")) {
     const std::string base = "polycw" + std::to_string(ln[1] - '0' - 1);          // layer name d<k>: index k - 1 in dec[]
@@ -899,29 +895,19 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
     p->polycw_bad |= 1u << (ln[1] - '0' - 1);
     fl = 0;
   }
-  // measured (profiles/r03_f_defer.txt): one launch instead of seven saves 20-26 us of SERIAL time, but the slabs (~250 MB a step) are then read
-  // cold from HBM on the critical path after the join instead of warm from L2 / MALL on the side stream: B = 512 -0.5..1 %, B = 64 +5 %.  Opt-in.
-  static const bool no_defer = getenv("SV_DEFER_REDUCE") == nullptr;
-  static const char* slots[7] = {"e1", "e2", "e3", "d2", "d3", "d4", "d5"};
-  int slot = -1;
-  for (int k = 0; k < 7; ++k) if (ln == slots[k]) slot = k;
-  // (not while gradient-bucket events are recorded: a deferred reduce writes dW / dbias AFTER the events the all-reduce waits on)
-  const bool defer = !no_defer && !p->buckets_now && slot >= 0 && L[0]->d.dtype == SV_BF16 && n <= SV_WGRAD_MAX_MULTI;
+  // (every layer reduces its own slabs on its own stream.  One reduce for all layers after the join was measured and removed: profiles/r03_f_defer.txt,
+  // the slabs are then read cold from HBM on the critical path -- B = 512 -0.5..1 %, B = 64 +5 %)
   for (int i = 0; i < n; ++i) {
     svg_wgrad_args(&L[i]->d, &a[i]);
     a[i].A = x[i]; a[i].dY = dy[i];
     a[i].dW = grads + p->params[L[i]->kparam].off;
     a[i].dbias = grads + p->params[L[i]->bparam].off;
     a[i].ws = (float*)((char*)p->bp("wgrad_ws") + (p->side_slot * SV_WGRAD_MAX_MULTI + i) * wsb); a[i].ws_bytes = wsb;
-    if (defer) {                        // its own slab region, reduced with every other layer's after the backward pass
-      a[i].ws = (float*)((char*)p->bp("wslab") + (int64_t)(slot * SV_WGRAD_MAX_MULTI + i) * SV_WGRAD_WS_BYTES); a[i].ws_bytes = SV_WGRAD_WS_BYTES;
-      a[i].defer = p->red_pending; a[i].n_defer = &p->n_pending;
-    }
     fl += conv_flops(L[i]->d);
   }
   Scope sc(p, st, nm, fl, by);
   sc.issued(fl);                        // (a polyphase form above may have been refused after booking its count)
-  if (!defer) sc.split(nm + ".reduce", 0, a[0].ev_mid);
+  sc.split(nm + ".reduce", 0, a[0].ev_mid);
   return svk_wgrad_dispatch_multi(a, n, L[0]->d.dtype, svg_pick_cfg(L[0]->d.Cout), st);
 }
 static int run_wgrad_layer(sv_lgvae_plan* p, Layer& L, const void* x, const void* dy, float* grads, hipStream_t st) {
@@ -945,7 +931,7 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
   const int B = d.B, H = d.H, W = d.W, dt = d.dtype;
   const int Lg = d.global_latent, Ll = d.local_latent, Lc = Lg + Ll;
   const char* en[2] = {"x", "xh"};
-  static const bool no_twin = getenv("SV_NO_TWIN_POINTWISE") != nullptr;   // A/B: one launch per network for the small pointwise kernels
+  const bool no_twin = no_twin_pointwise();
   bool pre_slabs = false;
   int pre_S[2] = {0, 0};
   int64_t pre_stride[2] = {0, 0};
@@ -1194,10 +1180,10 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
     // ReluGrad in the epilogue of Conv2DBackpropInput: the hi-res gradient gu never reaches HBM) ...
     // (it works on whole images -- its low-res rows straddle row bands -- so below ~one image per workgroup slot the banded
     // plain input gradient + upsample2x_bwd is faster: 64 images per network d5 43 vs 55 us, d4 40 vs 49; 128: 69 vs 56)
-    static const bool no_adj = getenv("SV_NO_FUSED_ADJOINT") != nullptr;
+    static const bool no_adj = SV_TUNE_FLAG("SV_NO_FUSED_ADJOINT");
     // (round 4, with the adjoint of d3 / d4 on the matrix pipe: 128 images per launch -- config 4's 64-image shard -- 0.641 -> 0.631 ms fused; the
     //  default moved from 256 to 128)
-    static const int adj_min = getenv("SV_RC_ADJ_MIN") ? atoi(getenv("SV_RC_ADJ_MIN")) : 128;
+    static const int adj_min = SV_TUNE_INT("SV_RC_ADJ_MIN", 128);
     int frc = SV_E_UNSUPPORTED;
     if (Ls[0]->wdp_off >= 0 && (nd == 1 || Ls[1]->wdp_off >= 0)) {
       // fp32: the polyphase form (polyd_dgrad.hip): conv-transpose + resize adjoint + ReLU gate as one stride-2 conv over dY, edge terms through a workspace
@@ -1274,7 +1260,7 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
       if (rc == SV_OK) {
         done = true;
         p->lat_d1_ok = true;
-        static const bool no_twin = getenv("SV_NO_TWIN_POINTWISE") != nullptr;
+        const bool no_twin = no_twin_pointwise();
         if (latent_fuse_on() && !d.external_global_encoder && !no_twin && q[0].splitk <= 16 && q[1].splitk <= 16) {     // reparam_kl_bwd sums the slabs (SPLIT-GMVAE reads gz_x: summed here)
           p->dz_slabs = true;
           for (int k = 0; k < 2; ++k) { p->dz_S[k] = q[k].splitk; p->dz_stride[k] = q[k].slab_stride; }
@@ -1302,7 +1288,7 @@ static int phase_bwd_encoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, boo
   }
   if (do_heads) {
     Scope sc(p, st, "reparam_kl_bwd", 0, 0);
-    static const bool no_twin = getenv("SV_NO_TWIN_POINTWISE") != nullptr;
+    const bool no_twin = no_twin_pointwise();
     if (!e0 && !no_twin) {
       const float* dz[2] = {(const float*)p->bp("gz_x"), (const float*)p->bp("gz_x") + Lg};
       const float* dz2[2] = {nullptr, (const float*)p->bp("gz_xh")};
@@ -1516,7 +1502,7 @@ static int run_phases(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t
     // B = 256 +1.8 %, 128 +6 %, 64 +3 % (launches too small to share the chip three ways); a data-parallel step (phase-split calls: the
     // communication stream is a further active queue) 2.14 -> 2.15 ms over torch's nccl, 2.12 -> 3.31 ms over sv_comm (four active streams
     // on GPU_MAX_HW_QUEUES = 3): one.  SV_SIDE_STREAMS forces a count.
-    static const int forced = getenv("SV_SIDE_STREAMS") ? atoi(getenv("SV_SIDE_STREAMS")) : 0;
+    const int forced = sv_knob_side_streams(0);
     const bool whole = (ph & SV_PHASE_ALL) == SV_PHASE_ALL;
     // fp32 (round 5, polyphase decoder layers + 52-KB weight-gradient tiles): two side streams 9.60-9.62 -> 9.37-9.39 ms at B = 512 (profiles/r05_f32_streams.txt)
     // (fp32, 256 images per network: 5.14 -> 5.09 ms; 128: 2.84 -> 2.87: from 256)
@@ -1532,8 +1518,8 @@ static int run_phases(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t
   }
   if (ph & SV_PHASE_PREP) SV_TRY(phase_prep(p, s, st, early));
   if (early) SV_TRY(p->early_done(early));
-  static const bool no_fused_nll = getenv("SV_NO_FUSED_NLL") != nullptr;    // A/B: dlogistic_kernel after the forward
-  static const bool no_fused_nll_f32 = getenv("SV_NO_FUSED_NLL_F32") != nullptr;    // (fp32 since round 6; A/B)
+  static const bool no_fused_nll = SV_TUNE_FLAG("SV_NO_FUSED_NLL");    // A/B: dlogistic_kernel after the forward
+  static const bool no_fused_nll_f32 = SV_TUNE_FLAG("SV_NO_FUSED_NLL_F32");    // (fp32 since round 6; A/B)
   const bool want_nll = !no_fused_nll && (ph & SV_PHASE_FWD_DECODERS) && (ph & SV_PHASE_LOSS) && s->grads && s->images6 &&
                         (p->d.dtype == SV_BF16 || !no_fused_nll_f32);
   if (!(ph & SV_PHASE_FORWARD)) p->nll_fused = false;
@@ -1550,7 +1536,6 @@ static int run_phases(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t
   // a backward phase invalidates the events of every earlier step: sv_lgvae_bucket_wait must never succeed against events that belong to gradients
   // of a previous step (it returns SV_E_STATE instead, and the trainer falls back to ordering the collective behind the compute stream)
   if (ph & SV_PHASE_BACKWARD) p->clear_buckets();
-  p->buckets_now = buckets;
   if (ph & SV_PHASE_BWD_DECODERS) {
     SV_TRY(phase_bwd_decoders(p, s, st));
     if (buckets) SV_TRY(p->record_bucket(0, st));
@@ -1558,12 +1543,6 @@ static int run_phases(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t
   if (ph & (SV_PHASE_BWD_ENC_HEADS | SV_PHASE_BWD_ENC_CONVS))
     SV_TRY(phase_bwd_encoders(p, s, ph & SV_PHASE_BWD_ENC_HEADS, ph & SV_PHASE_BWD_ENC_CONVS, st, buckets));
   SV_TRY(p->join_side(st));
-  if (p->n_pending) {                    // every layer's partial sums -> dW / dbias, one launch (fixed order: deterministic)
-    Scope sc(p, st, "wgrad.all.reduce", 0, 0);
-    const int np = p->n_pending;
-    p->n_pending = 0;
-    SV_TRY(svk_wgrad_reduce_all(p->red_pending, np, st));
-  }
   if (ph & SV_PHASE_ADAM) {
     Scope sc(p, st, "adam_step", 0, (double)p->nparams * 28);
     SV_TRY(svk_adam_step(s->params, s->grads, s->adam_m, s->adam_v, p->nparams, s->lr, s->beta1, s->beta2,

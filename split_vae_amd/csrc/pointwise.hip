@@ -927,7 +927,7 @@ extern "C" int sv_upsample2x_bwd(const void* g_hi, const void* y_lo_mask, void* 
                        dim3(256), 0, st, (const bf16_t*)g_hi, (const bf16_t*)y_lo_mask, (bf16_t*)g_lo, B, H, W, C);
   } else if (dtype == SV_F32) {
     if (C % 4) return SV_E_UNSUPPORTED;
-    static const bool plain = getenv("SV_UPS_BWD_PLAIN") != nullptr;            // A/B knob: one thread per output, sixteen loads each
+    const bool plain = sv_knob_ups_bwd_plain();            // A/B knob: one thread per output, sixteen loads each
     const int64_t band_threads = (int64_t)B * (H / 8) * W * (C / 4);
     if (!plain && H % 8 == 0 && band_threads >= 256 * 256)                      // (small launches keep the per-output form: more threads)
       hipLaunchKernelGGL((upsample2x_bwd_rows_kernel<8>), dim3(grid_for(band_threads)), dim3(256), 0, st, (const float*)g_hi,

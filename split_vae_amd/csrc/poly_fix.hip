@@ -282,7 +282,7 @@ int svk_poly_fix_multi(int n, const void* const* x_lo, const void* const* wfix, 
     m.out6[i] = out6 ? out6[k] : nullptr; m.fixbuf[i] = fixbuf ? fixbuf[k] : nullptr;
     if (!m.out6[i] && !m.fixbuf[i]) return SV_E_BADARG;
   }
-  static const int dbg = SV_DBG(getenv("SV_PF_DBG") ? atoi(getenv("SV_PF_DBG")) : 0);   // ablation: 1 skip the lines, 2 skip the classes, 4 skip the stores
+  static const int dbg = SV_TUNE_INT("SV_PF_DBG", 0);   // ablation: 1 skip the lines, 2 skip the classes, 4 skip the stores
   if (dtype == SV_BF16) {
     sv_ensure_dynamic_lds((const void*)poly_fix_kernel<bf16_t>, lds);
     hipLaunchKernelGGL(poly_fix_kernel<bf16_t>, dim3(B, n), dim3(256), lds, st, m, h, w, lda, Cout, dbg);

@@ -26,7 +26,7 @@ namespace {
 // LDS -> barrier -> 8-16 short K steps), so the next image's loads are issued BEFORE the current image's MFMAs and land in LDS after them (register prefetch).
 constexpr int FRAME_GROUPS_MAX = 64; // (round 5, with the group sum as its own streaming pass: more, shorter workgroups hide each other's load latency)
 static int frame_groups() {
-  static const int g = getenv("SV_POLYC_FRAME_GROUPS") ? atoi(getenv("SV_POLYC_FRAME_GROUPS")) : 32;      // in the step (2 x 512 images): 16 groups 9.80-9.84 ms, 32: 9.795, 64: 9.86-9.89 (serial: 137 / 101 / 101 us for d4)
+  static const int g = SV_TUNE_INT("SV_POLYC_FRAME_GROUPS", 32);      // in the step (2 x 512 images): 16 groups 9.80-9.84 ms, 32: 9.795, 64: 9.86-9.89 (serial: 137 / 101 / 101 us for d4)
   return g < 1 ? 1 : g > FRAME_GROUPS_MAX ? FRAME_GROUPS_MAX : g;
 }
 
@@ -243,7 +243,7 @@ static inline int64_t dwp_floats(const sv_conv_desc* d, int merged, int coff[4])
 
 // does the layer have a polyphase weight gradient at fp32?  1: per class (svg_polyc), 2: merged head (svg_poly)
 int svg_polyc_wgrad_form(const sv_conv_desc* d) {
-  static const bool off = getenv("SV_NO_POLYC_WGRAD") != nullptr;
+  static const bool off = SV_TUNE_FLAG("SV_NO_POLYC_WGRAD");
   if (off || d->dtype != SV_F32) return 0;
   const int cin = svg_cin_pad(d);
   if (svg_polyc(d) && d->KH == 6 && d->Cout == 32 && (cin == 64 || cin == 32) && d->H / 2 >= 8 && d->W / 2 >= 8 && d->H <= 64 && d->W <= 64) return 1;    // (instantiations: d4)
@@ -295,7 +295,7 @@ int svk_polyc_wgrad_multi(const sv_conv_desc* d, int n, const void* const* x_lo,
     if (hipMemsetAsync(pw[i] + ndwp, 0, 128 * sizeof(float), st) != hipSuccess) return (int)hipGetLastError();
   // OPT-IN forms that stage the input tile once for several classes (wgrad_tile_f32.hip: wgrad_polyc_f32_kernel).  SV_WGRAD_POLYC_FUSED=1: all four classes in one launch
   // (168 accumulator registers; profiles/r05_polyc_fused_ab.txt: 1.078 -> 0.949 ms alone on the chip, the 512-image step +2 %); =2: classes {0, 3} and {1, 2} as two launches
-  static const int fuse_mode = getenv("SV_WGRAD_POLYC_FUSED") ? atoi(getenv("SV_WGRAD_POLYC_FUSED")) : 0;
+  const int fuse_mode = sv_knob_wgrad_polyc_fused();
   bool fused = false;
   if (!merged && (fuse_mode == 1 || fuse_mode == 2)) {
     WgradArgs cls[8];

@@ -167,16 +167,10 @@ template <typename T, int NT, int NGRP, int NLI>
 static int launch_edge_n(const PolydEdgeMulti& m, int n, int B, int h, int w, int Cin, int gdy, int K, size_t lds, hipStream_t st) {
   int groups = (B + 7) / 8;                                 // ~8 images per workgroup
   if (groups < 1) groups = 1;
-  // strips in flight per thread: SV_POLYD_DEPTH (1: one image ahead, the default; 2: two register sets).  Measured and NOT kept (profiles/r06_polyd_depth.txt): depth 2 costs
-  // 20 VGPRs (152 -> 172: two resident workgroups per CU instead of three) and the 512-image fp32 step goes 9.13 -> 9.29 ms, the 64-image one 1.690 -> 1.697
-  static const int depth = getenv("SV_POLYD_DEPTH") ? atoi(getenv("SV_POLYD_DEPTH")) : 1;
-  if (depth >= 2) {
-    sv_ensure_dynamic_lds((const void*)polyd_edge_kernel<T, NT, NGRP, NLI, 2>, lds);
-    hipLaunchKernelGGL((polyd_edge_kernel<T, NT, NGRP, NLI, 2>), dim3(4 * (Cin >> 4), groups, n), dim3(256), lds, st, m, B, h, w, Cin, gdy, K);
-  } else {
-    sv_ensure_dynamic_lds((const void*)polyd_edge_kernel<T, NT, NGRP, NLI, 1>, lds);
-    hipLaunchKernelGGL((polyd_edge_kernel<T, NT, NGRP, NLI, 1>), dim3(4 * (Cin >> 4), groups, n), dim3(256), lds, st, m, B, h, w, Cin, gdy, K);
-  }
+  // strips in flight per thread (DEPTH): one image ahead.  Two register sets were measured and NOT kept (profiles/r06_polyd_depth.txt): depth 2 costs 20 VGPRs
+  // (152 -> 172: two resident workgroups per CU instead of three) and the 512-image fp32 step goes 9.13 -> 9.29 ms, the 64-image one 1.690 -> 1.697
+  sv_ensure_dynamic_lds((const void*)polyd_edge_kernel<T, NT, NGRP, NLI, 1>, lds);
+  hipLaunchKernelGGL((polyd_edge_kernel<T, NT, NGRP, NLI, 1>), dim3(4 * (Cin >> 4), groups, n), dim3(256), lds, st, m, B, h, w, Cin, gdy, K);
   SV_LAUNCH_CHECK();
   hipLaunchKernelGGL((polyd_corner_kernel<T, NGRP>), dim3(4 * (Cin >> 4), (B + 63) / 64, n), dim3(256), 0, st, m, B, h, w, Cin, gdy, K);
   SV_LAUNCH_CHECK();
@@ -215,7 +209,6 @@ int svk_polyd_dgrad_multi(const sv_conv_desc* d, int n, const void* const* dy, c
   int rc = SV_E_UNSUPPORTED;
   if (d->dtype == SV_F32 && K == 6 && cop == 32) rc = launch_edge<float, 9, 2>(m, n, d->B, h, w, cin, gdy, K, st);
   else if (d->dtype == SV_F32 && K == 6 && cop == 16) rc = launch_edge<float, 9, 1>(m, n, d->B, h, w, cin, gdy, K, st);
-  else if (d->dtype == SV_BF16 && K == 6 && cop == 32) rc = launch_edge<bf16_t, 9, 1>(m, n, d->B, h, w, cin, gdy, K, st);      // (32 dY channels = one bf16 MFMA group: d4 exactly, the head padded)
   if (rc) return rc;
   for (int i = 0; i < n; ++i) {
     svg_polyd_args(d, &a[i]);

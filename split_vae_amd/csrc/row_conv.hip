@@ -1011,14 +1011,14 @@ static int launch_row(const RowConvArgs* a, int n, hipStream_t st) {
   m.dbg = 0;
   m.stamps = nullptr;
 #ifdef SV_DEBUG_KNOBS
-  static const int dbg = getenv("SV_RC_DBG") ? atoi(getenv("SV_RC_DBG")) : 0;
+  static const int dbg = SV_TUNE_INT("SV_RC_DBG", 0);
   m.dbg = dbg;
   static unsigned long long* stamp_buf = nullptr;
-  static const bool stamp = getenv("SV_RC_STAMP") != nullptr;
+  static const bool stamp = SV_TUNE_FLAG("SV_RC_STAMP");
   if (stamp && !stamp_buf) (void)hipMalloc(&stamp_buf, 512 * 8 * 8 * 8);
   if (stamp) { m.stamps = stamp_buf; (void)hipMemsetAsync(stamp_buf, 0, 512 * 8 * 8 * 8, st); }
 #endif
-  static const int wgs_env = getenv("SV_RC_WGS") ? atoi(getenv("SV_RC_WGS")) : 0;
+  static const int wgs_env = SV_TUNE_INT("SV_RC_WGS", 0);
   const int wgs_max = wgs_env ? wgs_env : 256 * (C::WAVES == 8 ? 1 : 2);                 // one 8-wave or two 4-wave (or two 2-wave, 512-register) workgroups per CU
   int grid = m.units < wgs_max ? m.units : wgs_max;
   if (C::PAIR) grid = grid / n * n;                          // a workgroup stays on one problem (see the kernel's unit decode)
@@ -1070,9 +1070,8 @@ using RC_e2g  = RowCfg<3, 3, 64, 128, 16, 4, 2, 1, 1, 1, false, 4, false, true>;
 using RC_d2   = RowCfg<4, 4, 128, 64, 16, 4, 1, 2, 1, 1, false, 8, false, false, false, true>;
 // e3 forward (k 4, stride 2, 64 -> 128 channels, 16 x 16 -> 8 x 8): space-to-depth with shifted blocks (K 1024) on image pairs
 using RC_e3f  = RowCfg<2, 2, 256, 128, 16, 4, 1, 1, 1, 1, false, 8, false, false, true, true>;
-// e3 input gradient (k 4, stride 2): its four parity classes are four 2 x 2 stride-1 problems over the 8 x 8 dY grid with their own windows
-// (K 512, 64 columns each, class -> sub-pixel store with the ReLU mask): eight problems per launch (classes x networks) on image pairs
-using RC_e3g  = RowCfg<2, 2, 128, 64, 16, 4, 1, 1, 1, 1, false, 4, false, false, false, true, true>;
+// (e3's input gradient as eight class problems on image pairs -- the REV_ argument of RowCfg, which only CLS_ implies now -- was measured and removed: 2 x 512 images 0.050 ms here against
+// 0.044 on the tile kernel, eight problems of two 4-row steps per image pair are all prologue)
 // e2 forward (k 6, stride 2, 32 -> 64 channels) as a 3 x 3 stride-1 conv over the space-to-depth input (K 1152)
 using RC_e2f  = RowCfg<3, 3, 128, 64, 16, 4, 1, 1, 1, 1, false, 4, false, false, true>;
 // e1 forward (k 6, stride 2, 8-channel padded RGB -> 32 channels) the same way: 32 s2d channels = ONE K chunk per tap (K 288)
@@ -1082,8 +1081,13 @@ using RC_e1f  = RowCfg<3, 3, 32, 32, 32, 4, 1, 1, 2, 1, false, 4, false, false, 
 
 // n (1 or 2: the x / x-hat twins) tap-GEMM problems of identical geometry on the row-ring kernel; SV_E_UNSUPPORTED when
 // the shape has no instantiation (the caller falls back to the tile kernel)
+// A/B: the forward's resize / the input gradient's resize adjoint back on the VALU forms (stage_rows / adjoint_rows): d4 and d3, or d3 only
+static bool rc_no_mb() { static const bool v = SV_TUNE_FLAG("SV_RC_NO_MB"); return v; }
+static bool rc_no_mb3() { static const bool v = rc_no_mb() || SV_TUNE_FLAG("SV_RC_NO_MB3"); return v; }
+static bool rc_no_ma() { static const bool v = SV_TUNE_FLAG("SV_RC_NO_MA"); return v; }
+static bool rc_no_ma3() { static const bool v = rc_no_ma() || SV_TUNE_FLAG("SV_RC_NO_MA3"); return v; }
 static int row_plan(const TapGemmArgs* t, int n, int dtype, RowConvArgs* a, int* nprob = nullptr) {      // a[4]; -> instantiation id (and the number of kernel problems), or SV_E_UNSUPPORTED
-  static const bool off = getenv("SV_NO_ROWCONV") != nullptr;          // A/B: the tile kernel for every layer
+  const bool off = sv_knob_no_rowconv();          // A/B: the tile kernel for every layer
   if (off || dtype != SV_BF16 || n < 1 || n > 8) return SV_E_UNSUPPORTED;
   int cfg = -1;
   if (nprob) *nprob = n;
@@ -1091,11 +1095,11 @@ static int row_plan(const TapGemmArgs* t, int n, int dtype, RowConvArgs* a, int*
   for (int i = 0; i < n; ++i) {
     const TapGemmArgs& p = t[i];
     if (p.lOY < 0 || p.lOX < 0) return SV_E_UNSUPPORTED;
-    if (n > 2 && !(getenv("SV_RC_E3G") && p.S == 1 && p.OS == 2 && p.ntaps == 4 && !p.cls_n)) return SV_E_UNSUPPORTED;   // more than the twins: only e3's class problems
-    static const bool no_cls = getenv("SV_RC_NO_CLS") != nullptr;     // A/B: merged parity classes on the tile kernel
-    static const bool no_s2d = getenv("SV_RC_NO_S2D") != nullptr;     // A/B: the stride-2 forward on the tile kernel
-    static const bool no_pair_s2d = getenv("SV_RC_NO_E3") != nullptr; // A/B: e3's forward on the tile kernel
-    static const int e3_min = getenv("SV_RC_E3_MIN") ? atoi(getenv("SV_RC_E3_MIN")) : 256;
+    if (n > 2) return SV_E_UNSUPPORTED;                               // one problem or the x / x-hat twins
+    const bool no_cls = sv_knob_rc_no_cls();     // A/B: merged parity classes on the tile kernel
+    static const bool no_s2d = SV_TUNE_FLAG("SV_RC_NO_S2D");     // A/B: the stride-2 forward on the tile kernel
+    static const bool no_pair_s2d = SV_TUNE_FLAG("SV_RC_NO_E3"); // A/B: e3's forward on the tile kernel
+    static const int e3_min = SV_TUNE_INT("SV_RC_E3_MIN", 256);
     const bool cls = p.cls_n > 0;
     if (p.S == 2 && p.SX == 2 && !cls) {                               // stride-2 forward: the space-to-depth form
       if (no_s2d || p.OS != 1 || p.splitk != 1 || p.d2s || p.out_f32 || p.ooy || p.oox || p.mask || p.adj || p.ups) return SV_E_UNSUPPORTED;
@@ -1125,33 +1129,10 @@ static int row_plan(const TapGemmArgs* t, int n, int dtype, RowConvArgs* a, int*
       if (i && (r.B != a[0].B || r.H != a[0].H || r.bands != a[0].bands)) return SV_E_UNSUPPORTED;
       continue;
     }
-    // (measured, 2 x 512 images: 0.050 ms here against 0.044 on the tile kernel -- eight problems of two 4-row steps per image pair are all
-    // prologue --, so only SV_RC_E3G=1 sends it here)
-    static const bool e3g = getenv("SV_RC_E3G") != nullptr;
-    if (e3g && !cls && p.S == 1 && p.SX == 1 && p.OS == 2 && p.ntaps == 4 && p.N == 64 && p.lOX == 3 && p.lOY == 3 && !p.ups && !p.adj) {
-      const int cin = (1 << p.cl2) * 8;
-      if (p.splitk != 1 || p.d2s || p.out_f32 || p.bias || cin != 128 || p.lda != 128 || p.Ktot != 4 * 128 || p.ldo < 64) return SV_E_UNSUPPORTED;
-      if (p.IH != 8 || p.IW != 8 || p.OHF != 16 || p.OWF != 16 || (unsigned)p.ooy > 1u || (unsigned)p.oox > 1u) return SV_E_UNSUPPORTED;
-      for (int q = 0; q < 4; ++q)                                      // the class's own order: y-major, offsets descending
-        if (p.dy[q] != p.dy[0] - q / 2 || p.dx[q] != p.dx[0] - q % 2) return SV_E_UNSUPPORTED;
-      if (i && cfg != 13) return SV_E_UNSUPPORTED;
-      cfg = 13;
-      RowConvArgs& r = a[i];
-      r.A = p.A; r.Wt = p.Wt; r.bias = nullptr; r.out = p.out; r.mask = p.mask;
-      r.B = p.M >> 6; r.H = 8; r.W = 8;
-      r.lda = p.lda; r.ldo = p.ldo; r.Ktot = p.Ktot; r.act = p.act;
-      r.y_lo = p.dy[0] - 1; r.x_lo = p.dx[0] - 1;
-      r.bands = 1; r.band_rows = 8;
-      r.os = 2; r.ooy = p.ooy; r.oox = p.oox;
-      if (i && r.B != a[0].B) return SV_E_UNSUPPORTED;
-      continue;
-    }
-    if (n > 2) return SV_E_UNSUPPORTED;                               // every other form: one problem or the x / x-hat twins
-    static const bool no_pair = getenv("SV_RC_NO_PAIR") != nullptr;   // A/B: the 8 x 8-grid layer d2 on the tile kernel
+    static const bool no_pair = SV_TUNE_FLAG("SV_RC_NO_PAIR");   // A/B: the 8 x 8-grid layer d2 on the tile kernel
     // (measured, 2 x 512 images: forward 0.053 -> 0.048 ms; the input gradient 0.056 -> 0.058 -- but up to 2 x 256 images it is the faster
-    //  form: the step -1.1 % / -0.3 % / -0.6 % at 64 / 128 / 256 images per network (profiles/r04_b64_sweep3.txt).  SV_RC_PAIR_DGRAD=1 / 0 forces it)
-    static const int pair_dgrad_env = getenv("SV_RC_PAIR_DGRAD") ? atoi(getenv("SV_RC_PAIR_DGRAD")) : -1;
-    const bool pair_dgrad = pair_dgrad_env >= 0 ? pair_dgrad_env != 0 : n * (p.M >> (p.lOY + p.lOX)) <= 512;
+    //  form: the step -1.1 % / -0.3 % / -0.6 % at 64 / 128 / 256 images per network (profiles/r04_b64_sweep3.txt))
+    const bool pair_dgrad = n * (p.M >> (p.lOY + p.lOX)) <= 512;
     if (!no_pair && !cls && p.S == 1 && p.SX == 1 && p.OS == 1 && p.lOX == 3 && p.lOY == 3 && p.ntaps == 16 && p.N == 128 && !p.ups && !p.adj && (!p.mask || pair_dgrad)) {
       // d2 forward / input gradient: image pairs per strip, two output-channel halves per problem (RC_d2)
       const int cin = (1 << p.cl2) * 8;
@@ -1218,7 +1199,7 @@ static int row_plan(const TapGemmArgs* t, int n, int dtype, RowConvArgs* a, int*
     //  network used to leave half of the CUs without a workgroup in the three decoder input gradients: serial dgrad.d5 47 -> 26 us, d4 40 -> 32,
     //  step 0.640 -> 0.630 ms; a second workgroup per CU at 128 images per network does not pay for its warm-up steps: +0.3 %.
     //  SV_RC_ADJ_BANDS=0: whole images)
-    static const bool adj_bands = getenv("SV_RC_ADJ_BANDS") == nullptr || atoi(getenv("SV_RC_ADJ_BANDS")) != 0;
+    static const bool adj_bands = SV_TUNE_INT("SV_RC_ADJ_BANDS", 1) != 0;
     int bands = 1;
     while ((!p.adj || adj_bands) && n * r.B * bands < ((four && !p.adj) ? 512 : 256) && OY / (bands * 2) >= (p.adj ? 2 * step : step) && (OY / (bands * 2)) % step == 0) bands *= 2;
     r.bands = bands; r.band_rows = OY / bands; r.lead = p.adj && bands > 1 ? step : 0;
@@ -1227,11 +1208,10 @@ static int row_plan(const TapGemmArgs* t, int n, int dtype, RowConvArgs* a, int*
   // The upsampled forward layers: in the training step at B = 512 the LDS-tile kernel is as fast (fwd.d4 0.140 vs 0.141 ms,
   // fwd.d3 0.077 vs 0.081: their blend staging costs this kernel what the weight streaming costs that one); at small
   // batches this kernel wins clearly (128 images: d3 18 vs 33 us).  SV_RC_FWD=1 / 0 forces it on / off.
-  static const int fwd_mode = getenv("SV_RC_FWD") ? atoi(getenv("SV_RC_FWD")) : -1;
+  static const int fwd_mode = SV_TUNE_INT("SV_RC_FWD", -1);
   // (Round 3, re-measured under the two-side-stream schedule: d4 forward 0.137 ms here against 0.146 on the tile kernel, d3 still equal: d4 always here.)
   // (Round 4: with the resize on the matrix pipe -- RowCfg::MB, whole images per unit -- d3 stays here at every size.)
-  static const bool no_mb3 = getenv("SV_RC_NO_MB") != nullptr || getenv("SV_RC_NO_MB3") != nullptr;
-  const bool d3_mb = cfg == 2 && !no_mb3 && a[0].bands == 1 && a[0].H == 16 && a[0].W == 16 && a[0].lda == 128;
+  const bool d3_mb = cfg == 2 && !rc_no_mb3() && a[0].bands == 1 && a[0].H == 16 && a[0].W == 16 && a[0].lda == 128;
   if ((cfg == 0 && fwd_mode == 0) || (cfg == 2 && (fwd_mode == 0 || (fwd_mode < 0 && n * a[0].B > 512 && !d3_mb)))) return SV_E_UNSUPPORTED;
   return cfg;
 }
@@ -1246,28 +1226,24 @@ int svk_row_conv_try(const TapGemmArgs* t, int n, int dtype, hipStream_t st) {
   const int cfg = row_plan(t, n, dtype, a, &n);
   switch (cfg) {
     case 0: {
-      static const bool no_mb = getenv("SV_RC_NO_MB") != nullptr;       // A/B: the VALU blend staging (stage_rows)
       // two waves per SIMD with the K-half exchange (4-wave workgroups, the default) or ONE wave per SIMD holding the whole K in the 512-register
       // file (2-wave workgroups, no exchange: SV_RC_MB_WAVES=2) -- measured equal alone on the chip (136-138 us at 1024 images), the 4-wave
       // form 7 % faster inside the step (0.119 against 0.128 ms)
-      static const int mbw = getenv("SV_RC_MB_WAVES") ? atoi(getenv("SV_RC_MB_WAVES")) : 4;
-      if (!no_mb && a[0].bands == 1 && a[0].H == 32 && a[0].W == 32 && a[0].lda == 64) return mbw == 2 ? launch_row<RC_d4fw>(a, n, st) : launch_row<RC_d4fm>(a, n, st);
+      static const int mbw = SV_TUNE_INT("SV_RC_MB_WAVES", 4);
+      if (!rc_no_mb() && a[0].bands == 1 && a[0].H == 32 && a[0].W == 32 && a[0].lda == 64) return mbw == 2 ? launch_row<RC_d4fw>(a, n, st) : launch_row<RC_d4fm>(a, n, st);
       return launch_row<RC_d4f>(a, n, st);
     }
     case 1: return launch_row<RC_d4g>(a, n, st);
     case 2: {
-      static const bool no_mb3 = getenv("SV_RC_NO_MB") != nullptr || getenv("SV_RC_NO_MB3") != nullptr;
-      if (!no_mb3 && a[0].bands == 1 && a[0].H == 16 && a[0].W == 16 && a[0].lda == 128) return launch_row<RC_d3fm>(a, n, st);
+      if (!rc_no_mb3() && a[0].bands == 1 && a[0].H == 16 && a[0].W == 16 && a[0].lda == 128) return launch_row<RC_d3fm>(a, n, st);
       return launch_row<RC_d3f>(a, n, st);
     }
     case 3: return launch_row<RC_d3g>(a, n, st);
     case 4: {
-      static const bool no_ma = getenv("SV_RC_NO_MA") != nullptr;       // A/B: the adjoint through the LDS out ring (adjoint_rows)
-      return no_ma ? launch_row<RC_d4ga>(a, n, st) : launch_row<RC_d4gm>(a, n, st);
+      return rc_no_ma() ? launch_row<RC_d4ga>(a, n, st) : launch_row<RC_d4gm>(a, n, st);
     }
     case 5: {
-      static const bool no_ma3 = getenv("SV_RC_NO_MA") != nullptr || getenv("SV_RC_NO_MA3") != nullptr;
-      return no_ma3 ? launch_row<RC_d3ga>(a, n, st) : launch_row<RC_d3gm>(a, n, st);
+      return rc_no_ma3() ? launch_row<RC_d3ga>(a, n, st) : launch_row<RC_d3gm>(a, n, st);
     }
     case 6: return launch_row<RC_d5g>(a, n, st);
     case 7: return launch_row<RC_d5ga>(a, n, st);
@@ -1276,7 +1252,6 @@ int svk_row_conv_try(const TapGemmArgs* t, int n, int dtype, hipStream_t st) {
     case 10: return launch_row<RC_e1f>(a, n, st);
     case 11: return launch_row<RC_d2>(a, n, st);
     case 12: return launch_row<RC_e3f>(a, n, st);
-    case 13: return launch_row<RC_e3g>(a, n, st);
   }
   return SV_E_UNSUPPORTED;
 }

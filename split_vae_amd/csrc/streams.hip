@@ -30,7 +30,7 @@ hipStream_t sv_shared_stream(int k) {
     if (d.s[i]) continue;
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    static const bool normal = getenv("SV_SIDE_PRIO_NORMAL") != nullptr;     // (A/B: the side streams at the default priority)
+    static const bool normal = SV_TUNE_FLAG("SV_SIDE_PRIO_NORMAL");     // (A/B: the side streams at the default priority)
     if (hipStreamCreateWithPriority(&d.s[i], hipStreamNonBlocking, normal ? 0 : lo) != hipSuccess) { d.s[i] = nullptr; return nullptr; }
   }
   return d.s[k];

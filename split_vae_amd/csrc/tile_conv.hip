@@ -520,7 +520,7 @@ bool svk_tile_conv_plan(const TapGemmArgs& t, int dtype, int B, TileConvArgs* a,
   if (!tile_conv_plan_impl(t, dtype, B, a, cfg_out, false, &lds)) return false;
   // fp32: a 128-column tile that leaves ONE workgroup per CU (> 78 KB of LDS: e3's stride-2 forward, 2 x 18 x 18 padded pixels + 32 KB of weight slots) runs on
   // 64-column tiles if those fit twice -- nothing overlaps a lone workgroup's staging and epilogue (fwd.e3 0.201 -> 0.181 ms at 2 x 512 images; SV_TC_NO_LDS_NARROW=1: off)
-  static const bool no_narrow = getenv("SV_TC_NO_LDS_NARROW") != nullptr;
+  static const bool no_narrow = SV_TUNE_FLAG("SV_TC_NO_LDS_NARROW");
   if (!no_narrow && dtype == SV_F32 && t.N % 128 == 0 && !t.cls_n && lds > 78 * 1024) {
     TileConvArgs b;
     int c = 0;
@@ -538,7 +538,7 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
   if (t.d2s_y && (!t.d2s || t.N != 32 || ((2 * t.d2s * 4) & 7))) return false;
   if (t.clampin && (t.ups || t.S != 1)) return false;
   if (t.s2d3 && (dtype != SV_F32 || t.S != 1 || t.SX != 1 || t.ups || t.clampin || t.cl2 != 2)) return false;
-  if (t.fix_nc && !t.d2s_y && ((dtype != SV_F32 && t.S != 2) || !t.fix || !t.fix2 || (t.N & 15) || t.out_f32)) return false;     // (bf16: only the stride-2 polyphase input gradient has instantiations with the border-term epilogue)
+  if (t.fix_nc && !t.d2s_y && (dtype != SV_F32 || !t.fix || !t.fix2 || (t.N & 15) || t.out_f32)) return false;     // (bf16 has no instantiation with the border-term epilogue)
   if (t.nll_part && (!t.d2s_y || t.d2s != 6 || OY * OX < 256 || !t.nll_img || !t.nll_grad)) return false;
   if (t.cls_n && (t.OS != 2 || t.N != 4 * t.cls_n || (t.cls_n & 7) || t.out_f32 || t.bias)) return false;
   if (OY * OX < 16) return false;                       // dense / tiny spatial: im2col path
@@ -553,19 +553,19 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
   int BN, cfgN;
   // small launches (up to 256-image shards): a 128-column layer whose 128-row tiles give at most about one workgroup per CU
   // runs on 64-column tiles instead -- twice the workgroups, half the weight streaming each (SV_TC_SMALL_WGS: the threshold)
-  static const int small_wgs = getenv("SV_TC_SMALL_WGS") ? atoi(getenv("SV_TC_SMALL_WGS")) : 200;   // (per problem) measured: helps at 128 such workgroups per network (B = 256: -1.6 %; 128: -3.6 %, 64: -3.4 %), hurts at 256 (B = 512: +1.8 %)
+  static const int small_wgs = SV_TUNE_INT("SV_TC_SMALL_WGS", 200);   // (per problem) measured: helps at 128 such workgroups per network (B = 256: -1.6 %; 128: -3.6 %, 64: -3.4 %), hurts at 256 (B = 512: +1.8 %)
   const int64_t wgs128 = (((int64_t)B * OY * OX + 127) / 128) * (t.N / 128);
   // (fp32 too since round 5: at 64 images per network d2 / e3 -- 8 x 8 grids, 128 columns -- ran 64 workgroups on 256 CUs, 14 % of the fp32 matrix peak; SV_TC_SMALL_F32=0: off)
-  static const bool small_f32 = !(getenv("SV_TC_SMALL_F32") && atoi(getenv("SV_TC_SMALL_F32")) == 0);
+  static const bool small_f32 = SV_TUNE_INT("SV_TC_SMALL_F32", 1) != 0;
   const bool small = t.N % 128 == 0 && (wgs128 < small_wgs || narrow) && (dtype == SV_BF16 || small_f32) && !t.cls_n;
-  static const int tiny_wgs = getenv("SV_TC_TINY_WGS") ? atoi(getenv("SV_TC_TINY_WGS")) : 100;   // ... and on 32-column tiles below this (64-image shards: -1.3 .. -1.9 %)
+  static const int tiny_wgs = SV_TUNE_INT("SV_TC_TINY_WGS", 100);   // ... and on 32-column tiles below this (64-image shards: -1.3 .. -1.9 %)
   const bool tiny = small && wgs128 < tiny_wgs;
   // (round 6) the same for 64-column stride-1 layers: d3 of a 64-image SVHN-32 shard ran 64-128 workgroups of 128 x 64 on 256 CUs (89 us); 32-column tiles below
   // SV_TC_SMALL64_WGS workgroups per problem (fp32; 0: off).  Measured (profiles/r06_small64.txt): SVHN-32 64 images 1.062-1.074 -> 1.029-1.033 ms, CelebA-64 64 images
   // +-0; the stride-2 64-column layer (e2) LOSES on 32-column tiles (CelebA-64 64 images 1.69 -> 1.71): stride 1 only (SV_TC_SMALL64_S: 0 every stride, 2 stride 2)
-  static const int small64_wgs = getenv("SV_TC_SMALL64_WGS") ? atoi(getenv("SV_TC_SMALL64_WGS")) : 300;
+  static const int small64_wgs = SV_TUNE_INT("SV_TC_SMALL64_WGS", 300);
   const int64_t wgs64 = (((int64_t)B * OY * OX + 127) / 128) * (t.N / 64);
-  static const int small64_s = getenv("SV_TC_SMALL64_S") ? atoi(getenv("SV_TC_SMALL64_S")) : 1;
+  static const int small64_s = SV_TUNE_INT("SV_TC_SMALL64_S", 1);
   // (forward layers only -- OS == 1: the parity-class problems of a stride-2 input gradient are stride-1 problems too, and e3's at 512 images, 256 workgroups
   //  each, went 0.172 -> 0.201 ms on 32-column tiles)
   // (the stride-2 polyphase input gradient of d4 on 32-column tiles: measured, slower -- 64 images 1.679 -> 1.694 ms, 128: 2.732 -> 2.783)
@@ -586,11 +586,11 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
   // occupancy than the 2-way conflict, and at stride 2 no padding can make 2*PS/32 odd.
   // At stride 2 the fragment's pixels are 2*PS apart: +16 B makes 2*PS an odd multiple of 32 (linear
   // 64/128-B pixels are 4/8-way conflicted there).  scripts/lds_bank_model.py has the lane-group model.
-  static const bool s2pad = getenv("SV_TC_NO_S2PAD") == nullptr, p64 = getenv("SV_TC_PAD64") != nullptr;
+  static const bool s2pad = !SV_TUNE_FLAG("SV_TC_NO_S2PAD"), p64 = SV_TUNE_FLAG("SV_TC_PAD64");
   const int pb = cin * esz;
   // Stride-1 tiles of >= 64-B pixels are PLANAR (32-B planes: conflict-free with no padding; SV_TC_NO_PLANAR = the
   // padded linear layout for A/B)
-  static const bool planar_on = getenv("SV_TC_NO_PLANAR") == nullptr;
+  static const bool planar_on = !SV_TUNE_FLAG("SV_TC_NO_PLANAR");
   // layout of a pixel record of `bytes` channel bytes: planar (PS = 32) or linear with conflict-avoiding padding
   auto layout = [&](int bytes, bool* planar_out) {
     const bool pl = planar_on && t.SX == 1 && t.S == 1 && bytes >= 64;
@@ -600,10 +600,10 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
   const int lTW = OX >= 16 ? 4 : t.lOX;
   const int off_bytes = (((t.P + 31) / 32 * 32) * 4 + 15) / 16 * 16;   // padded to the largest K step
   // try MF = 4 (256-row tile) then MF = 2 (128 rows); BN = 128 only with MF = 2, BN = 16/32 only with MF = 4
-  static const char* mf2 = getenv("SV_TC_MF2");       // tuning knob: BN values (as letters a=16,b=32,c=64) forced to 128-row tiles
+  static const char* mf2 = SV_TUNE_STR("SV_TC_MF2", nullptr);       // tuning knob: BN values (as letters a=16,b=32,c=64) forced to 128-row tiles
   for (int MF = 4; MF >= 2; MF -= 2) {
     // 256 x 128 tiles (SV_TC_BN128_MF4=1): half the weight streaming per output of the small-grid 128-column layers
-    static const bool big128 = getenv("SV_TC_BN128_MF4") != nullptr;
+    static const bool big128 = SV_TUNE_FLAG("SV_TC_BN128_MF4");
     if (MF == 4 && BN == 128 && !(big128 && dtype == SV_BF16)) continue;
     if (MF == 4 && mf2 && strchr(mf2, BN == 16 ? 'a' : BN == 32 ? 'b' : 'c')) continue;
     if (MF == 4 && small) continue;                       // (128-row tiles: the point is more workgroups)
@@ -623,25 +623,24 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
     int yr = 0;
     // off for the 16-column kernel (BN letter a): the packed d5's un-phased 62 KB tile leaves two workgroups per CU
     // instead of three, which costs what the window saves (0.200 vs 0.191 ms in the step)
-    static const char* yr_off = getenv("SV_TC_NO_YR") ? getenv("SV_TC_NO_YR") : "a";   // "1" = off everywhere, or BN letters (a=16, b=32, c=64)
+    static const char* yr_off = SV_TUNE_STR("SV_TC_NO_YR", "a");   // "1" = off everywhere, or BN letters (a=16, b=32, c=64)
     if (dtype == SV_BF16 && MF == 4 && t.S == 1 && lTW == 4 && TH >= MF && cin >= 32 && BN <= 64 &&
         !(yr_off && (yr_off[0] == '1' || strchr(yr_off, BN == 16 ? 'a' : BN == 32 ? 'b' : 'c')))) {
       int kh = 1;
       while (kh < t.ntaps && t.dx[kh] == t.dx[0]) ++kh;
-      static const bool yr5 = getenv("SV_TC_YR5") != nullptr;         // A/B (off: measured 0.155 vs 0.141 ms for the polyphase head -- a step is one
-                                                                       // whole 5-tap column, 20 pieces: 128 VGPRs, 7 spilled, bigger weight slots)
-      bool ok = (kh == 4 || kh == 6 || (kh == 5 && yr5 && BN == 32)) && t.ntaps % kh == 0;
+      // (5-tap columns, the polyphase head: measured and removed -- 0.155 vs 0.141 ms, a step is one whole column, 20 pieces: 128 VGPRs, 7 spilled, bigger weight slots)
+      bool ok = (kh == 4 || kh == 6) && t.ntaps % kh == 0;
       for (int i = 0; i < t.ntaps && ok; ++i)
         ok = t.dx[i] == t.dx[i / kh * kh] && t.dy[i] == t.dy[0] + i % kh && t.dy[0] == y_lo;
       if (ok) yr = kh;
     }
-    static const int nph_max = getenv("SV_TC_NPH") ? atoi(getenv("SV_TC_NPH")) : 4;     // tuning knob (1 = off)
+    static const int nph_max = SV_TUNE_INT("SV_TC_NPH", 4);     // tuning knob (1 = off)
     const int64_t wgs = (int64_t)(OX / TW) * (OY / TH) * ((B + NB - 1) / NB) * ((t.N + BN - 1) / BN);
     // (round 6) fp32 32-column layers of small launches: 256-row tiles left 64-128 workgroups per problem on 256 CUs (SVHN-32, 64 images: e1 / the d4 class
     // problems); 128-row tiles below SV_TC_SMALL32_WGS workgroups per problem.  SVHN-32 64 images 1.029-1.038 -> 0.980 ms, 256 images 1.79 -> 1.78; CelebA-64 64 images
     // 1.689 -> 1.680, 128 images +-0 (forcing 128-row tiles on EVERY 32-column layer, SV_TC_MF2=b, costs CelebA-64 64 images 1 %).  Not the fused-loss head (one
     // partial per 256-pixel tile).  profiles/r06_small64.txt
-    static const int small32_wgs = getenv("SV_TC_SMALL32_WGS") ? atoi(getenv("SV_TC_SMALL32_WGS")) : 300;
+    static const int small32_wgs = SV_TUNE_INT("SV_TC_SMALL32_WGS", 300);
     if (MF == 4 && BN == 32 && dtype == SV_F32 && !t.nll_part && wgs < small32_wgs) continue;
     int lnph = 0, PS = 0, plane_bytes = 0;
     int64_t in_bytes = 0;
@@ -652,9 +651,9 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
       PS = layout(pbh, &planar);
       plane_bytes = planar ? NB * TIH * TIW * 32 : 0;
       in_bytes = planar ? (int64_t)plane_bytes * (pbh / 32) : (int64_t)NB * TIH * TIW * PS;
-      static const int ph_kb = getenv("SV_TC_PH_KB") ? atoi(getenv("SV_TC_PH_KB")) : 53;   // LDS per workgroup the split aims below (3 workgroups per CU)
-      static const bool s2_phases = getenv("SV_TC_NPH_NO_S2") == nullptr;               // A/B: phases for the padded stride-2 layouts too
-      static const int ph_wgs = getenv("SV_TC_PH_WGS") ? atoi(getenv("SV_TC_PH_WGS")) : 256;   // launches smaller than this keep one pass
+      static const int ph_kb = SV_TUNE_INT("SV_TC_PH_KB", 53);   // LDS per workgroup the split aims below (3 workgroups per CU)
+      static const bool s2_phases = !SV_TUNE_FLAG("SV_TC_NPH_NO_S2");               // A/B: phases for the padded stride-2 layouts too
+      static const int ph_wgs = SV_TUNE_INT("SV_TC_PH_WGS", 256);   // launches smaller than this keep one pass
       // (a tile that does not fit the CU at all is split whatever the launch size: e3's stride-2 forward at fp32 -- 2 x 18 x 18 pixels of 528 B -- fell to the
       //  im2col kernel below 256 workgroups: 0.102 ms for 64 images per network against 0.198 ms for 512)
       const int64_t tot = in_bytes + 2 * BN * tile_pps(BN) * 16 + off_bytes;
@@ -662,7 +661,7 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
                             ((wgs >= ph_wgs && tot > ph_kb * 1024) || tot > 150 * 1024))) break;
     }
     // whole K resident in LDS (kernel comment): one phase, <= 6 K steps, <= 24 KB of weights
-    static const bool wres_on = getenv("SV_TC_NO_WRES") == nullptr;
+    static const bool wres_on = !SV_TUNE_FLAG("SV_TC_NO_WRES");
     const int nks = (int)(((t.P >> lnph) + tile_pps(BN) - 1) / tile_pps(BN));
     // (measured: d5's input gradient -5 %; e1's stride-2 forward +10 %, so stride 1 only)
     const int wslots = (wres_on && !yr && dtype == SV_BF16 && BN == 32 && MF == 4 && t.S == 1 && lnph == 0 && nks > 2 && nks <= 6 && nks * BN * tile_pps(BN) * 16 <= 24 * 1024) ? nks : 2;
@@ -670,12 +669,12 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
     if (lds > 78 * 1024 && MF == 4 && BN >= 64) continue;   // prefer 2 workgroups per CU: retry with 128 rows
     // (the stride-2 9 x 9-tap polyphase input gradient, conv_geom.h svg_polyd: its 39 x 39-pixel hi-res tile leaves ONE workgroup per CU -- no overlap
     //  of one tile's staging with another's MFMAs; SV_TC_S2_MF4=1: the 256-row tile for A/B)
-    static const bool s2_mf4 = getenv("SV_TC_S2_MF4") != nullptr;
+    static const bool s2_mf4 = SV_TUNE_FLAG("SV_TC_S2_MF4");
     if (lds > 78 * 1024 && MF == 4 && t.S == 2 && t.fix_nc && !s2_mf4) continue;
     *lds_out = lds;
     if (lds > 150 * 1024) {
       if (MF == 4) continue;
-      if (getenv("SV_TC_VERBOSE")) fprintf(stderr, "tile_conv plan: REFUSED (LDS %lld) N=%d cin=%d S=%d ntaps=%d\n", (long long)lds, t.N, cin, t.S, t.ntaps);
+      if (SV_TUNE_FLAG("SV_TC_VERBOSE")) fprintf(stderr, "tile_conv plan: REFUSED (LDS %lld) N=%d cin=%d S=%d ntaps=%d\n", (long long)lds, t.N, cin, t.S, t.ntaps);
       return false;
     }
     memset(a, 0, sizeof(*a));
@@ -692,12 +691,12 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
     a->nph = 1 << lnph; a->lnph = lnph; a->wslots = wslots;
     {
       // (fp32: the register staging keeps four loads per lane in flight and waits -- three to four dependent L2 round trips per tile; SV_TC_NO_DMA: A/B)
-      static const bool no_dma = getenv("SV_TC_NO_DMA") != nullptr;
+      static const bool no_dma = SV_TUNE_FLAG("SV_TC_NO_DMA");
       a->dma = (!no_dma && dtype == SV_F32 && !t.ups && !t.s2d3 && (planar || PS == (pb >> lnph))) ? 1 : 0;
     }
-    if (getenv("SV_TC_VERBOSE")) fprintf(stderr, "tile_conv plan: yr=%d wslots=%d N=%d BN=%d MF=%d cin=%d pb=%d planar=%d nph=%d tile=%dx%dx%d PS=%d in_bytes=%lld lds=%lld ntiles=%d S=%d SX=%d\n", yr, wslots, t.N, BN, MF, cin, pb, (int)planar, 1 << lnph, NB, TIH, TIW, PS, (long long)in_bytes, (long long)lds, a->ntiles, t.S, t.SX);
+    if (SV_TUNE_FLAG("SV_TC_VERBOSE")) fprintf(stderr, "tile_conv plan: yr=%d wslots=%d N=%d BN=%d MF=%d cin=%d pb=%d planar=%d nph=%d tile=%dx%dx%d PS=%d in_bytes=%lld lds=%lld ntiles=%d S=%d SX=%d\n", yr, wslots, t.N, BN, MF, cin, pb, (int)planar, 1 << lnph, NB, TIH, TIW, PS, (long long)in_bytes, (long long)lds, a->ntiles, t.S, t.SX);
     {
-      static const bool xcd = getenv("SV_TC_NO_XCD") == nullptr;
+      static const bool xcd = !SV_TUNE_FLAG("SV_TC_NO_XCD");
       a->xcd_chunk = (xcd && a->ntiles >= 64 && (a->ntiles & 7) == 0) ? a->ntiles / 8 : 0;
     }
     a->off_bytes = off_bytes; a->in_bytes = (int)in_bytes;
@@ -705,9 +704,9 @@ static bool tile_conv_plan_impl(const TapGemmArgs& t, int dtype, int B, TileConv
     a->act = t.act; a->out_f32 = t.out_f32; a->ntaps = t.ntaps; a->ups = t.ups;
     memcpy(a->dy, t.dy, sizeof(a->dy));
     memcpy(a->dx, t.dx, sizeof(a->dx));
-    *cfg_out = cfgN * 2 + (MF == 4 ? 0 : 1) + (yr == 4 ? 32 : yr == 6 ? 64 : yr == 5 ? 96 : 0) + (wslots > 2 ? 128 : 0);
+    *cfg_out = cfgN * 2 + (MF == 4 ? 0 : 1) + (yr == 4 ? 32 : yr == 6 ? 64 : 0) + (wslots > 2 ? 128 : 0);
     // 256-row tiles that leave room for at most two workgroups per CU: 8 waves share the tile
-    static const char* nw8 = getenv("SV_TC_NW8");       // tuning knob: BN classes (a=16, b=32, c=64) run with 8-wave workgroups
+    static const char* nw8 = SV_TUNE_STR("SV_TC_NW8", nullptr);       // tuning knob: BN classes (a=16, b=32, c=64) run with 8-wave workgroups
     if (MF == 4 && dtype == SV_BF16 && nw8 && strchr(nw8, BN == 16 ? 'a' : BN == 32 ? 'b' : BN == 64 ? 'c' : 'd')) *cfg_out = 16 + cfgN;
     return true;
   }
@@ -721,15 +720,6 @@ int svk_tile_conv_multi(const TileConvArgs* a, int n, int dtype, int cfg, hipStr
   // wait also waited for that step's HBM slice loads, and the second buffer halved the resident
   // workgroups.  Overlap needs producer waves with their own load queue, not in-loop slices.)
   if (n < 1 || n > SV_MAX_MULTI) return SV_E_BADARG;
-  if (dtype == SV_BF16 && a[0].fix_nc) {              // the polyphase input gradient at bf16 (SV_POLYD_BF16=1): the border-term epilogue compiled in
-    switch (cfg) {
-      case 2: return launch_tile<bf16_t, 64, 4, 4, 0, false, true>(a, n, st);
-      case 3: return launch_tile<bf16_t, 64, 2, 4, 0, false, true>(a, n, st);
-      case 4: return launch_tile<bf16_t, 32, 4, 4, 0, false, true>(a, n, st);
-      case 5: return launch_tile<bf16_t, 32, 2, 4, 0, false, true>(a, n, st);
-    }
-    return SV_E_UNSUPPORTED;
-  }
   if (dtype == SV_BF16) {
     switch (cfg) {
       case 0: return launch_tile<bf16_t, 128, 4>(a, n, st);
@@ -744,7 +734,6 @@ int svk_tile_conv_multi(const TileConvArgs* a, int n, int dtype, int cfg, hipStr
       case 32 + 2: return launch_tile<bf16_t, 64, 4, 4, 4>(a, n, st);     // row-window reuse, KH = 4
       case 32 + 4: return launch_tile<bf16_t, 32, 4, 4, 4>(a, n, st);
       case 32 + 6: return launch_tile<bf16_t, 16, 4, 4, 4>(a, n, st);
-      case 96 + 4: return launch_tile<bf16_t, 32, 4, 4, 5>(a, n, st);     // KH = 5 (polyphase head)
       case 64 + 2: return launch_tile<bf16_t, 64, 4, 4, 6>(a, n, st);     // KH = 6
       case 64 + 4: return launch_tile<bf16_t, 32, 4, 4, 6>(a, n, st);
       case 64 + 6: return launch_tile<bf16_t, 16, 4, 4, 6>(a, n, st);
@@ -775,9 +764,8 @@ static const char* tile_form(const TapGemmArgs& t) { return t.s2d3 ? "tile_s2d3"
 // n tap-GEMM problems of the same shape: one multi launch of the tile kernel when they all plan
 // to the same configuration, individual launches otherwise
 int svk_conv_dispatch_multi(const TapGemmArgs* t, int n, int dtype, int tap_cfg, hipStream_t st) {
-  static const bool force_tap = getenv("SV_FORCE_IM2COL") != nullptr;   // A/B switch for tests and profiling
-  static const bool no_multi = getenv("SV_NO_MULTI") != nullptr;        // A/B: one launch per problem
-  static const int dbg = SV_DBG(getenv("SV_TC_DBG") ? atoi(getenv("SV_TC_DBG")) : 0);
+  const bool force_tap = sv_tune_force_im2col(), no_multi = sv_tune_no_multi();
+  static const int dbg = SV_TUNE_INT("SV_TC_DBG", 0);
   if (n < 1 || n > SV_MAX_MULTI) return SV_E_BADARG;
   if (!force_tap && n <= 8) {                          // weights in registers, rows rolling through LDS (row_conv.hip takes one problem, the x / x-hat
                                                        // twins, or the up to eight class problems of a stride-2 layer's input gradient)

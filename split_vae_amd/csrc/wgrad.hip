@@ -217,7 +217,7 @@ static int launch_wgrad(const WgradArgs* a, int n, hipStream_t st) {
   constexpr int SA = BR * (int)sizeof(T) + (sizeof(T) == 2 ? 32 : 16);
   constexpr int SB = BNW * (int)sizeof(T) + (sizeof(T) == 2 && BNW >= 32 ? 32 : 16);
   const size_t lds = 2 * MS * SA + 2 * MS * SB + SV_MAX_TAPS * 3 * sizeof(int);
-  static const bool no_plain = getenv("SV_WGRAD_NO_PLAIN") != nullptr;   // A/B knob: always atomics
+  static const bool no_plain = SV_TUNE_FLAG("SV_WGRAD_NO_PLAIN");   // A/B knob: always atomics
   WgradMulti m;
   m.n = n;
   int gx = 0, gy = 0, gz = 0;

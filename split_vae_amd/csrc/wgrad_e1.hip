@@ -201,7 +201,7 @@ int e1_wgs(int n, int ntasks) {               // workgroups per problem: 8 waves
 }  // namespace
 
 bool svk_wgrad_e1_supported(const WgradArgs* wv, int n) {
-  static const bool off = getenv("SV_NO_WGRAD_E1") != nullptr;
+  const bool off = sv_knob_no_wgrad_e1();
   if (off || n < 1 || n > SV_WGRAD_MAX_MULTI) return false;
   const WgradArgs& w = wv[0];
   if (w.ups || w.S != 2 || w.SX != 2 || w.ntaps != 36 || w.Cin_pad != 8 || w.lda != 8 || w.ldy != 32 || w.ycols != 32 || w.N != 32) return false;
@@ -210,7 +210,7 @@ bool svk_wgrad_e1_supported(const WgradArgs* wv, int n) {
   for (int t = 0; t < 36; ++t)
     if (w.dy[t] != t / 6 - 2 || w.dx[t] != t % 6 - 2) return false;
   const int B = w.M / (OH * OW);
-  static const int min_tasks = getenv("SV_WGRAD_E1_MIN") ? atoi(getenv("SV_WGRAD_E1_MIN")) : 512;
+  static const int min_tasks = SV_TUNE_INT("SV_WGRAD_E1_MIN", 512);
   if (n * 2 * B < min_tasks) return false;     // small launches: too few strips for the waves of the chip (the tile kernel cuts 2-D tiles)
   const int X = e1_wgs(n, 2 * B);
   const int64_t need = (int64_t)X * 4 * 10 * 256 * 4 + (int64_t)X * 128 * 4;
@@ -240,9 +240,5 @@ int svk_wgrad_e1_multi(const WgradArgs* wv, int n, hipStream_t st) {
   hipLaunchKernelGGL(wgrad_e1_kernel, dim3(X, 1, n), dim3(512), lds, st, m);
   SV_LAUNCH_CHECK();
   if (w.ev_mid[0]) { (void)hipEventRecord(w.ev_mid[0], st); (void)hipEventRecord(w.ev_mid[1], st); }
-  if (w.defer && w.n_defer && *w.n_defer + n <= 64) {
-    for (int i = 0; i < n; ++i) w.defer[(*w.n_defer)++] = rd[i];
-    return SV_OK;
-  }
   return svk_wgrad_reduce_all(rd, n, st);
 }

@@ -191,7 +191,7 @@ int e2_wgs(int n, int B) {
 }  // namespace
 
 bool svk_wgrad_e2_supported(const WgradArgs* wv, int n) {
-  static const bool off = getenv("SV_NO_WGRAD_E2") != nullptr;
+  const bool off = sv_knob_no_wgrad_e2();
   if (off || n < 1 || n > SV_WGRAD_MAX_MULTI) return false;
   const WgradArgs& w = wv[0];
   if (w.ups || w.S != 2 || w.SX != 2 || w.ntaps != 36 || w.Cin_pad != CI || w.Cin_real != CI || w.lda != CI || w.ldy != CO || w.ycols != CO || w.N != CO) return false;
@@ -200,7 +200,7 @@ bool svk_wgrad_e2_supported(const WgradArgs* wv, int n) {
   for (int t = 0; t < 36; ++t)
     if (w.dy[t] != t / 6 - 2 || w.dx[t] != t % 6 - 2) return false;
   const int B = w.M / (OH * OW);
-  static const int min_images = getenv("SV_WGRAD_E2_MIN") ? atoi(getenv("SV_WGRAD_E2_MIN")) : 512;
+  const int min_images = sv_knob_wgrad_e2_min();
   if (n * B < min_images) return false;        // small launches: a workgroup per image leaves the chip idle and still writes a full slab each
   const int X = e2_wgs(n, B);
   const int64_t need = (int64_t)X * 4 * 72 * 256 * 4 + (int64_t)X * 128 * 4;
@@ -228,9 +228,5 @@ int svk_wgrad_e2_multi(const WgradArgs* wv, int n, hipStream_t st) {
   hipLaunchKernelGGL(wgrad_e2_kernel, dim3(X, 1, n), dim3(512), LDS_BYTES, st, m);
   SV_LAUNCH_CHECK();
   if (w.ev_mid[0]) { (void)hipEventRecord(w.ev_mid[0], st); (void)hipEventRecord(w.ev_mid[1], st); }
-  if (w.defer && w.n_defer && *w.n_defer + n <= 64) {
-    for (int i = 0; i < n; ++i) w.defer[(*w.n_defer)++] = rd[i];
-    return SV_OK;
-  }
   return svk_wgrad_reduce_all(rd, n, st);
 }

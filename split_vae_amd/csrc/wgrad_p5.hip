@@ -223,8 +223,8 @@ static int p5_wgs(int n, int nstrips, int* per) {
 }
 
 bool svk_wgrad_p5_supported(const WgradArgs* wv, int n) {
-  static const bool off = getenv("SV_NO_WGRAD_P5") != nullptr;
-  static const int min_images = getenv("SV_WGRAD_P5_MIN") ? atoi(getenv("SV_WGRAD_P5_MIN")) : 128;
+  static const bool off = SV_TUNE_FLAG("SV_NO_WGRAD_P5");
+  static const int min_images = SV_TUNE_INT("SV_WGRAD_P5_MIN", 128);
   if (off || n < 1 || n > SV_WGRAD_MAX_MULTI) return false;
   const WgradArgs& w = wv[0];
   if (!w.dy_s2d || !w.clampin || !w.assign || w.ups || w.fold_kw || w.S != 1 || w.SX != 1 || w.ntaps != NTAP) return false;
@@ -263,9 +263,5 @@ int svk_wgrad_p5_multi(const WgradArgs* wv, int n, hipStream_t st) {
   hipLaunchKernelGGL(wgrad_p5_kernel, dim3(X, 1, n), dim3(512), P5_LDS, st, m);
   SV_LAUNCH_CHECK();
   if (w.ev_mid[0]) { (void)hipEventRecord(w.ev_mid[0], st); (void)hipEventRecord(w.ev_mid[1], st); }
-  if (w.defer && w.n_defer && *w.n_defer + n <= 64) {
-    for (int i = 0; i < n; ++i) w.defer[(*w.n_defer)++] = rd[i];
-    return SV_OK;
-  }
   return svk_wgrad_reduce_all(rd, n, st);
 }

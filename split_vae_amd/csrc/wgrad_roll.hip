@@ -397,25 +397,19 @@ __global__ __launch_bounds__(512, 1) void wgrad_roll_kernel(const RollMulti mg) 
 
 }  // namespace
 
-// workgroups per problem: one per CU over the launch, and at least `SV_ROLL_MIN_STRIPS` strips each (every workgroup flushes a 295-KB slab
-// whatever it computed: at 64 images per network 128 one-strip workgroups wrote and re-read 75 MB for 19 steps of work each)
+// workgroups per problem: one per CU over the launch (every workgroup flushes a 295-KB slab whatever it computed: at 64 images per network 128 one-strip
+// workgroups wrote and re-read 75 MB for 19 steps of work each)
 // (round 4: with two strips or fewer per workgroup, half as many workgroups -- 64 images per network: two strips each, step 0.607 -> 0.600 ms; 128: four
-//  each, 0.766 -> 0.754; SV_ROLL_MIN_STRIPS forces a minimum instead: profiles/r04_b64_sweep4.txt)
+//  each, 0.766 -> 0.754; a forced minimum of strips per workgroup instead had no effect: profiles/r04_b64_sweep4.txt)
 static int roll_wgs(int n, int nstrips) {
-  static const int min_strips = getenv("SV_ROLL_MIN_STRIPS") ? atoi(getenv("SV_ROLL_MIN_STRIPS")) : 0;
   int X = 256 / n;
-  if (min_strips > 0) {
-    const int cap = (nstrips + min_strips - 1) / min_strips;
-    if (X > cap) X = cap;
-  } else {
-    if (nstrips <= 2 * X) X /= 2;
-    if (X > nstrips) X = nstrips;
-  }
+  if (nstrips <= 2 * X) X /= 2;
+  if (X > nstrips) X = nstrips;
   return X < 1 ? 1 : X;
 }
 
 bool svk_wgrad_roll_supported(const WgradArgs* wv, int n) {
-  static const bool off = getenv("SV_NO_WGRAD_ROLL") != nullptr;
+  const bool off = sv_knob_no_wgrad_roll();
   if (off || n < 1 || n > SV_WGRAD_MAX_MULTI) return false;
   const WgradArgs& w = wv[0];
   if (!w.ups || w.S != 1 || w.SX != 1 || w.ntaps != NT || w.Cin_pad != 64 || w.Cin_real != 64 || w.ldy != 32 || w.ycols != 32 || w.N != 32) return false;
@@ -451,9 +445,5 @@ int svk_wgrad_roll_multi(const WgradArgs* wv, int n, hipStream_t st) {
   hipLaunchKernelGGL(wgrad_roll_kernel, dim3(X, 1, n), dim3(512), 0, st, m);
   SV_LAUNCH_CHECK();
   if (w.ev_mid[0]) { (void)hipEventRecord(w.ev_mid[0], st); (void)hipEventRecord(w.ev_mid[1], st); }
-  if (w.defer && w.n_defer && *w.n_defer + n <= 64) {
-    for (int i = 0; i < n; ++i) w.defer[(*w.n_defer)++] = rd[i];
-    return SV_OK;
-  }
   return svk_wgrad_reduce_all(rd, n, st);
 }

@@ -690,21 +690,21 @@ static int launch_wt_ng(const WgradTileArgs* a, int n, int groups, hipStream_t s
   int per_cu = (int)((160 * 1024) / lds);
   if (per_cu > OCC / NG) per_cu = OCC / NG;
   if (per_cu < 1) per_cu = 1;
-  static const int force_pc = getenv("SV_WT_PERCU") ? atoi(getenv("SV_WT_PERCU")) : 0;   // profiling knob
+  static const int force_pc = SV_TUNE_INT("SV_WT_PERCU", 0);   // profiling knob
   if (force_pc > 0 && force_pc < per_cu) per_cu = force_pc;
   // ablation bits: 1 skip the flush (+reduce), 2 skip input staging, 4 skip dY staging, 8 skip the MFMA loop
-  static const int dbg = SV_DBG(getenv("SV_WT_DBG") ? atoi(getenv("SV_WT_DBG")) : (getenv("SV_WT_NOFLUSH") ? 1 : 0));
+  static const int dbg = SV_TUNE_INT("SV_WT_DBG", SV_TUNE_FLAG("SV_WT_NOFLUSH") ? 1 : 0);
   // ONE resident round of workgroups over the whole launch (all n problems): every workgroup flushes one slab, so
   // a second round doubles the slab writes and the reduce's reads for no extra parallelism (SV_WT_ROUNDS=2: the old
   // one round PER PROBLEM, for A/B)
-  static const int rounds = getenv("SV_WT_ROUNDS") ? atoi(getenv("SV_WT_ROUNDS")) : 1;
+  static const int rounds = SV_TUNE_INT("SV_WT_ROUNDS", 1);
   const int share = rounds >= 2 ? 1 : n;
   int msplit = (256 * per_cu + groups * share - 1) / (groups * share);
   if (msplit < 1) msplit = 1;
   if (msplit > a[0].ntiles) msplit = a[0].ntiles;
   // small batches: a workgroup should own several tiles before it pays for a slab flush (the slab is as large for one tile as
   // for forty: at 64 images per network d2's 512 one-tile workgroups wrote and re-read 67 MB of partial sums)
-  static const int min_tiles = getenv("SV_WT_MIN_TILES") ? atoi(getenv("SV_WT_MIN_TILES")) : 4;   // B = 64: 0.768 -> 0.746 ms; 8: worse (too few workgroups)
+  static const int min_tiles = SV_TUNE_INT("SV_WT_MIN_TILES", 4);   // B = 64: 0.768 -> 0.746 ms; 8: worse (too few workgroups)
   if (min_tiles > 1) {
     int cand = (a[0].ntiles + min_tiles - 1) / min_tiles;
     const int floor_wgs = (256 + groups * n - 1) / (groups * n);     // ... but never fewer than one workgroup per CU in the launch
@@ -714,7 +714,7 @@ static int launch_wt_ng(const WgradTileArgs* a, int n, int groups, hipStream_t s
   dim3 grid(msplit, groups, n), block(256 * NG);
   constexpr int PER = 4 * TPW * CIF * COF * 256;
   const int64_t need = (int64_t)msplit * groups * PER * 4 + (int64_t)msplit * 128 * 4;      // + one (<= 128-column) bias partial per workgroup row
-  static const bool no_slab = getenv("SV_WT_ATOMICS") != nullptr;
+  static const bool no_slab = SV_TUNE_FLAG("SV_WT_ATOMICS");
   WgradTileMulti m;
   WgradReduceMulti r;
   bool slab = !no_slab;
@@ -729,8 +729,8 @@ static int launch_wt_ng(const WgradTileArgs* a, int n, int groups, hipStream_t s
   bool piped = false;
   if constexpr (NG == 2 && KC % 2 == 0) {
     // whole-image tiles, plain staging, slabs: the pipelined form (ring of 2..4 tile buffers filled by LDS-DMA)
-    static const bool no_pipe = getenv("SV_WT_NO_PIPE") != nullptr;
-    static const int force_nbuf = getenv("SV_WT_PIPE_NBUF") ? atoi(getenv("SV_WT_PIPE_NBUF")) : 0;
+    const bool no_pipe = sv_knob_wt_no_pipe();
+    static const int force_nbuf = SV_TUNE_INT("SV_WT_PIPE_NBUF", 0);
     const WgradTileArgs& q = a[0];
     const size_t stage = (size_t)q.in_bytes + q.dy_bytes;
     int nbuf = (int)((160 * 1024) / stage);
@@ -749,12 +749,6 @@ static int launch_wt_ng(const WgradTileArgs* a, int n, int groups, hipStream_t s
   if (!piped) hipLaunchKernelGGL((wgrad_tile_kernel<TPW, CIF, COF, KC, NG, OCC>), grid, block, lds, st, m);
   SV_LAUNCH_CHECK();
   if (ev_mid && ev_mid[0]) { (void)hipEventRecord(ev_mid[0], st); (void)hipEventRecord(ev_mid[1], st); }
-  if (slab && !(dbg & 1) && a[0].defer && a[0].n_defer && *a[0].n_defer + n <= 64) {      // the caller reduces every layer's slabs in one launch later
-    for (int i = 0; i < n; ++i)
-      a[0].defer[(*a[0].n_defer)++] = WgradReduceDesc{m.a[i].slab, a[i].dW, m.a[i].bslab, a[i].dbias, msplit, groups, a[0].ncg, a[0].CW, a[0].Cin_real,
-                                                      a[0].N, a[0].ntaps, a[0].fold_kw, a[0].fold_c, a[0].pairx, a[0].assign, TPW, CIF, COF};
-    return SV_OK;
-  }
   if (slab && !(dbg & 1)) {
     hipLaunchKernelGGL((wgrad_reduce_kernel<TPW, CIF, COF>), dim3(PER / 128, groups, n), dim3(256), 0, st, r, msplit, groups,
                        a[0].ncg, a[0].CW, a[0].Cin_real, a[0].N, a[0].ntaps, a[0].fold_kw, a[0].fold_c, a[0].pairx, a[0].assign);
@@ -765,13 +759,13 @@ static int launch_wt_ng(const WgradTileArgs* a, int n, int groups, hipStream_t s
 
 template <int TPW, int CIF, int COF, int KC>
 static int launch_wt(const WgradTileArgs* a, int n, int groups, hipStream_t st, const hipEvent_t* ev_mid) {
-  static const bool ng1 = getenv("SV_WT_NG1") != nullptr;      // A/B knob: 4-wave workgroups, two per CU
+  static const bool ng1 = SV_TUNE_FLAG("SV_WT_NG1");      // A/B knob: 4-wave workgroups, two per CU
   constexpr size_t HFB = ((TPW * CIF * COF + 1) / 2) * 4 * 1024;
   const size_t two = 2 * ((size_t)a[0].in_bytes + a[0].dy_bytes);
   const bool slab = a[0].ws != nullptr;                         // halving the slabs is the point; atomics keep NG = 1
   // measured per layer (B = 512): e2 -13 %, d2 -8 %, e1 -4 %, d3 0; d4 / d5 (the longest MFMA sections) lose
   // 5-12 % to the lockstep of the two groups, so the wide-tile layers keep two independent workgroups per CU
-  static const char* ng2 = getenv("SV_WT_NG2") ? getenv("SV_WT_NG2") : "3456";     // layer ids (see the table above)
+  static const char* ng2 = SV_TUNE_STR("SV_WT_NG2", "3456");     // layer ids (see the table above)
   const bool want = strchr(ng2, '0' + a[0].layer_id) != nullptr || (a[0].layer_id == 2 && !a[0].ups);    // d3 on its written-out resized input: the pipelined form
   if (!ng1 && want && slab && two <= 160 * 1024 && HFB <= 160 * 1024 && a[0].ntiles >= 64)
     return launch_wt_ng<TPW, CIF, COF, KC, 2>(a, n, groups, st, ev_mid);
@@ -783,8 +777,8 @@ static int launch_wt(const WgradTileArgs* a, int n, int groups, hipStream_t st, 
 int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
   if (n < 1 || n > SV_WGRAD_MAX_MULTI) return SV_E_BADARG;
   const WgradArgs& w = wv[0];                       // the n problems share one geometry, pointers differ
-  static const bool force_old = getenv("SV_FORCE_IM2COL") != nullptr;
-  static const char* skip = getenv("SV_WGRAD_IM2COL_IDS");    // e.g. "23": these layer ids use the im2col kernel (A/B)
+  const bool force_old = sv_tune_force_im2col();
+  static const char* skip = SV_TUNE_STR("SV_WGRAD_IM2COL_IDS", nullptr);    // e.g. "23": these layer ids use the im2col kernel (A/B)
   if (force_old || w.lOY < 0 || w.lOX < 0 || w.S > 2) return SV_E_UNSUPPORTED;   // power-of-two grids, stride <= 2
   if (svk_wgrad_roll_supported(wv, n)) { sv_trace_note("wgrad_roll"); return svk_wgrad_roll_multi(wv, n, st); }
   if (svk_wgrad_p5_supported(wv, n)) { sv_trace_note("wgrad_p5"); return svk_wgrad_p5_multi(wv, n, st); }
@@ -809,9 +803,9 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
   // 16-channel slices for d4 / d3 / packed d5: half the accumulators per wave, so three workgroups (3 waves per
   // SIMD) fit per CU instead of two; e1 fits four.  Measured together: 185.5k -> 188.7k images/s (SV_WT_CW16= /
   // SV_WT_HIOCC= with an empty list restore the wide variants).
-  static const char* cw16 = getenv("SV_WT_CW16") ? getenv("SV_WT_CW16") : "17";   // (round 2: d3 (id 2) back on 32-channel slices, step -1.3 %)
+  static const char* cw16 = SV_TUNE_STR("SV_WT_CW16", "17");   // (round 2: d3 (id 2) back on 32-channel slices, step -1.3 %)
   const bool narrow = strchr(cw16, '0' + id) && (id == 1 || id == 2 || id == 7);
-  static const char* hiocc = getenv("SV_WT_HIOCC") ? getenv("SV_WT_HIOCC") : "6";
+  static const char* hiocc = SV_TUNE_STR("SV_WT_HIOCC", "6");
   const bool hi = strchr(hiocc, '0' + id) != nullptr;
   if (narrow) CW = 16;
   // (e3 stayed on the im2col GEMM in round 1 -- "no faster here"; with one resident round of workgroups per launch and the
@@ -841,8 +835,8 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
   a.clampin = w.clampin; a.dy_s2d = w.dy_s2d; a.assign = w.assign;
   // tile walk of a workgroup: a contiguous run (neighbours share halos in one XCD's L2) or strided by the grid.  Re-measured per
   // layer (round 2): strided wins for the layers listed in SV_WT_STRIDED_IDS (SV_WT_STRIDED=1: every layer)
-  static const bool all_strided = getenv("SV_WT_STRIDED") != nullptr;
-  static const char* strided_ids = getenv("SV_WT_STRIDED_IDS") ? getenv("SV_WT_STRIDED_IDS") : "567";   // d5 (x-packed), e2, e1: -0.6 % of the step (almost all of it d5)
+  static const bool all_strided = SV_TUNE_FLAG("SV_WT_STRIDED");
+  static const char* strided_ids = SV_TUNE_STR("SV_WT_STRIDED_IDS", "567");   // d5 (x-packed), e2, e1: -0.6 % of the step (almost all of it d5)
   a.contig = (all_strided || strchr(strided_ids, '0' + id)) ? 0 : 1;
   a.CW = CW; a.ncg = cin / CW;
   a.cl2 = ilog2_exact(CW / 8);
@@ -854,7 +848,7 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
   // 16 / 32 / 96 B: PS/32 odd (or a single 16-B chunk); at x stride 2 the K pixels are 2*PS apart: 80 B
   // SV_WT_PAD16: 16-channel slices at x stride 2 (packed d5) on a 96-B K-pixel pitch.  Measured: LDS bank conflicts
   // 46 % -> 1.3 %, LDS-active cycles -45 %, kernel time unchanged (110 us): the loop is not LDS-throughput-bound.
-  static const bool pad16 = getenv("SV_WT_PAD16") != nullptr;
+  static const bool pad16 = SV_TUNE_FLAG("SV_WT_PAD16");
   a.PS = CW * 2 + (CW == 32 ? (w.SX == 2 ? 16 : 32) : (CW == 16 && w.SX == 2 && pad16) ? 16 : 0);
   a.ldy = cout; a.YS = cout * 2 + (cout >= 32 ? 32 : 0);
   a.lycp = ilog2_exact(cout / 8);
@@ -864,7 +858,7 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
   a.Cin_real = w.Cin_real; a.N = w.N; a.ntaps = nt;
   memcpy(a.dy, w.dy, sizeof(a.dy));
   memcpy(a.dx, w.dx, sizeof(a.dx));
-  static const bool no_pairx = getenv("SV_WT_NO_PAIRX") != nullptr;   // A/B knob
+  static const bool no_pairx = SV_TUNE_FLAG("SV_WT_NO_PAIRX");   // A/B knob
   const bool pairx = id == 6 && !no_pairx;
   if (pairx) {
     // 8-channel pixel records: fragment rows 8..15 (channel block 8..15 of the transposed read) are the next
@@ -881,7 +875,6 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
     av[i] = a;
     av[i].A = wv[i].A; av[i].dY = wv[i].dY; av[i].dW = wv[i].dW; av[i].dbias = wv[i].dbias;
     av[i].ws = allow_slab ? wv[i].ws : nullptr; av[i].ws_bytes = allow_slab ? wv[i].ws_bytes : 0;
-    av[i].defer = wv[i].defer; av[i].n_defer = wv[i].n_defer;
   }
   sv_trace_note("wgrad_tile");
   // <TPW, CIF, COF, KC>
@@ -911,7 +904,7 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
 int svk_wgrad_tile(const WgradArgs& w, hipStream_t st) { return svk_wgrad_tile_multi(&w, 1, st); }
 
 int svk_wgrad_dispatch_multi(const WgradArgs* w, int n, int dtype, int cfg, hipStream_t st) {
-  static const bool no_multi = getenv("SV_NO_MULTI") != nullptr;
+  const bool no_multi = sv_tune_no_multi();
   if (dtype == SV_BF16 && !no_multi && n <= SV_WGRAD_MAX_MULTI) {
     const int rc = svk_wgrad_tile_multi(w, n, st);
     if (rc != SV_E_UNSUPPORTED) return rc;

@@ -397,10 +397,15 @@ int launch_f32(const WgradTileArgs* a, int n, int msplit, int groups, size_t lds
 
 // The seven conv layers of the SPLIT-VAE encoders / decoders and the 3 x 3 layers of LG-SPAIR's object networks.  SV_E_UNSUPPORTED:
 // any other shape, a missing / small workspace -- the caller falls back to the im2col kernel.
+// A/B knobs of both planners below: pixels of the largest tile, workgroups a launch aims at, LDS bytes a workgroup's tile may take (the measurement
+// behind 52000 is beside its use in svk_wgrad_tile_f32_multi)
+static int wtf32_bm_max() { static const int v = SV_TUNE_INT("SV_WTF32_BM", 256); return v; }
+static int wtf32_wgs() { static const int v = SV_TUNE_INT("SV_WTF32_WGS", 512); return v; }
+static int wtf32_lds_max() { static const int v = SV_TUNE_INT("SV_WTF32_LDS", 52000); return v; }
 #define F32_REJ(why) do { if (trace) fprintf(stderr, "wgrad_tile_f32: not taken (%s)\n", why); return SV_E_UNSUPPORTED; } while (0)
 int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
-  static const bool trace = getenv("SV_TRACE_DISPATCH") != nullptr;
-  static const bool off = getenv("SV_NO_WGRAD_TILE_F32") != nullptr;
+  const bool trace = sv_trace_dispatch();
+  static const bool off = SV_TUNE_FLAG("SV_NO_WGRAD_TILE_F32");
   if (off || n < 1 || n > SV_WGRAD_MAX_MULTI) F32_REJ("off / problems");
   const WgradArgs& w = wv[0];
   if (w.lOY < 0 || w.lOX < 0 || w.S > 2 || (w.S != w.SX && !w.fold_kw) || (w.ups && w.S != 1) || w.ycols != w.ldy) F32_REJ("form");
@@ -417,7 +422,7 @@ int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
   const int CW = cin >= 16 ? 16 : 8;
   if (cin % CW || (cin != 8 && ilog2_exact(cin) < 0)) F32_REJ("channels");
   // 8-channel inputs (e1's padded RGB), even KW, taps y-major: tap pairs (wgrad_tile.hip's pairx)
-  static const bool no_pairx = getenv("SV_WTF32_NO_PAIRX") != nullptr;
+  static const bool no_pairx = SV_TUNE_FLAG("SV_WTF32_NO_PAIRX");
   bool pairx = CW == 8 && cin == 8 && nt == 36 && !w.fold_kw && !no_pairx;
   for (int u = 0; u < nt / 2 && pairx; ++u) pairx = w.dy[2 * u + 1] == w.dy[2 * u] && w.dx[2 * u + 1] == w.dx[2 * u] + 1;
   const int ntk = pairx ? nt / 2 : nt;                      // taps the kernel walks
@@ -432,17 +437,16 @@ int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
   }
   // pixels per tile: the largest of 256 .. 32 whose input patch + dY tile leave two workgroups per CU their LDS
   WgradTileArgs a;
-  static const int bm_max = getenv("SV_WTF32_BM") ? atoi(getenv("SV_WTF32_BM")) : 256;      // A/B knobs
-  static const int wgs = getenv("SV_WTF32_WGS") ? atoi(getenv("SV_WTF32_WGS")) : 512;
+  const int bm_max = wtf32_bm_max(), wgs = wtf32_wgs();
   // LDS per workgroup the tile may take.  78 KB (two workgroups per CU) gives the best launch ALONE on the chip; in the step the weight gradients run on the side
   // stream beside the input-gradient chain, and 52 KB tiles (three to five workgroups per CU fit beside the other stream's) make the 512-image fp32 step 2.3 %
   // shorter: 9.82-9.90 -> 9.60-9.62 ms (40 KB: 9.68; 128-pixel tiles at 78 KB: 9.77; profiles/r05_wtf32_lds_ab.txt), the serial rows 0-3 % longer
-  static const int lds_max = getenv("SV_WTF32_LDS") ? atoi(getenv("SV_WTF32_LDS")) : 52000;
+  const int lds_max = wtf32_lds_max();
   // double-buffered staging (plain / clamped inputs; the kernel's g.db loop): both buffers inside SV_WTF32_DB_LDS bytes.  OPT-IN (default 0 = single buffer).  Measured
   // (2 x 512 images): alone on the chip the d4 weight gradient goes 1.020 -> 0.990 ms and d5's 0.605 -> 0.590 at 64 KB (e2: 0.335 -> 0.359, its stride-2 tile halves),
   // but the STEP goes 9.19 -> 9.35 ms (48 KB: 9.32, 78 KB: 9.38, 120 KB: 9.60): the second buffer takes the LDS that the other streams' workgroups lived in
-  static const int db_lds = getenv("SV_WTF32_DB_LDS") ? atoi(getenv("SV_WTF32_DB_LDS")) : 0;
-  static const bool no_dma = getenv("SV_WT32_NO_DMA") != nullptr;          // A/B: the register staging
+  static const int db_lds = SV_TUNE_INT("SV_WTF32_DB_LDS", 0);
+  static const bool no_dma = SV_TUNE_FLAG("SV_WT32_NO_DMA");          // A/B: the register staging
   const bool db = db_lds > 0 && !no_dma && !w.ups && !w.s2d3;
   int BM = bm_max;
   for (;; BM >>= 1) {
@@ -470,7 +474,7 @@ int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
   a.contig = 1; a.CW = CW; a.ncg = cin / CW; a.cl2 = ilog2_exact(CW / 4);
   a.dma = no_dma ? 0 : 1;
   a.db = db ? 1 : 0;
-  static const int dbg = getenv("SV_WT32_DBG") ? atoi(getenv("SV_WT32_DBG")) : 0;       // (read by SV_DEBUG_KNOBS builds only)
+  static const int dbg = SV_TUNE_INT("SV_WT32_DBG", 0);       // (read by SV_DEBUG_KNOBS builds only)
   a.dbg = dbg;
   a.OY = OY; a.OX = OX; a.tilesX = OX / TW; a.tilesY = OY / TH;
   a.ntiles = a.tilesX * a.tilesY * ((B + NB - 1) / NB);
@@ -540,7 +544,7 @@ int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
 // The four class problems of n <= 2 per-class polyphase layers as ONE launch (see wgrad_polyc_f32_kernel).  cls[c * n + i]: class c of network i (svg_polyc_wgrad_args
 // + pointers; ws = the class's slab region); descriptors of the 4 n slab reduces are appended to rd.  SV_E_UNSUPPORTED: no instantiation / small workspace (nothing launched).
 int svk_wgrad_polyc_f32_multi(const WgradArgs* cls, int n, int mask, WgradReduceDesc* rd, int* nrd, hipStream_t st) {
-  static const bool trace = getenv("SV_TRACE_DISPATCH") != nullptr;
+  const bool trace = sv_trace_dispatch();
   // OPT-IN (SV_WGRAD_POLYC_FUSED=1).  Measured (2 x 512 images, profiles/r05_polyc_fused_ab.txt): alone on the chip the d4 weight gradient goes 1.078 -> 0.949 ms (the input
   // tile moves once), but the 512-image STEP goes 9.355 -> 9.54 ms: at 239 VGPRs the kernel leaves no room beside it for the other streams' workgroups, and the step lives
   // on that co-residency (same finding as the 52-KB tiles).  The default keeps the four class launches.
@@ -554,9 +558,7 @@ int svk_wgrad_polyc_f32_multi(const WgradArgs* cls, int n, int mask, WgradReduce
   if (ntc[0] != 25 || ntc[1] != 20 || ntc[2] != 20 || ntc[3] != 16) F32_REJ("taps");
   const int OY = 1 << w.lOY, OX = 1 << w.lOX, cin = w.Cin_pad, CW = 16;
   if (OX < 4 || OY * OX < 16 || cin % CW) F32_REJ("grid / channels");
-  static const int bm_max = getenv("SV_WTF32_BM") ? atoi(getenv("SV_WTF32_BM")) : 256;
-  static const int wgs = getenv("SV_WTF32_WGS") ? atoi(getenv("SV_WTF32_WGS")) : 512;
-  static const int lds_max = getenv("SV_WTF32_LDS") ? atoi(getenv("SV_WTF32_LDS")) : 52000;
+  const int bm_max = wtf32_bm_max(), wgs = wtf32_wgs(), lds_max = wtf32_lds_max();
   WgradTileArgs a;
   int BM = bm_max;
   for (;; BM >>= 1) {
