@@ -130,6 +130,32 @@ int sv_multibird_canvases(float* x, float* count, const uint8_t* sprites, int32_
                           const sv_multibird_layout* layouts, int32_t bg, int32_t B, uint64_t seed, int32_t split,
                           int64_t sample_offset, void* stream);
 
+/* ---------------------------------------------------------------- A1d: device-resident datasets
+ * The batch fetch of vae/main.py:56-61 (shuffle -> batch) over a training set that stays in device memory: src[N,H,W,3] is
+ * the whole set, uint8 (SVHN's pixel levels) or fp32 (the CelebA files' images), index[B] int32 the batch's rows on the
+ * device.  A uint8 level v becomes lut[v]: lut[256] fp32 on the device, filled by the host with vae/data.py:52's
+ * (v / 255.0 * 2 - 1) in float64 rounded once, so the fetch is bit for bit the host's normalisation; fp32 sources are
+ * copied (lut may be NULL).  An index outside [0, N) is clamped to it: nothing is read outside src (the host layer refuses
+ * such an index before upload).  No atomics, no workspace, every output element written exactly once.
+ * All three image entries: SV_E_BADARG for a null pointer (lut only for uint8), N, B, H or W <= 0, a src_dtype outside
+ * sv_src_dtype, or a src / output pointer that is not 16-byte aligned; SV_E_UNSUPPORTED for B > 65535 or H * W * 3 >= 2^30. */
+typedef enum { SV_SRC_U8 = 0, SV_SRC_F32 = 1 } sv_src_dtype;
+/* x[B,H,W,3] fp32, x[b] = value(src[index[b]]). */
+int sv_dataset_gather(const void* src, int32_t src_dtype, const float* lut, const int32_t* index, float* x, int32_t N, int32_t B,
+                      int32_t H, int32_t W, void* stream);
+/* The same fetch fused with the patch scramble and the step's input staging: bit for bit sv_dataset_gather followed by
+ * sv_scramble_gather_staged (perm, patch, images6, x8, xh8, dtype as there) without the intermediate x.  x8 = xh8 = NULL:
+ * images6 only (sv_scramble_gather).  A perm entry outside [0, (H/patch)^2) is clamped.  Also SV_E_BADARG: patch <= 0, one of
+ * x8 / xh8 NULL and the other not, a dtype outside sv_dtype when they are given; SV_E_UNSUPPORTED: H != W, H % patch != 0, or
+ * a uint8 image above 57 KiB (it is staged in LDS; 128 x 128 is 48 KiB). */
+int sv_dataset_gather_scramble(const void* src, int32_t src_dtype, const float* lut, const int32_t* index, const int32_t* perm,
+                               float* images6, void* x8, void* xh8, int32_t dtype, int32_t N, int32_t B, int32_t H, int32_t W,
+                               int32_t patch, void* stream);
+/* labels[N] uint8 on the device -> out[B,depth] fp32 = one_hot(labels[index[b]] - 1, depth) (vae/data.py:55-57: SVHN's
+ * label 10, the digit 0, lands on the last index); a label outside 1..depth gives an all-zero row (tf.one_hot).
+ * SV_E_BADARG: a null pointer, N, B or depth <= 0. */
+int sv_dataset_onehot(const uint8_t* labels, const int32_t* index, float* out, int32_t N, int32_t B, int32_t depth, void* stream);
+
 /* ---------------------------------------------------------------- A6: discretised logistic NLL
  * Replaces discretised_logistic_loss (vae/trainer.py:21-38) + reduce_sum[1,2,3] (:127-128) and,
  * when grad != NULL, its adjoint under tape.gradient (:137).

@@ -70,6 +70,7 @@ TAPE_PHASE_FORWARD, TAPE_PHASE_BACKWARD, TAPE_PHASE_ADAM = 1, 2, 4
 TAPE_MAX_LOSS = 16
 
 
+SV_SRC_U8, SV_SRC_F32 = 0, 1      # sv_src_dtype: element type of a device-resident dataset (include/splitvae.h)
 SV_MB_SOLID_FIXED, SV_MB_UNSEEN_SOLID_FIXED, SV_MB_CKB_ROT_6, SV_MB_UNSEEN_CKB_ROT_6 = range(4)
 
 
@@ -113,6 +114,9 @@ SYMBOLS = {
     "sv_multibird_layout_host": (C.c_int, [_vp, _i32, _i32, _u64, _i32, _i64]),
     "sv_multibird_layouts": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _u64, _i32, _i64, _vp]),
     "sv_multibird_canvases": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _u64, _i32, _i64, _vp]),
+    "sv_dataset_gather": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "sv_dataset_gather_scramble": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "sv_dataset_onehot": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "sv_dlogistic_nll": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _f, _i32, _i32, _i32, _vp, _vp]),
     "sv_dlogistic_nll_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "sv_reparam_kl_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32,

@@ -102,6 +102,40 @@ class Augmentator(object):
             self._mark_staged(out, plan)
         return out[0] if single else out
 
+    # ---------------------------------------------------------------- device-resident sets (data.ResidentDataset)
+    def scramble_from(self, dataset, index, perm=None, sample_offset=0, plan=None):
+        """scramble(dataset.gather(index), ...) in one kernel (sv_dataset_gather_scramble): index[B] int32 on the device (or a
+        host list, checked and uploaded) names the batch's rows of the resident set; the batch itself never exists in memory.
+        Same Philox draws in the same order as scramble(), same staging with plan=."""
+        return self._scramble_from(dataset, index, self.size, perm, sample_offset, plan)
+
+    def _scramble_from(self, dataset, index, size, perm, sample_offset, plan):
+        if not torch.is_tensor(index):
+            index = dataset.upload_index(index)
+        B, H, W = index.shape[0], dataset.H, dataset.W
+        if H != W or H % size:
+            raise ValueError("scramble assumes square images and size | H (augmentation.py:44-46)")
+        if perm is None:
+            perm = ops.random_perm(B, (H // size) * (W // size), self.seed, self._step, sample_offset, index.device)
+            self._step += 1
+        staged = self._staged_buffers(plan, False, B, H, W)
+        out = ops.dataset_gather_scramble(dataset.data, index, perm.to(torch.int32).contiguous(), size, lut=dataset.lut, staged=staged)
+        if staged is not None:
+            self._mark_staged(out, plan)
+        return out
+
+    def augment_from(self, dataset, index, plan=None):
+        """augment(dataset.gather(index)) for the constructor's type: scramble and the one-size-per-pipeline mix_scramble fetch
+        and scramble in one kernel; blur, high_low_pass, the per-image mix_scramble and no_op run on the gathered batch."""
+        if self.type == 'scramble':
+            return self._scramble_from(dataset, index, self.size, None, 0, plan)
+        if self.type == 'mix_scramble' and not self.per_image:
+            return self._scramble_from(dataset, index, self.mix_size, None, 0, plan)
+        if not torch.is_tensor(index):
+            index = dataset.upload_index(index)
+        x = dataset.gather(index)
+        return x if self.type == 'no_op' else self.augment(x, plan=plan)
+
     # ---------------------------------------------------------------- mix_scramble (augmentation.py:59-81)
     @property
     def mix_size(self):

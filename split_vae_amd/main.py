@@ -3,7 +3,8 @@
     python -m split_vae_amd.main --beta 120 --patch_size 8 --dataset celeba64 -no_label --synthetic
     python -m split_vae_amd.main --model gmvae --beta 40 --patch_size 4       (GMVAE baseline, Table 2)
 
-Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout, --mix_per_image.
+Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout, --mix_per_image,
+--resident_data.
 """
 import argparse
 
@@ -41,6 +42,9 @@ def build_parser():
     ap.add_argument("--mix_per_image", action="store_true",
                     help="--augmentation mix_scramble: draw a patch size per image (the intent of augmentation.py:60-64) instead of one "
                          "per pipeline (what the reference runs: np.random.choice when Dataset.map traces mix_scramble)")
+    ap.add_argument("--resident_data", action="store_true",
+                    help="hold the on-disk dataset in device memory (SVHN as uint8, CelebA as fp32) and fetch, scramble and stage each "
+                         "batch in one kernel from a host-side index list; same batches, same permutations, same losses")
     return ap
 
 
@@ -104,8 +108,10 @@ def main(argv=None):
     from . import data, trainer
 
     augmentor, test_augmentor = make_augmentors(config)
+    resident = bool(config.get("resident_data"))
     train_ds, test_ds, input_shape = data.get_dataset(config.dataset, config.batch_size, synthetic=config.synthetic,
-                                                      data_dir=config.data_dir, get_label=config.label)
+                                                      data_dir=config.data_dir, get_label=config.label,
+                                                      resident=resident)
     if config.label and not train_ds.labelled:
         # only the SVHN files carry labels (vae/data.py:54-62); the reference's labelled pipeline (vae/main.py:56-58)
         # cannot run on CelebA either, its README passes -no_label there
@@ -115,12 +121,24 @@ def main(argv=None):
         # vae/trainer.py:81-97 trains / loads the SVHN probe classifier here; its weights blob is missing upstream
         # (.MISSING_LARGE_BLOBS:1), so the labels ride along unused and the classifier metrics are not reported
         print('Note: classifier-based test metrics are not available (svhn_classifier_weights.h5 is not in the reference repo)')
+    if resident:
+        # the test batches first, as below: the augmentor's Philox call indices, hence every permutation, match a run without the flag
+        test_batches = [(test_augmentor.augment_from(test_ds, i), test_ds.one_hot(i)) if config.label else test_augmentor.augment_from(test_ds, i)
+                        for i in test_ds.index_batches()]
+    elif config.label:
         train_ds = ((augmentor.augment(x), y) for x, y in train_ds)     # vae/main.py:57-58
         test_batches = [(test_augmentor.augment(x), y) for x, y in test_ds]
     else:
         train_ds = (augmentor.augment(x) for x in train_ds)             # vae/main.py:60-61
         test_batches = [test_augmentor.augment(x) for x in test_ds]
     model, optimizer = make_model(args.model, config, input_shape)
+    if resident:
+        # the fetch writes the training plan's padded inputs itself (the plan of this batch size, looked up per batch: the trainer sets beta first)
+        rds, B = train_ds, config.batch_size
+        if config.label:
+            train_ds = ((augmentor.augment_from(rds, i, plan=model.plan(B)), rds.one_hot(i)) for i in rds.index_batches())
+        else:
+            train_ds = (augmentor.augment_from(rds, i, plan=model.plan(B)) for i in rds.index_batches())
     model.summary()
     print('Training local-global autoencoder')
     return trainer.train_local_global_autoencoder(model, optimizer, config.dataset, train_ds, test_batches, config=config)

@@ -161,6 +161,47 @@ def scramble_gather_mixed(x, perm, sizes, staged=None):
     return out
 
 
+# ------------------------------------------------------------------ A1d device-resident datasets (vae/main.py:56-61 on the device)
+_SRC_DT = {torch.uint8: _lib.SV_SRC_U8, torch.float32: _lib.SV_SRC_F32}
+
+
+def _dataset_args(src, lut, index):
+    N, H, W, Cc = src.shape
+    assert Cc == 3 and src.dtype in _SRC_DT and index.dtype == torch.int32 and index.dim() == 1
+    if src.dtype == torch.uint8:
+        assert lut is not None and lut.dtype == torch.float32 and lut.shape == (256,)
+    return N, H, W, index.shape[0], _SRC_DT[src.dtype]
+
+
+def dataset_gather(src, index, lut=None):
+    """src[N,H,W,3] uint8 or fp32 (the resident set), index[B] int32, lut[256] fp32 (uint8 sources: the value of each level)
+    -> x[B,H,W,3] fp32 = value(src[index])."""
+    N, H, W, B, sdt = _dataset_args(src, lut, index)
+    x = torch.empty((B, H, W, 3), dtype=torch.float32, device=src.device)
+    check(_lib.load().sv_dataset_gather(_p(src), sdt, _p(lut), _p(index), _p(x), N, B, H, W, _stream()), "sv_dataset_gather")
+    return x
+
+
+def dataset_gather_scramble(src, index, perm, patch, lut=None, staged=None):
+    """dataset_gather followed by scramble_gather(..., staged=) in one kernel -> [B,H,W,6] = concat([x, x_aug], axis=-1)."""
+    N, H, W, B, sdt = _dataset_args(src, lut, index)
+    assert perm.dtype == torch.int32 and perm.shape == (B, (H // patch) * (W // patch))
+    out = torch.empty((B, H, W, 6), dtype=torch.float32, device=src.device)
+    x8, xh8, dt = (None, None, SV_F32) if staged is None else _staged_args(staged, B, H, W)
+    check(_lib.load().sv_dataset_gather_scramble(_p(src), sdt, _p(lut), _p(index), _p(perm), _p(out), x8, xh8, dt, N, B, H, W, patch,
+                                                 _stream()), "sv_dataset_gather_scramble")
+    return out
+
+
+def dataset_onehot(labels, index, depth=10):
+    """labels[N] uint8 (resident), index[B] int32 -> [B,depth] fp32 = one_hot(labels[index] - 1) (data.one_hot_svhn)."""
+    assert labels.dtype == torch.uint8 and labels.dim() == 1 and index.dtype == torch.int32 and index.dim() == 1
+    B = index.shape[0]
+    out = torch.empty((B, depth), dtype=torch.float32, device=labels.device)
+    check(_lib.load().sv_dataset_onehot(_p(labels), _p(index), _p(out), labels.shape[0], B, depth, _stream()), "sv_dataset_onehot")
+    return out
+
+
 # ------------------------------------------------------------------ A1c Multi-Bird canvases (spair/data.py:39-174)
 MULTIBIRD_LAYOUT_WORDS = C.sizeof(_lib.MultibirdLayout) // 4
 
