@@ -691,7 +691,9 @@ typedef struct {
   int64_t w_off, b_off;
   int32_t B, H, W, C, Cout, k, stride, Ho, Wo, Hc, Wc, inverse, training;
   int32_t loss_idx, dyn_idx, mode, R, stream_id;
-  int32_t group;                /* UNARY: consecutive nodes with the same non-zero group are independent of each other and run as ONE launch */
+  int32_t group;                /* UNARY: consecutive nodes with the same non-zero group are independent of each other and run as ONE launch (at most 8 per launch).
+                                   Parts may READ the same source columns (a tile of z into two places): their adjoints then run one launch per part, in tape
+                                   order reversed, because they add into the same gradient */
   int32_t lane;                 /* 0: the caller's stream; 1..3: a HIP stream of the tape's own.  Independent branches of the model (LG-SPAIR's x-hat / background
                                    networks beside the object pipeline, spair/spair.py:84-104) recorded on another lane run concurrently with lane 0; sv_tape_finalize
                                    derives every cross-lane dependency from the nodes' tensors and sv_tape_run orders conflicting accesses in tape order with events,

@@ -13,8 +13,8 @@
 //   STN / RENDER / ZPRES / LOSS   stn.hip, spair_render.hip and the per-image loss sums of spair/trainer.py with their gradients
 //   NOISE      Philox draws for the tensors the reference fills from tf.random (pinned by the caller in tests)
 // Gradient buffers are zeroed once per step; every adjoint ADDS into its inputs' gradients (plain read-modify-write: launches are
-// stream-ordered), so fan-out needs no bookkeeping; kernels that can only assign go through a scratch buffer when their target has
-// other writers.  The loss nodes add their (weight / B)-scaled gradients during the forward pass: total = sum_i w_i * mean_b(loss_i),
+// stream-ordered), so fan-out needs no bookkeeping; kernels that can only assign (UPSAMPLE, the renderer's g_obj / g_bg, the LDS form
+// of the inverse STN) go through a scratch buffer when their target has other writers.  The loss nodes add their (weight / B)-scaled gradients during the forward pass: total = sum_i w_i * mean_b(loss_i),
 // weights per run (the annealed beta of spair/trainer.py:165-167 moves with the step).
 //
 // LANES (round 6): a node may name a lane (sv_tape_node::lane, 0 = the caller's stream).  Independent branches of the model -- LG-SPAIR's x-hat / background
@@ -294,7 +294,7 @@ inline int nblk(int64_t n) { return (int)((n + 255) / 256); }
 struct sv_tape {
   std::vector<TT> tens;
   std::vector<sv_tape_node> nodes;
-  struct Extra { sv_conv_desc cd; int64_t wf_off = 0, wd_off = 0; int64_t scratch = -1, scratch2 = -1; int split_fwd = 0; bool has_conv = false; };
+  struct Extra { sv_conv_desc cd; int64_t wf_off = 0, wd_off = 0; int64_t scratch = -1, scratch2 = -1, scratch3 = -1, scratch4 = -1; int split_fwd = 0; bool has_conv = false; };
   std::vector<Extra> ex;
   std::vector<PrepJob> jobs;
   int prep_blocks = 0;
@@ -599,12 +599,20 @@ extern "C" int sv_tape_finalize(sv_tape* t) {
       e.scratch = scratch((t->tens[n.x].rows * t->tens[n.x].ld + 1) / 2);
       e.scratch2 = scratch((t->tens[n.y].rows * t->tens[n.y].ld + 1) / 2);
     }
-    if (n.kind == SV_TAPE_STN) e.scratch = scratch(t->tens[n.t2].rows * 4);
+    auto shared = [&](int id) { return gr(id) && t->tens[t->root(id)].writers > 1; };       // another adjoint (or a loss node) adds into this gradient too
+    if (n.kind == SV_TAPE_STN) {
+      e.scratch = scratch(t->tens[n.t2].rows * 4);
+      // the LDS form of the inverse STN's adjoint STORES the object's gradient: through a scratch buffer when the objects have other consumers
+      if (shared(n.x) && sv_stn_bwd_overwrites(n.H, n.W, n.C, n.inverse)) e.scratch3 = scratch(t->tens[n.x].rows * t->tens[n.x].ld);
+    }
     if (n.kind == SV_TAPE_ZPRES) { e.scratch = scratch(t->tens[n.t2].rows); e.scratch2 = scratch(t->tens[n.t3].rows); }
     if (n.kind == SV_TAPE_RENDER) {
       const int64_t nz = t->tens[n.t3].rows;
       e.scratch = scratch(2 * ((nz + 63) / 64 * 64) + (gr(n.t2) ? 0 : (int64_t)n.B * n.H * n.W * n.C));     // g_zp, g_zd (+ a sink for g_bg)
       e.scratch2 = scratch(sv_spair_render_bwd_workspace_floats(n.B, n.H, n.W));
+      // the renderer's adjoint STORES g_obj and g_bg: through scratch buffers when the objects / the background have other consumers
+      if (shared(n.x)) e.scratch3 = scratch(t->tens[n.x].rows * t->tens[n.x].ld);
+      if (shared(n.t2)) e.scratch4 = scratch(t->tens[n.t2].rows * t->tens[n.t2].ld);
     }
     if (n.kind == SV_TAPE_UPSAMPLE && gr(n.x) && t->tens[t->root(n.x)].writers > 1) e.scratch = scratch(t->tens[n.x].rows * t->tens[n.x].ld);
   }
@@ -903,8 +911,13 @@ int node_backward(sv_tape* t, size_t i, const sv_tape_run_args* a, hipStream_t s
     case SV_TAPE_STN: {
       if (!t->grad(n.y)) return SV_OK;
       const TT& zw = T(n.t2);
-      SV_TRY(sv_stn_sample_bwd(t->act(n.x), t->act(n.t2), t->grad(n.y), t->grad(n.x), t->scr(e.scratch), n.B, n.Hc, n.Wc, n.H, n.W, n.C, n.Ho, n.Wo,
-                               n.inverse, st));
+      SV_TRY(sv_stn_sample_bwd(t->act(n.x), t->act(n.t2), t->grad(n.y), e.scratch3 >= 0 ? t->scr(e.scratch3) : t->grad(n.x), t->scr(e.scratch), n.B, n.Hc,
+                               n.Wc, n.H, n.W, n.C, n.Ho, n.Wo, n.inverse, st));
+      if (e.scratch3 >= 0) {
+        const TT& x = T(n.x);
+        hipLaunchKernelGGL(acc_kernel, dim3(nblk(x.rows * x.ld)), dim3(256), 0, st, t->grad(n.x), x.ld, 0, t->scr(e.scratch3), x.rows * x.ld, x.ld, 1.0f);
+        SV_LAUNCH_CHECK();
+      }
       if (t->grad(n.t2)) {
         hipLaunchKernelGGL(acc_kernel, dim3(nblk(zw.rows * 4)), dim3(256), 0, st, t->grad(n.t2), 4, 0, t->scr(e.scratch), zw.rows * 4, 4, 1.0f);
         SV_LAUNCH_CHECK();
@@ -917,10 +930,19 @@ int node_backward(sv_tape* t, size_t i, const sv_tape_run_args* a, hipStream_t s
       const int64_t nz = (zd.rows + 63) / 64 * 64;
       float* g_zp = t->scr(e.scratch);
       float* g_zd = g_zp + nz;
-      float* g_bg = t->grad(n.t2) ? t->grad(n.t2) : g_zd + nz;
+      float* g_bg = e.scratch4 >= 0 ? t->scr(e.scratch4) : t->grad(n.t2) ? t->grad(n.t2) : g_zd + nz;
+      float* g_obj = e.scratch3 >= 0 ? t->scr(e.scratch3) : t->grad(n.x);
       SV_TRY(sv_spair_render_bwd_ws(t->act(n.x), t->act(n.t2), t->act(n.t3), t->act(n.t4), n.t6 >= 0 ? t->act(n.t6) : nullptr,
-                                    t->grad(n.y), t->grad(n.x), g_bg, g_zp, g_zd, n.B, n.R, n.H, n.W, n.C, t->scr(e.scratch2),
+                                    t->grad(n.y), g_obj, g_bg, g_zp, g_zd, n.B, n.R, n.H, n.W, n.C, t->scr(e.scratch2),
                                     sv_spair_render_bwd_workspace_floats(n.B, n.H, n.W), st));
+      if (e.scratch3 >= 0) {
+        const TT& x = T(n.x);
+        hipLaunchKernelGGL(acc_kernel, dim3(nblk(x.rows * x.ld)), dim3(256), 0, st, t->grad(n.x), x.ld, 0, g_obj, x.rows * x.ld, x.ld, 1.0f);
+      }
+      if (e.scratch4 >= 0) {
+        const TT& bg = T(n.t2);
+        hipLaunchKernelGGL(acc_kernel, dim3(nblk(bg.rows * bg.ld)), dim3(256), 0, st, t->grad(n.t2), bg.ld, 0, g_bg, bg.rows * bg.ld, bg.ld, 1.0f);
+      }
       if (t->grad(n.t3)) hipLaunchKernelGGL(acc_kernel, dim3(nblk(zd.rows)), dim3(256), 0, st, t->grad(n.t3), zd.ld, 0, g_zd, zd.rows, 1, 1.0f);
       if (t->grad(n.t4)) hipLaunchKernelGGL(acc_kernel, dim3(nblk(zp.rows)), dim3(256), 0, st, t->grad(n.t4), zp.ld, 0, g_zp, zp.rows, 1, 1.0f);
       SV_LAUNCH_CHECK();
@@ -964,7 +986,25 @@ int group_forward(sv_tape* t, size_t b, size_t e, hipStream_t st) {
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
-int group_backward(sv_tape* t, size_t b, size_t e, hipStream_t st) {
+// Two parts of a group that add into overlapping columns of one gradient (a tile of z into two places) would read-modify-write them from different threads of one
+// launch, in no order: such a group runs its adjoint as one launch per part, last part first.  (Views of a root are compared by the root alone.)
+bool group_sources_overlap(const sv_tape* t, size_t b, size_t e) {
+  for (size_t i = b; i < e; ++i) {
+    const sv_tape_node& p = t->nodes[i];
+    if (!t->grad(p.y) || !t->grad(p.x)) continue;
+    for (size_t j = i + 1; j < e; ++j) {
+      const sv_tape_node& q = t->nodes[j];
+      if (!t->grad(q.y) || !t->grad(q.x) || t->root(p.x) != t->root(q.x)) continue;
+      if (p.x != q.x || (p.xo < q.xo + q.n && q.xo < p.xo + p.n)) return true;
+    }
+  }
+  return false;
+}
+int group_backward(sv_tape* t, size_t b, size_t e, const sv_tape_run_args* a, hipStream_t st) {
+  if (group_sources_overlap(t, b, e)) {
+    for (size_t i = e; i-- > b;) SV_TRY(node_backward(t, i, a, st));
+    return SV_OK;
+  }
   UMulti m;
   memset(&m, 0, sizeof(m));
   int64_t tot = 0;
@@ -1080,7 +1120,7 @@ extern "C" int sv_tape_run(sv_tape* t, const sv_tape_run_args* a, void* stream) 
       const size_t b = group_begin(t, i);
       hipStream_t s = lanes ? lane_stream(t, t->nodes[i].lane, st) : st;
       if (lanes) SV_TRY(lane_waits(t, t->bs.waits[i], s));
-      if (b < i) { SV_TRY(group_backward(t, b, i + 1, s)); i = b; }
+      if (b < i) { SV_TRY(group_backward(t, b, i + 1, a, s)); i = b; }
       else SV_TRY(node_backward(t, i, a, s));
       if (lanes && t->bs.rec[i]) SV_TRY(lane_record(t, (int)i, s));          // (i = the unit's first node by now)
     }
