@@ -645,6 +645,50 @@ int sv_lgvae_profile_read(sv_lgvae_plan* plan, int32_t max_entries, char names[]
  * rate against the MFMA peak is a utilisation figure only at THIS count.  Equal to flops_per_launch for every direct-form scope. */
 int sv_lgvae_profile_read_issued(sv_lgvae_plan* plan, int32_t max_entries, double* issued_flops_per_launch);
 
+/* ---------------------------------------------------------------- IW: importance-weighted test log-likelihood of LGVae
+ * No reference counterpart: test_step_lg_vae (vae/trainer.py:199-233) reports the single-sample ELBO pieces only.  This is the
+ * K-sample importance-weighted bound (Burda et al.), log (1/K) sum_k p(x, z_k) / q(z_k | x), the estimator of log p(x) VAE papers
+ * are compared by.  The expensive parts are the plan's: SV_PHASE_FWD_ENCODERS once per batch, then per sample
+ * SV_PHASE_FWD_DECODERS | SV_PHASE_LOSS over the latents in `zcat`; the two entries below are the code between those passes
+ * (csrc/iw.hip).  K samples cost K decoder passes and K + 1 launches of sv_iw_advance, all on one stream, no host round trip.
+ *
+ * The estimator.  Image i has encoder outputs mu_g, sig_g [Lg] (from x) and mu_l, sig_l [Ll] (from x_hat): the plan buffers
+ * z_mean_x, z_sig_x, z_mean_xh, z_sig_xh.  Sample k:
+ *   z = mu + sig * eps per dimension -- the fp32 expression of sv_reparam_kl_fwd -- stored to zcat in the plan's dtype, columns
+ *     [0, Lg) global, [Lg, Lg + Ll) local;
+ *   r(i,k) = sum_j [log N(z_j; 0, 1) - log N(z_j; mu_j, sig_j)] = sum_j [(eps_j^2 - z_j^2) / 2 + log sig_j] over all Lg + Ll
+ *     dimensions, fp32;
+ *   after the decoder + loss pass over that zcat the plan holds nll_x[i], nll_xh[i] (fp32);
+ *   lw_joint = -nll_x - nll_xh + r   estimates log p(x, x_hat) under p(z_g) p(z_l) p(x | z_g, z_l) p(x_hat | z_l);
+ *   lw_x     = -nll_x + r            the same proposal as an importance sampler for the marginal p(x): the literature's figure;
+ *   per image L_K = logsumexp_k lw(i,k) - log K for both weights, elbo = mean_k lw_joint;
+ *   bits per dimension of x = -mean_i L_K^x / (H W 3 ln 2), no offset: the discretised logistic is a probability MASS over the
+ *     256 levels.
+ * SV_BF16 plans: the stored value enters -- z~ = bf16(z) in the prior term, eps~ = (z~ - mu) / sig in the q term -- so the weight
+ * is evaluated at the latent the decoder consumed.  SV_F32: z and eps as drawn.
+ * Device state [B,5] fp64 per image: (m, s) of the streamed log-sum-exp of lw_joint, (m, s) of lw_x, sum_k lw_joint;
+ * m' = max(m, lw), s' = s exp(m - m') + exp(lw - m').  (Log-weights are ~1e4 nats and K may be thousands: fp32 sums lose the
+ * third decimal.)
+ * Random numbers: eps [B, Lg + Ll] pins the draw; NULL: the library's Philox4x32-10 with a key constant of its own (seed ^
+ * 0x1a7e17a11eed) and counter (dimension j, global image index sample_offset + b, 'iw' tag | 0 global / 1 local, sample k), the
+ * Box-Muller of sv_reparam_kl_fwd: sample k of image i is a pure function of (seed, i, k), whatever batch it sits in and
+ * whatever K is, and never coincides with a training step's draws.
+ *
+ * sv_iw_advance: `k` = the number of samples drawn before this call.  SV_IW_ACCUMULATE folds sample k - 1 -- nll_x, nll_xh and
+ * the r its draw left in r[B] -- into state (k == 1 starts the state: it need not be initialised); SV_IW_DRAW then draws sample
+ * k: writes zcat (row pitch ldz elements) and r.  The first call of a batch is draw-only (k = 0), the last accumulate-only
+ * (k = K).  One wave per image; no atomics; bit-reproducible.  SV_E_BADARG: B, Lg or Ll <= 0, k < 0, flags 0 or with an unknown
+ * bit, a z_dtype outside sv_dtype, r NULL; with ACCUMULATE: nll_x / nll_xh / state NULL or k < 1; with DRAW: a null mean / sig /
+ * zcat or ldz < Lg + Ll. */
+enum { SV_IW_ACCUMULATE = 1, SV_IW_DRAW = 2 };
+int sv_iw_advance(const float* z_mean_x, const float* z_sig_x, const float* z_mean_xh, const float* z_sig_xh, const float* eps,
+                  void* zcat, int32_t z_dtype, int32_t ldz, float* r, const float* nll_x, const float* nll_xh, double* state,
+                  int32_t B, int32_t Lg, int32_t Ll, int32_t k, uint64_t seed, int64_t sample_offset, int32_t flags, void* stream);
+/* out3 [B,3] fp32 = per image (L_K^joint, L_K^x, elbo) from the state after K accumulated samples; acc (may be NULL) [4] fp64 +=
+ * (sum_i L_K^joint, sum_i L_K^x, sum_i elbo, B), the fp64 values added in image index order by one workgroup (deterministic):
+ * zero it once per test set, read it back once.  SV_E_BADARG: state or out3 NULL, K or B <= 0. */
+int sv_iw_finish(const double* state, int32_t K, float* out3, double* acc, int32_t B, void* stream);
+
 /* ---------------------------------------------------------------- SPLIT-SPAIR: Dense layers, exact fp32 on the matrix cores
  * tf.keras.layers.Dense (spair/spair.py:135-154, :185-202, :246-273, :341-366, :424-467) for ANY fan-in / fan-out, reading the Keras
  * [in, out] kernel as it lies in the variable buffer (dense_f32.hip).  x [M, ldx], y / dy [M, ldy], w [K, N] row-major.

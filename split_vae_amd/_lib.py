@@ -18,6 +18,7 @@ PHASE_INPUTS_STAGED = 512  # modifier: in8_x / in8_xh were written by sv_scrambl
 PHASE_NO_RECON = 256      # modifier: the fused-loss training step does not store out6_x / out6_xh (include/splitvae.h)
 PHASE_BUCKET_EVENTS = 1024  # modifier: record the gradient-bucket events of the data-parallel step (include/splitvae.h)
 PHASE_INFER = PHASE_PREP | PHASE_FORWARD
+IW_ACCUMULATE, IW_DRAW = 1, 2      # sv_iw_advance flags (include/splitvae.h)
 
 STATUS = {0: "SV_OK", -1: "SV_E_BADARG", -2: "SV_E_UNSUPPORTED", -3: "SV_E_WORKSPACE", -4: "SV_E_STATE"}
 STATUS_BADARG, STATUS_UNSUPPORTED, STATUS_WORKSPACE, STATUS_STATE = -1, -2, -3, -4
@@ -222,6 +223,8 @@ SYMBOLS = {
     "sv_lgvae_profile_filter": (C.c_int, [_vp, C.c_char_p]),
     "sv_lgvae_profile_read": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "sv_lgvae_profile_read_issued": (C.c_int, [_vp, _i32, _vp]),
+    "sv_iw_advance": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _i64, _i32, _vp]),
+    "sv_iw_finish": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp]),
 }
 
 _lib = None

@@ -4,7 +4,7 @@
     python -m split_vae_amd.main --model gmvae --beta 40 --patch_size 4       (GMVAE baseline, Table 2)
 
 Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout, --mix_per_image,
---resident_data.
+--resident_data, --iw_samples.
 """
 import argparse
 
@@ -45,6 +45,9 @@ def build_parser():
     ap.add_argument("--resident_data", action="store_true",
                     help="hold the on-disk dataset in device memory (SVHN as uint8, CelebA as fp32) and fetch, scramble and stage each "
                          "batch in one kernel from a host-side index list; same batches, same permutations, same losses")
+    ap.add_argument("--iw_samples", type=int, default=0,
+                    help="K > 0: after the report of every evaluation, the K-sample importance-weighted bound of the test log-likelihood "
+                         "(joint and x-only, nats) and the bits per dimension of x (split_vae_amd/iw.py); --model lgvae only")
     return ap
 
 
@@ -99,6 +102,8 @@ def make_model(model_name, config, input_shape):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    from .iw import check_model_name
+    check_model_name(args.model, args.iw_samples)    # before any data or device work
     from . import configure_hw_queues
     configure_hw_queues()                            # before the first HIP call (split_vae_amd/__init__.py)
     config = dotdict(vars(args))

@@ -697,8 +697,32 @@ def param_table(desc):
     return out
 
 
+# ------------------------------------------------------------------ IW: importance-weighted log-likelihood (include/splitvae.h)
+def iw_advance(z_mean_x, z_sig_x, z_mean_xh, z_sig_xh, zcat, r, k, flags, nll_x=None, nll_xh=None, state=None, eps=None, seed=0,
+               sample_offset=0):
+    """sv_iw_advance between two decoder passes: fold sample k - 1 into state [B,5] fp64 (IW_ACCUMULATE) and / or draw sample k
+    into zcat [B,Lg+Ll] (the plan's dtype) and r [B] (IW_DRAW).  eps [B,Lg+Ll] pins the draw."""
+    B, Lg = z_mean_x.shape
+    Ll = z_mean_xh.shape[1]
+    assert r.dtype == torch.float32 and (state is None or (state.dtype == torch.float64 and tuple(state.shape) == (B, 5)))
+    assert eps is None or (eps.dtype == torch.float32 and tuple(eps.shape) == (B, Lg + Ll))
+    check(_lib.load().sv_iw_advance(_p(z_mean_x), _p(z_sig_x), _p(z_mean_xh), _p(z_sig_xh), _p(eps), _p(zcat), sv_dtype(zcat.dtype),
+                                    zcat.shape[1], _p(r), _p(nll_x), _p(nll_xh), _p(state), B, Lg, Ll, int(k), int(seed),
+                                    int(sample_offset), int(flags), _stream()), "sv_iw_advance")
+
+
+def iw_finish(state, K, out3=None, acc=None):
+    """sv_iw_finish: out3 [B,3] fp32 = per-image (L_joint, L_x, elbo); acc [4] fp64 += their sums and the image count."""
+    B = state.shape[0]
+    if out3 is None:
+        out3 = torch.empty((B, 3), dtype=torch.float32, device=state.device)
+    assert state.dtype == torch.float64 and out3.dtype == torch.float32 and (acc is None or (acc.dtype == torch.float64 and acc.numel() >= 4))
+    check(_lib.load().sv_iw_finish(_p(state), int(K), _p(out3), _p(acc), B, _stream()), "sv_iw_finish")
+    return out3
+
+
 # ------------------------------------------------------------------ A9 SPLIT-GMVAE glue (vae/model.py:48-79,:116-135)
-ACT = {None: _lib.SV_ACT_NONE, "relu": _lib.SV_ACT_RELU, "elu": _lib.SV_ACT_ELU}
+ACT ={None: _lib.SV_ACT_NONE, "relu": _lib.SV_ACT_RELU, "elu": _lib.SV_ACT_ELU}
 
 
 def act_fwd(a, C_, x, act=None, y_act=None, rate=0.0, keep_in=None, keep_out=None, seed=0, step=0, stream_id=0,

@@ -210,6 +210,9 @@ def train_local_global_autoencoder(model, optimizer, dataset, train_dataset, tes
                                   te["x_recon_loss"], te["x_kl_loss"], te["x_recon_loss"] + te["x_kl_loss"],
                                   te["x_hat_recon_loss"], te["x_hat_kl_loss"], te["x_hat_recon_loss"] + te["x_hat_kl_loss"],
                                   tr["total_kl_loss"], te["total_kl_loss"]))
+            if int(config.get("iw_samples") or 0) > 0:
+                from . import iw
+                print(iw.report_line(config.iw_samples, iw.evaluate(model, test_dataset, config.iw_samples)))
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             # vae/trainer.py:405-414 resets x_recon / x_kl / total_kl but never the x_hat_* means
             metrics.reset_states(["x_recon_loss", "x_kl_loss", "total_kl_loss"])
