@@ -108,6 +108,15 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // numerically stable helpers used by the ELBO kernels
 __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x))); }
+// softplus'(a) = sigmoid(a) from the stored OUTPUT s = softplus(a): 1 - exp(-s).  Below s = 0.25 the difference cancels (6e-5 relative at a = -7, 2 % at a = -12,
+// exactly 0 below a = -16.6, while the factor in front of it holds -kl_scale / sigma), so it is taken as -expm1f(-s) there; from 0.25 up the plain difference is good
+// to 2e-7 (half an ulp of exp(-s) <= 3e-8 over 1 - exp(-0.25) = 0.22) and is kept as it was: steps whose sigma stay there, as a step from initialisation does,
+// keep their bits.  (dlogistic.hip.h switches the same expression at the same point.)
+__device__ __forceinline__ float softplus_der_from_out(float s) {
+  float d = 1.f - expf(-s);
+  if (s < 0.25f) d = -expm1f(-s);                     // (a branch, not a select: a wave without a small sigma skips it)
+  return d;
+}
 __device__ __forceinline__ float sigmoid_f(float x) {
   // 1/(1+exp(-x)) without overflow for large |x|
   float e = __expf(-fabsf(x));

@@ -189,7 +189,8 @@ __global__ __launch_bounds__(256) void gm_head_fwd_kernel(const float* a_m, cons
   if (lane == 0) kl2[b] = acc;
 }
 
-// adjoint of the heads: dL/dz from the decoder plus c = beta/B times d kl2; through softplus via sigmoid(a) = 1 - exp(-softplus(a))
+// adjoint of the heads: dL/dz from the decoder plus c = beta/B times d kl2; through softplus via sigmoid(a) = 1 - exp(-softplus(a)),
+// without the cancellation of that difference at small sigma (softplus_der_from_out, common.hip.h)
 __global__ __launch_bounds__(256) void gm_head_bwd_kernel(const float* dz, int lddz, const float* zm, const float* zs, const float* pm,
                                                           const float* ps, const float* eps, float c, void* g_am, void* g_as,
                                                           void* g_apm, void* g_aps, int g_dtype, int B, int L) {
@@ -203,9 +204,9 @@ __global__ __launch_bounds__(256) void gm_head_bwd_kernel(const float* dz, int l
     const float gm2 = -c * d * is2;
     const float gs2 = c * (1.f / s2 - (s * s + d * d) * is2 / s2);
     st_dt(g_am, g_dtype, i, gm);
-    st_dt(g_as, g_dtype, i, gs * (1.f - expf(-s)));
+    st_dt(g_as, g_dtype, i, gs * softplus_der_from_out(s));
     st_dt(g_apm, g_dtype, i, gm2);
-    st_dt(g_aps, g_dtype, i, gs2 * (1.f - expf(-s2)));
+    st_dt(g_aps, g_dtype, i, gs2 * softplus_der_from_out(s2));
   }
 }
 

@@ -419,7 +419,7 @@ __global__ __launch_bounds__(256) void reparam_kl_bwd_kernel(
     const float mu = z_mean[i], sg = z_sig[i], e = eps[i];
     const float dmu = g + kl_scale * mu;
     const float dsg = g * e + kl_scale * (sg - 1.f / sg);
-    const float dpre = dsg * (1.f - expf(-sg));          // softplus'(pre) = 1 - exp(-softplus(pre))
+    const float dpre = dsg * softplus_der_from_out(sg);  // softplus'(pre) = 1 - exp(-softplus(pre)), without its cancellation at small sigma
     g_pre[(int64_t)b * 2 * L + j] = from_f32<TG>(dmu);
     g_pre[(int64_t)b * 2 * L + L + j] = from_f32<TG>(dpre);
   }
@@ -458,7 +458,7 @@ __global__ __launch_bounds__(256) void reparam_kl_bwd_twin_kernel(const ReparamB
     const float mu = g.z_mean[i], sg = g.z_sig[i], e = g.eps[i];
     const float dmu = gg + kl_scale * mu;
     const float dsg = gg * e + kl_scale * (sg - 1.f / sg);
-    const float dpre = dsg * (1.f - expf(-sg));          // as reparam_kl_bwd_kernel
+    const float dpre = dsg * softplus_der_from_out(sg);  // as reparam_kl_bwd_kernel
     g_pre[(int64_t)b * 2 * L + j] = from_f32<TG>(dmu);
     g_pre[(int64_t)b * 2 * L + L + j] = from_f32<TG>(dpre);
   }

@@ -68,8 +68,8 @@ __device__ __forceinline__ float un_fwd(int op, float v, float p0, float p1) {
 __device__ __forceinline__ float un_der(int op, float y, float p0, float p1) {
   switch (op) {
     case SV_TAPE_RELU: return y > 0.f ? 1.f : 0.f;
-    case SV_TAPE_SIGMOID: return y * (1.f - y);
-    case SV_TAPE_SOFTPLUS: return 1.f - __expf(-y);          // softplus'(a) = sigmoid(a) = 1 - exp(-softplus(a))
+    case SV_TAPE_SIGMOID: return y * (1.f - y);              // (1 - y loses relative accuracy only where y > 1 - 1e-4: the derivative is below 1e-4 there)
+    case SV_TAPE_SOFTPLUS: return y < 0.25f ? -expm1f(-y) : 1.f - __expf(-y);   // softplus'(a) = sigmoid(a) = 1 - exp(-softplus(a)); small y: as softplus_der_from_out
     case SV_TAPE_CLAMP: return (y > p0 && y < p1) ? 1.f : 0.f;
     case SV_TAPE_SCALE: return p0;
     default: return 1.f;

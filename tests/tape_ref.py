@@ -564,6 +564,31 @@ CASES["unary_rep3"] = _unary_rep(3, 3, 7)
 CASES["unary_rep16"] = _unary_rep(16, 2, 65)
 
 
+@case("unary_softplus_small_sigma")
+def _softplus_small_sigma():
+    """SOFTPLUS (p0 = -1) on pre-activations in (-14, -7): sig from 9e-4 down to 8e-7, where its adjoint taken as 1 - exp(-sig) is a cancelling difference (6e-5 relative
+    at -7, 13 % at -14; the float32 twin differentiates with a true sigmoid).  Out of place and in place, each next to a block at (-3, 5); the small block has a tensor
+    of its own, so its gradient's relative error is not measured against the other block's norm."""
+    B, rows = 2, 66
+    g = Graph(B)
+    small = g.tensor(rows, 8, 8, init=uniform(-13.0, -6.0))
+    wide = g.tensor(rows, 8, 8, init=uniform(-2.0, 6.0))
+    mu = g.tensor(rows, 8, 8)
+    y = g.tensor(rows, 8, 8)
+    g.unary(SOFTPLUS, small, y, 4, xo=0, yo=0, p0=-1.0)
+    g.unary(SOFTPLUS, wide, y, 4, xo=0, yo=4, p0=-1.0)
+    g.loss(1, mu, 0, y, 0, 8, 0.7)
+    zs = g.tensor(rows, 5, 8)
+    zw = g.tensor(rows, 5, 8)
+    g.unary(COPY, small, zs, 5, xo=3)
+    g.unary(COPY, wide, zw, 5, xo=3)
+    g.unary(SOFTPLUS, zs, zs, 4, xo=1, yo=1, p0=-1.0)
+    g.unary(SOFTPLUS, zw, zw, 4, xo=1, yo=1, p0=-1.0)
+    g.loss(1, mu, 0, zs, 1, 4, -1.3)
+    g.loss(1, mu, 4, zw, 1, 4, 0.9)
+    return g
+
+
 def _group(parts, rows, lanes=None, no_grad_part=None):
     """a concat group of `parts` column blocks (widths 1, 5, 13, ...) with mixed ops from `parts` sources into one tensor; 11 parts: the 8-part cut falls inside"""
     def build():

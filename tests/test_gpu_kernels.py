@@ -168,6 +168,32 @@ def test_reparam_kl_fwd_bwd(ops):
     g = ops.reparam_kl_bwd(torch.from_numpy(dz).cuda(), z_mean, z_sig, eps_out, beta / B, g_dtype=torch.float32,
                            dz2=torch.from_numpy(dz2).cuda())
     torch.testing.assert_close(g.cpu().double(), pt.grad, rtol=2e-4, atol=2e-5)
+    # a second input set: sigma pre-activations (bias included) pinned at -7, -9, -11 and -14 on whole rows -- sigma from 9e-4 down to 8e-7, where softplus' taken
+    # as 1 - exp(-sigma) is a cancelling difference (6e-5 relative at -7, 13 % at -14) in front of -kl_scale / sigma.  Element by element:
+    # |gpu - ref| <= 1e-4 |ref| + 1e-5 * the largest |addend| of the element in the float64 reference (the rule of tests/test_gpu_gm_pointwise.py)
+    pins = (-7.0, -9.0, -11.0, -14.0)
+    pre2 = pre.copy()
+    for k, v in enumerate(pins):
+        pre2[k, L:] = v - bias[L:]
+    z_mean, z_sig, z, _, kl, eps_out = ops.reparam_kl_fwd(torch.from_numpy(pre2).cuda(), torch.from_numpy(bias).cuda(), torch.from_numpy(eps).cuda(),
+                                                          z_dtype=torch.float32)
+    pt = torch.from_numpy(pre2).double().requires_grad_(True)
+    et, gt, ks = torch.from_numpy(eps).double(), torch.from_numpy(dz + dz2).double(), beta / B
+    mu = pt[:, :L] + bt[:L]
+    sg = F.softplus(pt[:, L:] + bt[L:], threshold=1e9)
+    assert float(sg.min()) >= 5e-7 and float(sg[3].max()) < 1e-6
+    kl_ref = -0.5 * torch.sum(1 + torch.log(sg ** 2) - mu ** 2 - sg ** 2, dim=1)
+    ((mu + sg * et) * gt).sum().add(beta * kl_ref.mean()).backward()
+    with torch.no_grad():
+        scale = torch.cat([torch.maximum(gt.abs(), ks * mu.abs()),
+                           torch.maximum(torch.maximum((gt * et).abs(), ks * sg), ks / sg) * torch.sigmoid(pt[:, L:] + bt[L:])], dim=1)
+    torch.testing.assert_close(z_sig.cpu().double(), sg.detach(), rtol=F32_RTOL, atol=0)
+    g = ops.reparam_kl_bwd(torch.from_numpy(dz).cuda(), z_mean, z_sig, eps_out, ks, g_dtype=torch.float32, dz2=torch.from_numpy(dz2).cuda()).cpu().double()
+    err = (g - pt.grad).abs()
+    for k, v in enumerate(pins):
+        print("reparam_kl_bwd, row pinned at %+.0f: worst rel %.3e" % (v, float((err[k, L:] / pt.grad[k, L:].abs()).max())))
+    bound = F32_RTOL * pt.grad.abs() + 1e-5 * scale
+    assert bool((err <= bound).all()), "worst err / bound %.3f" % float((err / bound).max())
 
 
 def test_reparam_philox_normal(ops):

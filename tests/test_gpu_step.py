@@ -435,3 +435,44 @@ def test_encoder_backward_without_the_decoders_sees_zero_dz(lib_built):
     gm, gs = g["encoder_x_hat/e4_mean/bias"].double(), g["encoder_x_hat/e4_sd/bias"].double()
     assert float((gm - want_mean).abs().max()) <= 2e-2 * float(want_mean.abs().max()) + 1e-6
     assert float((gs - want_sd).abs().max()) <= 2e-2 * float(want_sd.abs().max()) + 1e-6
+
+
+@pytest.mark.gpu
+def test_encoder_head_adjoint_at_small_sigma(lib_built):
+    """reparam_kl_bwd_twin_kernel is reached only through the plan.  The phase sequence of the test above on an fp32 model, with encoder_x_hat's sigma-head bias
+    at -8, -10, -12 and -14 on four 8-wide bands of latent dimensions (sigma 3e-4 .. 8e-7; the other 96 dimensions stay at the initial 0).  With dz = 0 the bias
+    gradient is sum_b ks (sigma - 1 / sigma) softplus', softplus' = -expm1(-sigma), computed here in float64 from the plan's z_sig_xh.  Every band is held to
+    1e-4 of ITS OWN maximum: taken as 1 - exp(-sigma), softplus' is 2 % off on the -12 band, which the maximum of the unpinned dimensions would hide."""
+    import torch
+    from split_vae_amd import data, trainer
+    from split_vae_amd._lib import PHASE_PREP, PHASE_FORWARD, PHASE_LOSS, PHASE_BWD_ENC_HEADS, PHASE_BWD_ENC_CONVS
+    from split_vae_amd.augmentation import Augmentator
+    from split_vae_amd.model import LGVae
+    from split_vae_amd.optimizer import Adam
+    B, H, L = 8, 32, 128
+    x = data.synthetic_images(B, H, H, seed=0, device="cuda")
+    img = Augmentator("scramble", size=8, seed=1).augment(x)
+    m = LGVae(L, L, image_shape=[-1, H, H, 3], dtype="f32", device=torch.device("cuda"), seed=3)
+    m.beta = 120.0
+    bands = {-8.0: slice(0, 8), -10.0: slice(8, 16), -12.0: slice(16, 24), -14.0: slice(24, 32), 0.0: slice(32, L)}
+    off = {n: o for n, o, _ in m.param_table}["encoder_x_hat/e4_sd/bias"]
+    for v, sl in bands.items():
+        m.flat[off + sl.start:off + sl.stop] = v
+    opt = Adam(learning_rate=1e-4)
+    for _ in range(2):
+        plan = trainer.train_step(m, img, opt)
+    plan.step(PHASE_PREP | PHASE_FORWARD | PHASE_LOSS, params=m.flat, grads=m.grad_flat, images6=img, seed=m.seed, step=7)
+    plan.step(PHASE_BWD_ENC_HEADS | PHASE_BWD_ENC_CONVS, params=m.flat, grads=m.grad_flat, images6=img, seed=m.seed, step=7)
+    torch.cuda.synchronize()
+    zs = plan.buffer("z_sig_xh", torch.float32, (B, L)).double()
+    ks = m.beta / B
+    want = (ks * (zs - 1.0 / zs) * -torch.expm1(-zs)).sum(0)
+    got = {n: t for (n, _, _), t in zip(m.param_table, m.gradients)}["encoder_x_hat/e4_sd/bias"].double()
+    assert float(zs[:, bands[-14.0]].max()) < 2e-6 and float(zs[:, bands[-8.0]].max()) < 1e-3 and float(zs.min()) >= 5e-7
+    bad = []
+    for v, sl in bands.items():
+        err, top = float((got[sl] - want[sl]).abs().max()), float(want[sl].abs().max())
+        print("e4_sd/bias gradient, band at %+.0f: worst |err| / max |want| %.3e" % (v, err / top))
+        if not err <= 1e-4 * top:
+            bad.append((v, err / top))
+    assert not bad, bad
