@@ -689,6 +689,37 @@ int sv_iw_advance(const float* z_mean_x, const float* z_sig_x, const float* z_me
  * zero it once per test set, read it back once.  SV_E_BADARG: state or out3 NULL, K or B <= 0. */
 int sv_iw_finish(const double* state, int32_t K, float* out3, double* acc, int32_t B, void* stream);
 
+/* ---------------------------------------------------------------- k-NN label probe of the latents (csrc/knn.hip)
+ * No reference counterpart: the probe classifier of vae/trainer.py:81-97 needs a weights blob that is missing upstream.  This is
+ * the parameter-free representation metric instead: classify each query latent q [Nq, L] (row pitch ldq) by the majority label of
+ * its k nearest reference latents r [Nr, L] (row pitch ldr, classes r_class [Nr] uint8).  fp32 only; ALL INPUTS ARE FINITE --
+ * a NaN or Inf in q or r is the caller's error (the order below is not total then).
+ *   norm         n(v) = sum_j v_j^2 in fp32, per row, computed once per row in a pre-pass in one fixed order (lane l of a wave
+ *                sums j = l, l + 64, ... in ascending j, then the 64-lane xor butterfly 32, 16, ..., 1): it does not depend on
+ *                where the row lies;
+ *   distance     d(q, r) = max(0, (n(q) + n(r)) - 2 (q . r)), fp32 operations in that order; the dot product runs over the whole
+ *                of L in ascending order on v_mfma_f32_16x16x4_f32 (exact fp32 fma chain, L zero-padded to a multiple of 32): no
+ *                split over L, no atomics.  d(q, r) is therefore bit-identical whatever Nq, Nr, the rows' positions or the
+ *                chunking;
+ *   neighbours   the k references smallest under the total order (d, reference index): equal fp32 distances go to the lower
+ *                index; reported in ascending order: nn_index [Nq, k] int32, nn_dist [Nq, k] fp32 (either may be NULL);
+ *   prediction   pred [Nq] int32 = the class with the most votes among the k neighbours' r_class; vote ties go to the lowest
+ *                class id: a function of the neighbour SET only.  Classes >= n_class get no votes.
+ *   acc          (may be NULL) int64 [2] += (number of queries with pred == q_class, Nq); q_class NULL: only the count is added.
+ *                Integer atomics: the sums do not depend on the order.  Zero it once per test set, read it back once.
+ * The references are cut into chunks of sv_knn_chunk_rows() rows; a tile kernel leaves one sorted k-list per (query, chunk) in
+ * the workspace and a second kernel merges them per query in chunk order.  The workspace (sv_knn_workspace_bytes; 16-byte aligned)
+ * may hold anything on entry.  Everything is enqueued on `stream`; no host synchronisation.
+ * Accepted domain: Nq >= 1, 1 <= k <= 32, k <= Nr <= 65535 chunks, 1 <= L <= 512, ldq, ldr >= L, 2 <= n_class <= 64: anything
+ * else SV_E_UNSUPPORTED; a null q / r / r_class / pred / workspace or a misaligned pointer (4 bytes; acc 8; workspace 16):
+ * SV_E_BADARG; workspace_bytes below sv_knn_workspace_bytes: SV_E_WORKSPACE.  All checked before anything is enqueued. */
+int sv_knn_chunk_rows(void);     /* reference rows per chunk of the tile kernel: lets callers and tests size Nr */
+int sv_knn_workspace_bytes(int32_t Nq, int32_t Nr, int32_t k, int64_t* bytes);
+int sv_knn_classify(const float* q, int32_t ldq, const float* r, int32_t ldr, const uint8_t* r_class, int32_t Nq, int32_t Nr,
+                    int32_t L, int32_t k, int32_t n_class, int32_t* nn_index /* [Nq,k] or NULL */,
+                    float* nn_dist /* [Nq,k] or NULL */, int32_t* pred /* [Nq] */, const uint8_t* q_class /* or NULL */,
+                    int64_t* acc /* [2]: hits, count; ADDED to; or NULL */, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- SPLIT-SPAIR: Dense layers, exact fp32 on the matrix cores
  * tf.keras.layers.Dense (spair/spair.py:135-154, :185-202, :246-273, :341-366, :424-467) for ANY fan-in / fan-out, reading the Keras
  * [in, out] kernel as it lies in the variable buffer (dense_f32.hip).  x [M, ldx], y / dy [M, ldy], w [K, N] row-major.

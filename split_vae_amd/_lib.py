@@ -19,6 +19,7 @@ PHASE_NO_RECON = 256      # modifier: the fused-loss training step does not stor
 PHASE_BUCKET_EVENTS = 1024  # modifier: record the gradient-bucket events of the data-parallel step (include/splitvae.h)
 PHASE_INFER = PHASE_PREP | PHASE_FORWARD
 IW_ACCUMULATE, IW_DRAW = 1, 2      # sv_iw_advance flags (include/splitvae.h)
+KNN_MAX_K, KNN_MAX_L, KNN_MAX_CLASSES = 32, 512, 64      # accepted domain of sv_knn_classify (include/splitvae.h)
 
 STATUS = {0: "SV_OK", -1: "SV_E_BADARG", -2: "SV_E_UNSUPPORTED", -3: "SV_E_WORKSPACE", -4: "SV_E_STATE"}
 STATUS_BADARG, STATUS_UNSUPPORTED, STATUS_WORKSPACE, STATUS_STATE = -1, -2, -3, -4
@@ -225,6 +226,9 @@ SYMBOLS = {
     "sv_lgvae_profile_read_issued": (C.c_int, [_vp, _i32, _vp]),
     "sv_iw_advance": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _i64, _i32, _vp]),
     "sv_iw_finish": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp]),
+    "sv_knn_chunk_rows": (C.c_int, []),
+    "sv_knn_workspace_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "sv_knn_classify": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

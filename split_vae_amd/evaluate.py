@@ -1,38 +1,56 @@
-"""Measure a saved SPLIT-VAE (LGVae) without training: the importance-weighted test log-likelihood of split_vae_amd/iw.py.
+"""Measure a saved model without training: the importance-weighted test log-likelihood of split_vae_amd/iw.py (LGVae) and / or
+the k-NN label probe of the latents of split_vae_amd/probe.py (every model).
 
     python -m split_vae_amd.evaluate --weights models/20260101-120000.h5 --dataset svhn --iw_samples 64 -no_label
+    python -m split_vae_amd.evaluate --weights models/20260101-120000.h5 --dataset svhn --knn_probe 5
 
 Takes the flags of split_vae_amd.main (the model's latent widths, --dataset, --batch_size, --dtype, --data_dir, --synthetic,
 --seed, --patch_size / --augmentation for the x_hat half of the test batches) plus --weights; builds the model, loads the .h5 /
-.npz file, runs iw.evaluate over the test set and prints the line the training loop prints with --iw_samples.
+.npz file, runs iw.evaluate and / or probe.knn_probe over the test set and prints the lines the training loop prints with
+--iw_samples / --knn_probe.  The probe loads the labels and the training split (its first --knn_refs images are the references).
 """
-from .main import build_parser, check_augmentation, make_augmentors, make_model
+from .main import build_parser, check_augmentation, make_augmentors, make_model, make_probe_references
 from .utils import dotdict
 
 
 def main(argv=None):
     ap = build_parser()
-    ap.description = "Importance-weighted test log-likelihood of a saved SPLIT-VAE (LGVae) weights file"
+    ap.description = "Importance-weighted test log-likelihood (LGVae) and k-NN latent label probe of a saved weights file"
     ap.add_argument("--weights", type=str, required=True, help="file written by save_weights (.h5 / .hdf5 / .keras, else .npz)")
     args = ap.parse_args(argv)
-    from . import iw
-    if args.iw_samples <= 0:
-        raise SystemExit("--iw_samples K: the number of importance samples per image (K >= 1)")
+    from . import iw, probe
     iw.check_model_name(args.model, args.iw_samples)     # before any data or device work
+    if args.iw_samples <= 0 and args.knn_probe == 0:
+        raise SystemExit("nothing to measure: pass --iw_samples K (importance samples per image, K >= 1) and / or --knn_probe K "
+                         "(neighbours of the latent label probe, 1 <= K <= 32)")
+    probe.check_flags(args.knn_probe, args.knn_refs, args.no_label)
     from . import configure_hw_queues
     configure_hw_queues()                                # before the first HIP call (split_vae_amd/__init__.py)
     config = dotdict(vars(args))
-    config.label = False
+    config.label = bool(args.knn_probe)
     check_augmentation(config.augmentation, args.model)
     from . import data
     _, test_augmentor = make_augmentors(config)
-    _, test_ds, input_shape = data.get_dataset(config.dataset, config.batch_size, synthetic=config.synthetic, data_dir=config.data_dir,
-                                               get_label=False)
-    test_batches = (test_augmentor.augment(x) for x in test_ds)      # the test batches of main(): the augmentor's first calls
+    train_ds, test_ds, input_shape = data.get_dataset(config.dataset, config.batch_size, synthetic=config.synthetic,
+                                                      data_dir=config.data_dir, get_label=config.label)
+    if config.label and not train_ds.labelled:
+        print(probe.SKIPPED)
+        config.label, config.knn_probe = False, 0
+    if config.label:
+        test_batches = [(test_augmentor.augment(x), y) for x, y in test_ds]      # the test batches of main(): the augmentor's first calls
+    else:
+        test_batches = (test_augmentor.augment(x) for x in test_ds)
     model, _ = make_model(args.model, config, input_shape)
     model.load_weights(args.weights)
-    res = iw.evaluate(model, test_batches, config.iw_samples)
-    print(iw.report_line(config.iw_samples, res))
+    res = {}
+    if config.iw_samples > 0:
+        res = iw.evaluate(model, test_batches, config.iw_samples)
+        print(iw.report_line(config.iw_samples, res))
+    if config.knn_probe:
+        refs = make_probe_references(train_ds, config)
+        pr = probe.knn_probe(model, refs, test_batches, config.knn_probe)
+        print(probe.report_line(pr))
+        res = dict(res, knn_acc_g=pr["acc_g"], knn_acc_l=pr["acc_l"])
     return res
 
 

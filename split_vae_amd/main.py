@@ -4,7 +4,7 @@
     python -m split_vae_amd.main --model gmvae --beta 40 --patch_size 4       (GMVAE baseline, Table 2)
 
 Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout, --mix_per_image,
---resident_data, --iw_samples.
+--resident_data, --iw_samples, --knn_probe, --knn_refs.
 """
 import argparse
 
@@ -48,6 +48,12 @@ def build_parser():
     ap.add_argument("--iw_samples", type=int, default=0,
                     help="K > 0: after the report of every evaluation, the K-sample importance-weighted bound of the test log-likelihood "
                          "(joint and x-only, nats) and the bits per dimension of x (split_vae_amd/iw.py); --model lgvae only")
+    ap.add_argument("--knn_probe", type=int, default=0,
+                    help="K > 0: after the report of every evaluation, the accuracy of a K-nearest-neighbour classifier of the test "
+                         "set's latent means over --knn_refs training images, for z_g and z_l separately (split_vae_amd/probe.py); "
+                         "needs labels; K <= 32")
+    ap.add_argument("--knn_refs", type=int, default=20000,
+                    help="--knn_probe: the number of reference images, the first N of the training set in file order")
     return ap
 
 
@@ -72,6 +78,23 @@ def make_augmentors(config):
     train = ReferenceAugmentator(pipeline=0, **kw)
     test = ReferenceAugmentator(pipeline=1, **kw) if config.augmentation == 'mix_scramble' else train
     return train, test
+
+
+def make_probe_references(train_ds, config):
+    """--knn_probe: the reference batches, from the training set as data.get_dataset returned it (before main wraps it), through an
+    augmentor of the probe's own (the test pipeline's settings)."""
+    from . import probe
+    from .augmentation import ReferenceAugmentator
+    n_train = train_ds.N if hasattr(train_ds, "N") else train_ds.x.shape[0]
+    n = int(config.knn_refs)
+    if n > n_train:
+        print('Note: --knn_refs %d clipped to the training set\'s %d images' % (n, n_train))
+        n = n_train
+    if n < int(config.knn_probe):
+        raise SystemExit("--knn_probe %d: the training set has only %d images" % (config.knn_probe, n))
+    aug = ReferenceAugmentator(type=config.augmentation, size=config.patch_size, seed=config.seed,
+                               per_image=bool(config.get("mix_per_image")), pipeline=1)
+    return probe.reference_batches(train_ds, n, aug, config.batch_size)
 
 
 def make_model(model_name, config, input_shape):
@@ -104,6 +127,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     from .iw import check_model_name
     check_model_name(args.model, args.iw_samples)    # before any data or device work
+    from .probe import check_flags
+    check_flags(args.knn_probe, args.knn_refs, args.no_label)
     from . import configure_hw_queues
     configure_hw_queues()                            # before the first HIP call (split_vae_amd/__init__.py)
     config = dotdict(vars(args))
@@ -126,6 +151,14 @@ def main(argv=None):
         # vae/trainer.py:81-97 trains / loads the SVHN probe classifier here; its weights blob is missing upstream
         # (.MISSING_LARGE_BLOBS:1), so the labels ride along unused and the classifier metrics are not reported
         print('Note: classifier-based test metrics are not available (svhn_classifier_weights.h5 is not in the reference repo)')
+    if config.knn_probe:
+        config.knn_ref_batches = None
+        if not config.label:
+            from . import probe
+            print(probe.SKIPPED)
+            config.knn_probe = 0
+        else:
+            config.knn_ref_batches = make_probe_references(train_ds, config)
     if resident:
         # the test batches first, as below: the augmentor's Philox call indices, hence every permutation, match a run without the flag
         test_batches = [(test_augmentor.augment_from(test_ds, i), test_ds.one_hot(i)) if config.label else test_augmentor.augment_from(test_ds, i)

@@ -721,6 +721,56 @@ def iw_finish(state, K, out3=None, acc=None):
     return out3
 
 
+# ------------------------------------------------------------------ k-NN label probe of the latents (include/splitvae.h)
+def knn_chunk_rows():
+    return int(_lib.load().sv_knn_chunk_rows())
+
+
+def knn_workspace_bytes(Nq, Nr, k):
+    n = C.c_int64()
+    check(_lib.load().sv_knn_workspace_bytes(int(Nq), int(Nr), int(k), C.byref(n)), "sv_knn_workspace_bytes")
+    return n.value
+
+
+def _rows_f32(t, name):
+    if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise ValueError("%s must be a 2-D fp32 device tensor with contiguous rows (a row pitch >= its width is allowed)" % name)
+    return C.c_void_p(t.data_ptr()), int(t.stride(0))
+
+
+def _classes_u8(t, n, name):
+    if not torch.is_tensor(t) or t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (n,):
+        raise ValueError("%s must be a contiguous uint8 device tensor of %d class ids" % (name, n))
+    return C.c_void_p(t.data_ptr())
+
+
+def knn_classify(q, r, r_class, k, n_class, q_class=None, acc=None, want_neighbours=False, workspace=None):
+    """sv_knn_classify: pred [Nq] int32 = the majority class among the k references of r [Nr,L] nearest to each row of q [Nq,L]
+    (squared Euclidean distance, ties to the lower index / class).  q_class [Nq] uint8 and acc [2] int64 (device): acc += (hits,
+    Nq).  want_neighbours: returns (pred, nn_index [Nq,k] int32, nn_dist [Nq,k] fp32).  workspace: a uint8 device tensor of at
+    least knn_workspace_bytes(Nq, Nr, k) bytes with any contents (default: allocated here)."""
+    qp, ldq = _rows_f32(q, "q")
+    rp, ldr = _rows_f32(r, "r")
+    Nq, L = q.shape
+    Nr = r.shape[0]
+    if r.shape[1] != L or r.device != q.device:
+        raise ValueError("q [%d,%d] and r [%d,%d] must have one width and one device" % (Nq, L, Nr, r.shape[1]))
+    rc = _classes_u8(r_class, Nr, "r_class")
+    qc = None if q_class is None else _classes_u8(q_class, Nq, "q_class")
+    if acc is not None and (acc.dtype != torch.int64 or not acc.is_cuda or not acc.is_contiguous() or acc.numel() < 2):
+        raise ValueError("acc must be a contiguous int64 device tensor of >= 2 elements")
+    pred = torch.empty((Nq,), dtype=torch.int32, device=q.device)
+    nn_i = torch.empty((Nq, int(k)), dtype=torch.int32, device=q.device) if want_neighbours else None
+    nn_d = torch.empty((Nq, int(k)), dtype=torch.float32, device=q.device) if want_neighbours else None
+    nbytes = knn_workspace_bytes(Nq, Nr, k)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous():
+        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    check(_lib.load().sv_knn_classify(qp, ldq, rp, ldr, rc, Nq, Nr, L, int(k), int(n_class), _p(nn_i), _p(nn_d), _p(pred), qc, _p(acc),
+                                      _p(ws), ws.numel(), _stream()), "sv_knn_classify")
+    return (pred, nn_i, nn_d) if want_neighbours else pred
+
+
 # ------------------------------------------------------------------ A9 SPLIT-GMVAE glue (vae/model.py:48-79,:116-135)
 ACT ={None: _lib.SV_ACT_NONE, "relu": _lib.SV_ACT_RELU, "elu": _lib.SV_ACT_ELU}
 

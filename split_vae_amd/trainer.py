@@ -213,6 +213,7 @@ def train_local_global_autoencoder(model, optimizer, dataset, train_dataset, tes
             if int(config.get("iw_samples") or 0) > 0:
                 from . import iw
                 print(iw.report_line(config.iw_samples, iw.evaluate(model, test_dataset, config.iw_samples)))
+            _knn_probe_report(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             # vae/trainer.py:405-414 resets x_recon / x_kl / total_kl but never the x_hat_* means
             metrics.reset_states(["x_recon_loss", "x_kl_loss", "total_kl_loss"])
@@ -221,6 +222,21 @@ def train_local_global_autoencoder(model, optimizer, dataset, train_dataset, tes
             print('Training done!')
             break
     return _save(model, RUN_NAME)
+
+
+def _knn_probe_report(model, test_dataset, config, step):
+    """--knn_probe K: the k-NN label probe of the latent means (probe.py) behind an evaluation's report.  The loops return the path
+    of the saved weights, so the figures are kept in config.knn_history: one dict(step, knn_acc_g, knn_acc_l) per evaluation."""
+    k = int(config.get("knn_probe") or 0)
+    if k <= 0 or not config.label or not config.get("knn_ref_batches"):
+        return None
+    from . import probe
+    res = probe.knn_probe(model, config.knn_ref_batches, test_dataset, k)
+    print(probe.report_line(res))
+    if config.get("knn_history") is None:
+        config.knn_history = []
+    config.knn_history.append(dict(step=step, knn_acc_g=res["acc_g"], knn_acc_l=res["acc_l"]))
+    return res
 
 
 def _save(model, run_name):
@@ -292,6 +308,7 @@ def _train_lggmvae(model, optimizer, train_dataset, test_dataset, config):
                       '{}Y KL loss: {:.4f}'.format(tag, v[0], tag, v[1], tag, v[2], tag, v[3], tag, v[4]))
             if cluster is not None:
                 print('            Classifier cluster acc: {:.4f}'.format(cluster.result()))
+            _knn_probe_report(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             acc, n_acc = None, 0
             start = time.time()
@@ -347,6 +364,7 @@ def _train_gmvae(model, optimizer, train_dataset, test_dataset, config):
             if cluster is not None:
                 print('            Classifier cluster acc: {:.4f}'.format(cluster.result()))
             print('            Y KL train loss: {:.4f}, Y KL test loss: {:.4f}'.format(tr[2], te[2]))
+            _knn_probe_report(model, test_dataset, config, step)
             acc, n_acc = None, 0
             start = time.time()
         if step >= config.training_steps:
