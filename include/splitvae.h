@@ -733,6 +733,79 @@ int sv_dense_f32_dgrad(const float* dy, int32_t ldy, const float* w, float* dx, 
 int sv_dense_f32_wgrad(const float* x, int32_t ldx, const float* dy, int32_t ldy, float* dw, float* dbias, int32_t M, int32_t K,
                        int32_t N, void* stream);
 
+/* ---------------------------------------------------------------- the latent block's kernels, one by one (csrc/latent_gemm.hip)
+ * Direct access for tests and host bindings to the kernels sv_lgvae_step runs between the encoder convs and the decoder convs: the Dense
+ * layers e4_mean | e4_sd (vae/model.py:41-42) and d1 (:152), their input and weight gradients, and the twin Sampling + KL kernels that read
+ * the GEMMs' K-slice slabs.  Thin wrappers: they add no kernel and no launch of the step goes through them.  Every argument is checked before
+ * anything is enqueued; a refused call leaves every buffer untouched.  `dtype` is the sv_dtype of the operands (SV_BF16: bf16 operands, fp32
+ * accumulate; SV_F32: exact fp32 products and sums).  All of a launch's problems share it.
+ *
+ * sv_latent_nt_gemm: out [M, N] = A [M, K] . W^T for n = 1 or 2 problems in one launch.  A [M][lda] and the weight image W [N][ldw] are
+ *   K-contiguous, in `dtype`.
+ *   out_f32 = 0 (needs splitk = 1): out [M][ldo] in `dtype` = gate(act(product + bias)); bias [N] fp32 or NULL, act SV_ACT_NONE | SV_ACT_RELU,
+ *     mask [M][ldo] in `dtype` or NULL: elements whose mask is not > 0 are stored as zero (ReluGrad of the tensor the gradient lands on).
+ *   out_f32 = 1: out = fp32 slabs [splitk][M][ldo], slab s at out + s * slab_stride floats = the product over K slice s alone; bias, act and
+ *     mask are ignored (they belong to the consumer of the summed slabs).
+ *   splitk = 0 on entry: replaced by sv_latent_nt_pick_splitk(M, N, K, n), the plan's choice; on return p[i].splitk is what ran.
+ *   bm = 64 | 128 rows per tile (the plan: 128 from B >= 256 for typed outputs, 64 for slabs).  *form (may be NULL) = the kernel that was
+ *     launched: 0 = nt_gemm_kernel (one LDS slot), 1 = nt_gemm_ring_kernel (three slots; bm = 64, every problem out_f32 with slices of two
+ *     or more phases, a phase being 128 (bf16) or 64 (fp32) of K).
+ *   Rows >= M, columns [N, ldo) and everything behind the last slab are not written.
+ *   SV_E_BADARG: p NULL, n outside 1..2, bm not 64 | 128, a dtype outside sv_dtype, a null A / W / out, M < 1, lda or ldw < K, ldo < N,
+ *     splitk < 0, an act outside NONE | RELU.  SV_E_UNSUPPORTED: N or the K of a slice no multiple of 128 (N) / a phase (K), K % splitk != 0,
+ *     lda / ldw no multiple of the elements of 16 bytes, ldo % 4 != 0, A / W / out / bias / mask not 16-byte aligned, splitk > 1 without
+ *     out_f32 (every slice would store its own partial product over the others'), out_f32 with a slab_stride that is no multiple of 4 floats
+ *     or below M * ldo (slabs would overlap). */
+typedef struct {
+  const void* A; int32_t lda;
+  const void* W; int32_t ldw;
+  void* out; int32_t ldo;
+  const float* bias;
+  const void* mask;
+  int32_t M, N, K, act, splitk, out_f32;
+  int64_t slab_stride;
+} sv_latent_nt_prob;
+int sv_latent_nt_gemm(sv_latent_nt_prob* p, int32_t n, int32_t dtype, int32_t bm, int32_t* form, void* stream);
+/* K slices the plan gives a big-K layer of `nprob` problems per launch (host logic, no device): 1 <= s <= K / 128, K % s == 0,
+ * (K / s) % 128 == 0; 1 for a shape the kernels do not take. */
+int32_t sv_latent_nt_pick_splitk(int32_t M, int32_t N, int32_t K, int32_t nprob);
+/* out [M][ldo] = 0.f + slab 0 + slab 1 + ... + slab S-1 in fp32, in that order, for n = 1 or 2 problems in one launch (all M * ldo floats
+ * of a slab are read).  SV_E_BADARG: a null pointer, n outside 1..2, S < 1, M < 1, ldo < 1; SV_E_UNSUPPORTED: ldo or slab_stride no
+ * multiple of 4 floats, a pointer not 16-byte aligned. */
+typedef struct { const float* slabs; float* out; int32_t S, M, ldo; int64_t slab_stride; } sv_latent_reduce_prob;
+int sv_latent_nt_slab_reduce(const sv_latent_reduce_prob* p, int32_t n, void* stream);
+/* Weight gradients dW [Kw, N] = X^T . dY (rows [0, Kw_real) stored, row pitch N; ASSIGNED) and, unless dbias is NULL, dbias [N] = column sums
+ * of dY, for n = 1 .. 4 problems in one launch.  X [M][ldx] (columns [0, Kw) read) and dY [M][ldy] (columns [0, N) from the pointer) in
+ * `dtype`; the contraction runs over the M rows.  SV_E_BADARG: p NULL, n outside 1..4, a dtype outside sv_dtype, a null X / dY / dW,
+ * ldx < Kw, ldy < N; SV_E_UNSUPPORTED: M no positive multiple of 32, Kw or N no positive multiple of 128, Kw_real outside 1..Kw, ldx / ldy
+ * no multiple of the elements of 16 bytes, X / dY not 16-byte aligned. */
+typedef struct { const void* X; int32_t ldx; const void* dY; int32_t ldy; float* dW; float* dbias; int32_t M, Kw, Kw_real, N; } sv_latent_tn_prob;
+int sv_latent_tn_wgrad(const sv_latent_tn_prob* p, int32_t n, int32_t dtype, void* stream);
+/* Both networks' Sampling + KL in one launch (a[0] = x, a[1] = x-hat; sv_reparam_kl_fwd each, Philox stream id = the index), as the plan calls
+ * it.  S > 0: `pre` is the first of S K-slice slabs [B][2L] fp32, slab_stride floats apart, summed in the kernel as sv_latent_nt_slab_reduce
+ * sums them (the same bits as reduce + sv_reparam_kl_fwd); S = 0: `pre` [B][2L] itself.  z_lp [B][ldz] in z_dtype is shared: network e writes
+ * columns [z_col, z_col + L).  SV_E_BADARG: a NULL, B <= 0, a z_dtype outside sv_dtype, per network a null pre / bias_mean / bias_sd / z_mean /
+ * z_sig / z / kl, L <= 0, S < 0, z_col < 0 or z_col + L > ldz; z_lp NULL. */
+typedef struct {
+  const float *pre, *bias_mean, *bias_sd, *eps;   /* eps NULL: Philox, written to eps_out */
+  float *eps_out, *z_mean, *z_sig, *z, *kl;       /* eps_out may be NULL */
+  int32_t L, z_col, S;
+  int64_t slab_stride;
+} sv_reparam_twin_fwd;
+int sv_reparam_kl_fwd_twin(const sv_reparam_twin_fwd* a, void* z_lp, int32_t z_dtype, int32_t ldz, int32_t B, uint64_t seed, uint64_t step,
+                           int64_t sample_offset, void* stream);
+/* The adjoints of both networks in one launch (sv_reparam_kl_bwd each).  S > 0: dz is the first of S slabs (row pitch ld_dz, `stride` floats
+ * apart) and dz2, unless NULL, the first of S2 slabs (ld_dz2, stride2); each set is summed from 0.f in slice order and the two sums are then
+ * added.  S = 0: plain tensors.  g_pre [B][2L] in g_dtype.  SV_E_BADARG: a NULL, B <= 0, a g_dtype outside sv_dtype, per network a null dz /
+ * z_mean / z_sig / eps / g_pre, L <= 0, S < 0, ld_dz < L, with dz2: ld_dz2 < L, and with dz2 and S > 0: S2 < 1. */
+typedef struct {
+  const float *dz, *dz2, *z_mean, *z_sig, *eps;
+  void* g_pre;
+  int32_t ld_dz, ld_dz2, L, S, S2;
+  int64_t stride, stride2;
+} sv_reparam_twin_bwd;
+int sv_reparam_kl_bwd_twin(const sv_reparam_twin_bwd* a, float kl_scale, int32_t g_dtype, int32_t B, void* stream);
+
 /* ---------------------------------------------------------------- SPLIT-SPAIR: the train step as one native launch sequence
  * Replaces, for spair/: SPAIR.call / LGSPAIR.call (spair/spair.py:35-49, :84-106), the loss assembly and tape.gradient of train_step
  * (spair/trainer.py:136-228) and optimizer.apply_gradients (:226-227, spair/main.py:109).  The host records the model ONCE as a list

@@ -94,6 +94,36 @@ class GmArgs(C.Structure):
                 ("seed", C.c_uint64), ("step", C.c_uint64), ("sample_offset", C.c_int64)]
 
 
+class LatentNtProb(C.Structure):
+    """sv_latent_nt_prob (include/splitvae.h)."""
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int32), ("W", C.c_void_p), ("ldw", C.c_int32), ("out", C.c_void_p), ("ldo", C.c_int32),
+                ("bias", C.c_void_p), ("mask", C.c_void_p)] + [(n, C.c_int32) for n in ("M", "N", "K", "act", "splitk", "out_f32")] + \
+               [("slab_stride", C.c_int64)]
+
+
+class LatentReduceProb(C.Structure):
+    """sv_latent_reduce_prob (include/splitvae.h)."""
+    _fields_ = [("slabs", C.c_void_p), ("out", C.c_void_p), ("S", C.c_int32), ("M", C.c_int32), ("ldo", C.c_int32), ("slab_stride", C.c_int64)]
+
+
+class LatentTnProb(C.Structure):
+    """sv_latent_tn_prob (include/splitvae.h)."""
+    _fields_ = [("X", C.c_void_p), ("ldx", C.c_int32), ("dY", C.c_void_p), ("ldy", C.c_int32), ("dW", C.c_void_p), ("dbias", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("M", "Kw", "Kw_real", "N")]
+
+
+class ReparamTwinFwd(C.Structure):
+    """sv_reparam_twin_fwd (include/splitvae.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("pre", "bias_mean", "bias_sd", "eps", "eps_out", "z_mean", "z_sig", "z", "kl")] + \
+               [("L", C.c_int32), ("z_col", C.c_int32), ("S", C.c_int32), ("slab_stride", C.c_int64)]
+
+
+class ReparamTwinBwd(C.Structure):
+    """sv_reparam_twin_bwd (include/splitvae.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("dz", "dz2", "z_mean", "z_sig", "eps", "g_pre")] + \
+               [(n, C.c_int32) for n in ("ld_dz", "ld_dz2", "L", "S", "S2")] + [("stride", C.c_int64), ("stride2", C.c_int64)]
+
+
 # every symbol include/splitvae.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _u64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 SYMBOLS = {
@@ -185,6 +215,12 @@ SYMBOLS = {
     "sv_gm_encoder_forward": (C.c_int, [_vp, C.POINTER(GmArgs), _vp]),
     "sv_gm_encoder_backward": (C.c_int, [_vp, C.POINTER(GmArgs), _vp]),
     "sv_gm_encoder_y_kl": (C.c_int, [_vp, _vp]),
+    "sv_latent_nt_gemm": (C.c_int, [C.POINTER(LatentNtProb), _i32, _i32, _i32, C.POINTER(_i32), _vp]),
+    "sv_latent_nt_pick_splitk": (_i32, [_i32, _i32, _i32, _i32]),
+    "sv_latent_nt_slab_reduce": (C.c_int, [C.POINTER(LatentReduceProb), _i32, _vp]),
+    "sv_latent_tn_wgrad": (C.c_int, [C.POINTER(LatentTnProb), _i32, _i32, _vp]),
+    "sv_reparam_kl_fwd_twin": (C.c_int, [C.POINTER(ReparamTwinFwd), _vp, _i32, _i32, _i32, _u64, _u64, _i64, _vp]),
+    "sv_reparam_kl_bwd_twin": (C.c_int, [C.POINTER(ReparamTwinBwd), _f, _i32, _i32, _vp]),
     "sv_dense_f32_fwd": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "sv_dense_f32_dgrad": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "sv_dense_f32_wgrad": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),

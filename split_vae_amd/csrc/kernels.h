@@ -232,7 +232,7 @@ struct NtGemmMulti { NtGemmProb p[2]; int n; };
 struct NtReduceMulti { const float* slab[2]; float* out[2]; int S[2]; int64_t stride[2]; int64_t count[2]; };
 bool svk_nt_gemm_supported(const NtGemmProb& p);
 int svk_nt_gemm_pick_splitk(int M, int N, int K, int nprob);
-int svk_nt_gemm_multi(NtGemmProb* p, int n, int bm, hipStream_t st);
+int svk_nt_gemm_multi(NtGemmProb* p, int n, int bm, hipStream_t st, int* form = nullptr);   // *form: 0 = one-slot kernel, 1 = ring (what was launched)
 int svk_nt_slab_reduce(const NtGemmProb* p, float* const* out, int n, hipStream_t st);
 
 // dW [Kw, N] = X^T . dY, dbias [N] = colsum(dY): X [M, ldx] (columns [0, Kw) used; Kw_real <= Kw rows of dW are stored), dY [M, ldy]

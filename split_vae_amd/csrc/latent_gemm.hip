@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void nt_slab_reduce_kernel(const NtReduceMulti
 }
 
 template <typename T, int BM>
-int launch_nt(const NtGemmMulti& m, hipStream_t st) {
+int launch_nt(const NtGemmMulti& m, hipStream_t st, int* form) {
   int gx = 0, gy = 0;
   bool ring = BM == 64;                 // slab launches whose slices span several phases: the ring form
   const bool no_ring = sv_knob_no_nt_ring();
@@ -275,6 +275,7 @@ int launch_nt(const NtGemmMulti& m, hipStream_t st) {
       sv_ensure_dynamic_lds((const void*)nt_gemm_ring_kernel<T, BM, NS>, lds);
       hipLaunchKernelGGL((nt_gemm_ring_kernel<T, BM, NS>), dim3(gx, gy, gz), dim3(256), lds, st, m);
       SV_LAUNCH_CHECK();
+      if (form) *form = 1;
       return SV_OK;
     }
   }
@@ -282,6 +283,7 @@ int launch_nt(const NtGemmMulti& m, hipStream_t st) {
   sv_ensure_dynamic_lds((const void*)nt_gemm_kernel<T, BM>, lds);
   hipLaunchKernelGGL((nt_gemm_kernel<T, BM>), dim3(gx, gy, gz), dim3(256), lds, st, m);
   SV_LAUNCH_CHECK();
+  if (form) *form = 0;
   return SV_OK;
 }
 
@@ -292,6 +294,9 @@ bool svk_nt_gemm_supported(const NtGemmProb& p) {
   if (p.M < 1 || p.N < BN || (p.N % BN) || p.K < bk || (p.K % bk) || p.splitk < 1 || (p.K % p.splitk) || ((p.K / p.splitk) % bk)) return false;
   if ((p.lda & pe) || (p.ldw & pe) || (p.ldo & 3) || ((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15) || ((uintptr_t)p.out & 15)) return false;
   if (p.bias && ((uintptr_t)p.bias & 15)) return false;
+  if (p.mask && ((uintptr_t)p.mask & 15)) return false;
+  if (!p.out_f32 && p.splitk > 1) return false;               // every slice would store its partial product (plus bias) over the others'
+  if (p.out_f32 && ((p.slab_stride & 3) || p.slab_stride < (int64_t)p.M * p.ldo)) return false;   // float4 stores; slabs must not overlap
   return true;
 }
 
@@ -311,7 +316,7 @@ int svk_nt_gemm_pick_splitk(int M, int N, int K, int nprob) {
 }
 
 // n <= 2 problems per launch (the x / x-hat twins); zbase is filled here.  bm: 64 | 128 rows per tile.
-int svk_nt_gemm_multi(NtGemmProb* p, int n, int bm, hipStream_t st) {
+int svk_nt_gemm_multi(NtGemmProb* p, int n, int bm, hipStream_t st, int* form) {
   if (n < 1 || n > 2 || (bm != 64 && bm != 128)) return SV_E_BADARG;
   NtGemmMulti m;
   m.n = n;
@@ -325,8 +330,8 @@ int svk_nt_gemm_multi(NtGemmProb* p, int n, int bm, hipStream_t st) {
   if (n == 1) m.p[1] = m.p[0];
   static const int bm32 = SV_TUNE_INT("SV_NT_F32_BM", 0);
   if (p[0].f32 && bm32) bm = bm32;
-  if (p[0].f32) return bm == 64 ? launch_nt<float, 64>(m, st) : launch_nt<float, 128>(m, st);
-  return bm == 64 ? launch_nt<bf16_t, 64>(m, st) : launch_nt<bf16_t, 128>(m, st);
+  if (p[0].f32) return bm == 64 ? launch_nt<float, 64>(m, st, form) : launch_nt<float, 128>(m, st, form);
+  return bm == 64 ? launch_nt<bf16_t, 64>(m, st, form) : launch_nt<bf16_t, 128>(m, st, form);
 }
 
 int svk_nt_slab_reduce(const NtGemmProb* p, float* const* out, int n, hipStream_t st) {
@@ -561,4 +566,55 @@ int svk_tn_wgrad_multi(const TnWgradProb* p, int n, hipStream_t st) {
   hipLaunchKernelGGL(tn_wgrad_kernel, dim3(gx, gy, n), dim3(256), lds, st, m);
   SV_LAUNCH_CHECK();
   return SV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Direct entry points (include/splitvae.h, "the latent block's kernels, one by one"): argument checks + the launches above, nothing else.
+extern "C" int32_t sv_latent_nt_pick_splitk(int32_t M, int32_t N, int32_t K, int32_t nprob) { return svk_nt_gemm_pick_splitk(M, N, K, nprob); }
+
+extern "C" int sv_latent_nt_gemm(sv_latent_nt_prob* p, int32_t n, int32_t dtype, int32_t bm, int32_t* form, void* stream) {
+  if (!p || n < 1 || n > 2 || (bm != 64 && bm != 128) || (dtype != SV_BF16 && dtype != SV_F32)) return SV_E_BADARG;
+  NtGemmProb q[2];
+  for (int i = 0; i < n; ++i) {
+    const sv_latent_nt_prob& s = p[i];
+    if (!s.A || !s.W || !s.out || s.M < 1 || s.N < 1 || s.K < 1 || s.lda < s.K || s.ldw < s.K || s.ldo < s.N || s.splitk < 0) return SV_E_BADARG;
+    if (s.act != SV_ACT_NONE && s.act != SV_ACT_RELU) return SV_E_BADARG;
+    NtGemmProb& g = q[i];
+    g = NtGemmProb{};
+    g.A = s.A; g.lda = s.lda; g.W = s.W; g.ldw = s.ldw; g.out = s.out; g.ldo = s.ldo; g.bias = s.bias; g.mask = s.mask;
+    g.M = s.M; g.N = s.N; g.K = s.K; g.act = s.act; g.out_f32 = s.out_f32 ? 1 : 0; g.f32 = dtype == SV_F32; g.slab_stride = s.slab_stride;
+    g.splitk = s.splitk ? s.splitk : svk_nt_gemm_pick_splitk(s.M, s.N, s.K, n);
+    if (!svk_nt_gemm_supported(g)) return SV_E_UNSUPPORTED;
+  }
+  int f = -1;
+  const int rc = svk_nt_gemm_multi(q, n, bm, (hipStream_t)stream, &f);
+  if (rc != SV_OK) return rc;
+  for (int i = 0; i < n; ++i) p[i].splitk = q[i].splitk;
+  if (form) *form = f;
+  return SV_OK;
+}
+
+extern "C" int sv_latent_nt_slab_reduce(const sv_latent_reduce_prob* p, int32_t n, void* stream) {
+  if (!p || n < 1 || n > 2) return SV_E_BADARG;
+  NtGemmProb q[2];
+  float* outs[2];
+  for (int i = 0; i < n; ++i) {
+    if (!p[i].slabs || !p[i].out || p[i].S < 1 || p[i].M < 1 || p[i].ldo < 1) return SV_E_BADARG;
+    if ((p[i].ldo & 3) || (p[i].slab_stride & 3) || ((uintptr_t)p[i].slabs & 15) || ((uintptr_t)p[i].out & 15)) return SV_E_UNSUPPORTED;
+    q[i] = NtGemmProb{};
+    q[i].out = (void*)p[i].slabs; q[i].splitk = p[i].S; q[i].slab_stride = p[i].slab_stride; q[i].M = p[i].M; q[i].ldo = p[i].ldo;
+    outs[i] = p[i].out;
+  }
+  return svk_nt_slab_reduce(q, outs, n, (hipStream_t)stream);
+}
+
+extern "C" int sv_latent_tn_wgrad(const sv_latent_tn_prob* p, int32_t n, int32_t dtype, void* stream) {
+  if (!p || n < 1 || n > 4 || (dtype != SV_BF16 && dtype != SV_F32)) return SV_E_BADARG;
+  TnWgradProb q[4];
+  for (int i = 0; i < n; ++i) {
+    if (!p[i].X || !p[i].dY || !p[i].dW || p[i].ldx < p[i].Kw || p[i].ldy < p[i].N) return SV_E_BADARG;
+    q[i] = TnWgradProb{p[i].X, p[i].ldx, p[i].dY, p[i].ldy, p[i].dW, p[i].dbias, p[i].M, p[i].Kw, p[i].Kw_real, p[i].N, dtype == SV_F32};
+    if (!svk_tn_wgrad_supported(q[i])) return SV_E_UNSUPPORTED;
+  }
+  return svk_tn_wgrad_multi(q, n, (hipStream_t)stream);
 }

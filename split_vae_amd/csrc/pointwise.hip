@@ -502,6 +502,42 @@ extern "C" int sv_reparam_kl_bwd(const float* dz, int32_t ld_dz, const float* dz
   return SV_OK;
 }
 
+// the twin kernels as the plan calls them, for tests and host bindings (include/splitvae.h): argument checks + the launches above
+extern "C" int sv_reparam_kl_fwd_twin(const sv_reparam_twin_fwd* a, void* z_lp, int32_t z_dtype, int32_t ldz, int32_t B, uint64_t seed,
+                                      uint64_t step, int64_t sample_offset, void* stream) {
+  if (!a || !z_lp || B <= 0 || (z_dtype != SV_BF16 && z_dtype != SV_F32)) return SV_E_BADARG;
+  const float *pre[2], *bm[2], *bs[2], *eps[2];
+  float *eo[2], *zm[2], *zs[2], *zz[2], *kl[2];
+  int zc[2], L[2], S[2];
+  int64_t sd[2];
+  for (int e = 0; e < 2; ++e) {
+    const sv_reparam_twin_fwd& g = a[e];
+    if (!g.pre || !g.bias_mean || !g.bias_sd || !g.z_mean || !g.z_sig || !g.z || !g.kl || g.L <= 0 || g.S < 0 || g.z_col < 0 ||
+        (int64_t)g.z_col + g.L > ldz)
+      return SV_E_BADARG;
+    pre[e] = g.pre; bm[e] = g.bias_mean; bs[e] = g.bias_sd; eps[e] = g.eps; eo[e] = g.eps_out; zm[e] = g.z_mean; zs[e] = g.z_sig; zz[e] = g.z;
+    kl[e] = g.kl; zc[e] = g.z_col; L[e] = g.L; S[e] = g.S; sd[e] = g.slab_stride;
+  }
+  return svk_reparam_kl_fwd_twin(pre, bm, bs, eps, eo, zm, zs, zz, z_lp, z_dtype, ldz, zc, kl, B, L, seed, step, sample_offset,
+                                 (hipStream_t)stream, nullptr, S, sd);
+}
+
+extern "C" int sv_reparam_kl_bwd_twin(const sv_reparam_twin_bwd* a, float kl_scale, int32_t g_dtype, int32_t B, void* stream) {
+  if (!a || B <= 0 || (g_dtype != SV_BF16 && g_dtype != SV_F32)) return SV_E_BADARG;
+  const float *dz[2], *dz2[2], *zm[2], *zs[2], *ep[2];
+  void* gp[2];
+  int ld[2], ld2[2], L[2], S[2], S2[2];
+  int64_t sd[2], sd2[2];
+  for (int e = 0; e < 2; ++e) {
+    const sv_reparam_twin_bwd& g = a[e];
+    if (!g.dz || !g.z_mean || !g.z_sig || !g.eps || !g.g_pre || g.L <= 0 || g.S < 0 || g.ld_dz < g.L) return SV_E_BADARG;
+    if (g.dz2 && (g.ld_dz2 < g.L || (g.S > 0 && g.S2 < 1))) return SV_E_BADARG;
+    dz[e] = g.dz; dz2[e] = g.dz2; zm[e] = g.z_mean; zs[e] = g.z_sig; ep[e] = g.eps; gp[e] = g.g_pre; ld[e] = g.ld_dz; ld2[e] = g.ld_dz2;
+    L[e] = g.L; S[e] = g.S; S2[e] = g.S2; sd[e] = g.stride; sd2[e] = g.stride2;
+  }
+  return svk_reparam_kl_bwd_twin(dz, ld, dz2, ld2, zm, zs, ep, kl_scale, gp, g_dtype, B, L, (hipStream_t)stream, S, sd, S2, sd2);
+}
+
 // ============================================================================ K14 Keras Adam
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,

@@ -883,3 +883,78 @@ def dense_f32_wgrad(x, dy):
     db = torch.zeros((N,), dtype=torch.float32, device=x.device)
     check(_lib.load().sv_dense_f32_wgrad(_pr(x), x.stride(0), _pr(dy), dy.stride(0), _p(dw), _p(db), M, K, N, _stream()), "sv_dense_f32_wgrad")
     return dw, db
+
+
+# ---------------------------------------------------------------- the latent block's kernels, one by one (latent_gemm.hip)
+def _pany(t):
+    """Pointer of a device tensor or view (the caller states the pitches)."""
+    if t is None:
+        return None
+    assert t.is_cuda
+    return t.data_ptr()
+
+
+def latent_nt_pick_splitk(M, N, K, nprob):
+    return int(_lib.load().sv_latent_nt_pick_splitk(M, N, K, nprob))
+
+
+def latent_nt_gemm(probs, dtype, bm=64):
+    """sv_latent_nt_gemm over 1 or 2 problems, each a dict: A [M, K] and W [N, K] (2-D views, last dimension contiguous, the row stride is
+    the pitch), out (tensor or view: its data pointer), ldo, and optionally bias, mask, act ("relu"), splitk (0: the plan's pick), out_f32,
+    slab_stride.  Returns (form, [splitk that ran per problem]); form 0 = the one-slot kernel, 1 = the ring."""
+    arr = (_lib.LatentNtProb * len(probs))()
+    for g, q in zip(arr, probs):
+        A, W = q["A"], q["W"]
+        assert A.dim() == 2 and W.dim() == 2 and A.stride(1) == 1 and W.stride(1) == 1 and A.shape[1] == W.shape[1]
+        g.A, g.lda, g.W, g.ldw = _pany(A), A.stride(0), _pany(W), W.stride(0)
+        g.out, g.ldo, g.bias, g.mask = _pany(q["out"]), q["ldo"], _pany(q.get("bias")), _pany(q.get("mask"))
+        g.M, g.N, g.K = A.shape[0], W.shape[0], A.shape[1]
+        g.act = 1 if q.get("act") == "relu" else 0
+        g.splitk, g.out_f32, g.slab_stride = q.get("splitk", 1), int(bool(q.get("out_f32"))), q.get("slab_stride", 0)
+    form = C.c_int32(-1)
+    check(_lib.load().sv_latent_nt_gemm(arr, len(probs), sv_dtype(dtype), bm, C.byref(form), _stream()), "sv_latent_nt_gemm")
+    return form.value, [g.splitk for g in arr]
+
+
+def latent_nt_slab_reduce(probs):
+    """sv_latent_nt_slab_reduce over 1 or 2 problems, each a dict: slabs, out (fp32 tensors or views), S, M, ldo, slab_stride."""
+    arr = (_lib.LatentReduceProb * len(probs))()
+    for g, q in zip(arr, probs):
+        g.slabs, g.out, g.S, g.M, g.ldo, g.slab_stride = _pany(q["slabs"]), _pany(q["out"]), q["S"], q["M"], q["ldo"], q["slab_stride"]
+    check(_lib.load().sv_latent_nt_slab_reduce(arr, len(probs), _stream()), "sv_latent_nt_slab_reduce")
+
+
+def latent_tn_wgrad(probs, dtype):
+    """sv_latent_tn_wgrad over 1 .. 4 problems, each a dict: X [M, Kw] and dY [M, N] (2-D views, the row stride is the pitch), dW (fp32, row
+    pitch N), dbias (fp32 or None), Kw_real (default Kw)."""
+    arr = (_lib.LatentTnProb * len(probs))()
+    for g, q in zip(arr, probs):
+        X, dY = q["X"], q["dY"]
+        assert X.dim() == 2 and dY.dim() == 2 and X.stride(1) == 1 and dY.stride(1) == 1 and X.shape[0] == dY.shape[0]
+        g.X, g.ldx, g.dY, g.ldy, g.dW, g.dbias = _pany(X), X.stride(0), _pany(dY), dY.stride(0), _pany(q["dW"]), _pany(q.get("dbias"))
+        g.M, g.Kw, g.Kw_real, g.N = X.shape[0], X.shape[1], q.get("Kw_real", X.shape[1]), dY.shape[1]
+    check(_lib.load().sv_latent_tn_wgrad(arr, len(probs), sv_dtype(dtype), _stream()), "sv_latent_tn_wgrad")
+
+
+def reparam_kl_fwd_twin(nets, z_lp, ldz, B, seed=0, step=0, sample_offset=0):
+    """sv_reparam_kl_fwd_twin: nets = two dicts with pre, bias_mean, bias_sd, eps, eps_out, z_mean, z_sig, z, kl, L, z_col and, for K-slice
+    slabs, S and slab_stride; z_lp the shared [B, ldz] decoder input (bf16 or fp32)."""
+    arr = (_lib.ReparamTwinFwd * 2)()
+    for g, q in zip(arr, nets):
+        for k in ("pre", "bias_mean", "bias_sd", "eps", "eps_out", "z_mean", "z_sig", "z", "kl"):
+            setattr(g, k, _pany(q.get(k)))
+        g.L, g.z_col, g.S, g.slab_stride = q["L"], q["z_col"], q.get("S", 0), q.get("slab_stride", 0)
+    check(_lib.load().sv_reparam_kl_fwd_twin(arr, _pany(z_lp), sv_dtype(z_lp.dtype), ldz, B, seed, step, sample_offset, _stream()),
+          "sv_reparam_kl_fwd_twin")
+
+
+def reparam_kl_bwd_twin(nets, kl_scale, g_dtype, B):
+    """sv_reparam_kl_bwd_twin: nets = two dicts with dz, ld_dz, dz2 (or None), ld_dz2, z_mean, z_sig, eps, g_pre, L and, for slabs, S, stride,
+    S2, stride2."""
+    arr = (_lib.ReparamTwinBwd * 2)()
+    for g, q in zip(arr, nets):
+        for k in ("dz", "dz2", "z_mean", "z_sig", "eps", "g_pre"):
+            setattr(g, k, _pany(q.get(k)))
+        g.ld_dz, g.ld_dz2, g.L = q["ld_dz"], q.get("ld_dz2", 0), q["L"]
+        g.S, g.S2, g.stride, g.stride2 = q.get("S", 0), q.get("S2", 0), q.get("stride", 0), q.get("stride2", 0)
+    check(_lib.load().sv_reparam_kl_bwd_twin(arr, float(kl_scale), sv_dtype(g_dtype), B, _stream()), "sv_reparam_kl_bwd_twin")
