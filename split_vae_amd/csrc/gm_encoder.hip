@@ -9,7 +9,7 @@
 // Variables, in the reference's layer-tracking order (kernel, bias each): h_block conv2d x3, y_block dense x2, y_dense,
 // h_top_dense, z_prior_mean, z_prior_sig, e1, z_mean, z_sig.  The Dropout layers do1-4, do6, do7 exist in the reference
 // but are never called (:59-75 vs :116-135); only y_block's Dropout and do5 act, in training.
-#include <map>
+#include <algorithm>
 #include <string>
 #include <vector>
 #include <stdio.h>
@@ -17,6 +17,7 @@
 #include "common.hip.h"
 #include "kernels.h"
 #include "conv_geom.h"
+#include "buffer_table.h"
 
 #define SV_TRY(x)            \
   do {                       \
@@ -34,7 +35,25 @@ const char* const LAYER_NAMES[NLAYER] = {
     "encoder_x/z_prior_sig", "encoder_x/e1", "encoder_x/z_mean", "encoder_x/z_sig"};
 
 struct GmParam { std::string name; int64_t off; int ndim; int64_t shape[4]; int64_t count; };
-struct GmBuf { int64_t off, bytes; };
+// THE buffer list: id (B_<name>), public name (sv_gm_encoder_buffer) and position in the workspace, in this order.
+//   h1 .. ykl: forward (compute dtype unless noted); g_am .. g_c1: backward;
+//   g_hh .. acc_end: fp32 accumulation targets of the split-K input gradients, zeroed with one memset per backward (acc_end: empty, marks their end);
+//   wgrad_ws: partial-sum slabs of the tile weight gradients (two-stage flush: faster than fp32 atomics and run-to-run identical)
+#define GM_BUFFERS(X) \
+  X(jobs) X(warena) X(h1) X(h2) X(h3) X(a1) X(yh1a) X(yh1) X(keep1) X(a2) X(yh2) X(logits) X(y) X(y_lp) X(u) X(a_pm) X(a_ps) X(a_t) X(h_top) X(h5) \
+  X(keep5) X(a_e) X(he) X(hh) X(a_m) X(a_s) X(zm) X(zs) X(z) X(pm) X(ps) X(eps) X(kl2) X(ykl) X(g_am) X(g_as) X(g_apm) X(g_aps) X(g_ae) X(g_at) \
+  X(g_logits) X(g_a2) X(g_a1) X(g_c3) X(g_h2) X(g_c2) X(g_h1d) X(g_c1) X(g_hh) X(g_h5) X(g_y) X(g_yh2) X(g_yh1) X(g_h1) X(acc_end) X(wgrad_ws)
+enum GmBufId {
+#define X(n) B_##n,
+  GM_BUFFERS(X)
+#undef X
+  GM_NBUF
+};
+const char* const GM_BUF_NAMES[GM_NBUF] = {
+#define X(n) #n,
+  GM_BUFFERS(X)
+#undef X
+};
 
 inline int r8(int v) { return (v + 7) / 8 * 8; }
 
@@ -79,9 +98,8 @@ struct sv_gm_encoder {
   int64_t wf_off[NLAYER], wd_off[NLAYER];   // prepared forward / input-gradient images (element offsets in the arena)
   std::vector<PrepJob> jobs;
   int prep_blocks;
-  std::map<std::string, GmBuf> bufs;
-  int64_t ws_bytes = 0;
-  char* ws = nullptr;
+  BufTable<GM_NBUF> bufs{GM_BUF_NAMES};
+  bool bound = false;
   float rate = 0.f;                          // dropout rate of the last forward (its backward uses the same)
   int64_t F;
   int Kp;
@@ -94,16 +112,12 @@ struct sv_gm_encoder {
   }
 
   size_t esz() const { return d.dtype == SV_BF16 ? 2 : 4; }
-  void add(const std::string& n, int64_t bytes) {
-    bufs[n] = GmBuf{ws_bytes, bytes};
-    ws_bytes += (bytes + 255) / 256 * 256;
-  }
-  char* bp(const char* n) const { return ws + bufs.at(n).off; }
-  float* fp(const char* n) const { return (float*)bp(n); }
+  char* bp(int id) const { return (char*)bufs.ptr[id]; }
+  float* fp(int id) const { return (float*)bp(id); }
   const float* kernel(const float* flat, int l) const { return flat + params[2 * l].off; }
   const float* bias(const float* flat, int l) const { return flat + params[2 * l + 1].off; }
-  void* wfwd(int l) const { return bp("warena") + wf_off[l] * esz(); }
-  void* wdgrad(int l) const { return bp("warena") + wd_off[l] * esz(); }
+  void* wfwd(int l) const { return bp(B_warena) + wf_off[l] * esz(); }
+  void* wdgrad(int l) const { return bp(B_warena) + wd_off[l] * esz(); }
 };
 
 extern "C" int64_t sv_gm_param_count(const sv_gm_desc* d) {
@@ -185,110 +199,96 @@ extern "C" int sv_gm_encoder_create(const sv_gm_desc* d, sv_gm_encoder** out) {
 
   const int64_t es = (int64_t)e->esz(), Kp = e->Kp;
   const int64_t P1 = (int64_t)B * (H / 2) * (H / 2) * 128, P2 = (int64_t)B * (H / 4) * (H / 4) * 128, BF = (int64_t)B * F;
-  e->add("jobs", (int64_t)e->jobs.size() * sizeof(PrepJob));
-  e->add("warena", (arena + 128) * es);
-  // forward (compute dtype unless noted)
-  e->add("h1", P1 * es); e->add("h2", P2 * es); e->add("h3", BF * es);
-  e->add("a1", (int64_t)B * 1024 * 4); e->add("yh1a", (int64_t)B * 1024 * es); e->add("yh1", (int64_t)B * 1024 * es);
-  e->add("keep1", (int64_t)B * 1024 * 4);
-  e->add("a2", (int64_t)B * 128 * 4); e->add("yh2", (int64_t)B * 128 * es);
-  e->add("logits", (int64_t)B * K * 4); e->add("y", (int64_t)B * K * 4); e->add("y_lp", (int64_t)B * Kp * es); e->add("u", (int64_t)B * K * 4);
-  e->add("a_pm", (int64_t)B * L * 4); e->add("a_ps", (int64_t)B * L * 4); e->add("a_t", (int64_t)B * 512 * 4);
-  e->add("h_top", (int64_t)B * 512 * es);
-  e->add("h5", BF * es); e->add("keep5", BF * 4); e->add("a_e", (int64_t)B * 512 * 4); e->add("he", (int64_t)B * 512 * es);
-  e->add("hh", (int64_t)B * 512 * es);
-  e->add("a_m", (int64_t)B * L * 4); e->add("a_s", (int64_t)B * L * 4);
-  for (const char* n : {"zm", "zs", "z", "pm", "ps", "eps"}) e->add(n, (int64_t)B * L * 4);
-  e->add("kl2", (int64_t)B * 4); e->add("ykl", (int64_t)B * 4);
-  // backward
-  for (const char* n : {"g_am", "g_as", "g_apm", "g_aps"}) e->add(n, (int64_t)B * L * es);
-  e->add("g_ae", (int64_t)B * 512 * es); e->add("g_at", (int64_t)B * 512 * es);
-  e->add("g_logits", (int64_t)B * Kp * es); e->add("g_a2", (int64_t)B * 128 * es); e->add("g_a1", (int64_t)B * 1024 * es);
-  e->add("g_c3", BF * es); e->add("g_h2", P2 * es); e->add("g_c2", P2 * es); e->add("g_h1d", P1 * es); e->add("g_c1", P1 * es);
-  // fp32 accumulation targets of the split-K input gradients: adjacent, zeroed with one memset per backward
-  e->add("g_hh", (int64_t)B * 512 * 4); e->add("g_h5", BF * 4); e->add("g_y", (int64_t)B * Kp * 4);
-  e->add("g_yh2", (int64_t)B * 128 * 4); e->add("g_yh1", (int64_t)B * 1024 * 4); e->add("g_h1", BF * 4);
-  e->add("acc_end", 0);
-  // partial-sum slabs of the tile weight gradients (two-stage flush: faster than fp32 atomics and run-to-run identical)
-  int64_t wsb = 0;
-  for (int l = 0; l < NLAYER; ++l) { const int64_t b = sv_conv2d_wgrad_workspace_bytes(&e->conv[l]); wsb = b > wsb ? b : wsb; }
-  e->add("wgrad_ws", wsb);
+  int64_t sz[GM_NBUF];                  // bytes by id (GM_BUFFERS gives the positions); this object has every buffer
+  for (auto& v : sz) v = -1;
+  sz[B_jobs] = (int64_t)e->jobs.size() * sizeof(PrepJob);
+  sz[B_warena] = (arena + 128) * es;
+  sz[B_h1] = P1 * es; sz[B_h2] = P2 * es; sz[B_h3] = BF * es;
+  sz[B_a1] = (int64_t)B * 1024 * 4; sz[B_yh1a] = sz[B_yh1] = (int64_t)B * 1024 * es; sz[B_keep1] = (int64_t)B * 1024 * 4;
+  sz[B_a2] = (int64_t)B * 128 * 4; sz[B_yh2] = (int64_t)B * 128 * es;
+  sz[B_logits] = sz[B_y] = sz[B_u] = (int64_t)B * K * 4; sz[B_y_lp] = (int64_t)B * Kp * es;
+  sz[B_a_pm] = sz[B_a_ps] = (int64_t)B * L * 4; sz[B_a_t] = (int64_t)B * 512 * 4;
+  sz[B_h_top] = sz[B_he] = sz[B_hh] = (int64_t)B * 512 * es;
+  sz[B_h5] = BF * es; sz[B_keep5] = BF * 4; sz[B_a_e] = (int64_t)B * 512 * 4;
+  for (int id : {B_a_m, B_a_s, B_zm, B_zs, B_z, B_pm, B_ps, B_eps}) sz[id] = (int64_t)B * L * 4;
+  sz[B_kl2] = sz[B_ykl] = (int64_t)B * 4;
+  for (int id : {B_g_am, B_g_as, B_g_apm, B_g_aps}) sz[id] = (int64_t)B * L * es;
+  sz[B_g_ae] = sz[B_g_at] = (int64_t)B * 512 * es;
+  sz[B_g_logits] = (int64_t)B * Kp * es; sz[B_g_a2] = (int64_t)B * 128 * es; sz[B_g_a1] = (int64_t)B * 1024 * es;
+  sz[B_g_c3] = BF * es; sz[B_g_h2] = sz[B_g_c2] = P2 * es; sz[B_g_h1d] = sz[B_g_c1] = P1 * es;
+  sz[B_g_hh] = (int64_t)B * 512 * 4; sz[B_g_h5] = sz[B_g_h1] = BF * 4; sz[B_g_y] = (int64_t)B * Kp * 4;
+  sz[B_g_yh2] = (int64_t)B * 128 * 4; sz[B_g_yh1] = (int64_t)B * 1024 * 4;
+  sz[B_acc_end] = 0;
+  sz[B_wgrad_ws] = 0;
+  for (int l = 0; l < NLAYER; ++l) sz[B_wgrad_ws] = std::max<int64_t>(sz[B_wgrad_ws], sv_conv2d_wgrad_workspace_bytes(&e->conv[l]));
+  e->bufs.layout(sz);
+  // every buffer got a size above -- so g_hh .. acc_end, which sv_gm_encoder_backward zeroes with one memset, hold exactly the accumulators between them
+  if (!e->bufs.run(0, GM_NBUF - 1)) { delete e; return SV_E_STATE; }
   *out = e;
   return SV_OK;
 }
 
 extern "C" void sv_gm_encoder_destroy(sv_gm_encoder* e) { delete e; }
 
-extern "C" int64_t sv_gm_encoder_workspace_bytes(const sv_gm_encoder* e) { return e ? e->ws_bytes : -1; }
+extern "C" int64_t sv_gm_encoder_workspace_bytes(const sv_gm_encoder* e) { return e ? e->bufs.ws_bytes : -1; }
 
 extern "C" int sv_gm_encoder_bind(sv_gm_encoder* e, void* workspace, int64_t bytes, void* stream) {
-  if (!e || !workspace) return SV_E_BADARG;
-  if (bytes < e->ws_bytes) return SV_E_WORKSPACE;
-  if ((uintptr_t)workspace & 255) return SV_E_BADARG;
-  e->ws = (char*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(workspace, 0, (size_t)e->ws_bytes, st) != hipSuccess) return (int)hipGetLastError();     // pad channels and accumulation targets start from zero (as sv_lgvae_plan_bind)
-  if (hipMemcpyAsync(e->bp("jobs"), e->jobs.data(), e->jobs.size() * sizeof(PrepJob), hipMemcpyHostToDevice, st) != hipSuccess)
-    return (int)hipGetLastError();
-  if (hipStreamSynchronize(st) != hipSuccess) return (int)hipGetLastError();   // the host vector may go away
+  if (!e) return SV_E_BADARG;
+  SV_TRY(e->bufs.bind(workspace, bytes, (hipStream_t)stream, B_jobs, e->jobs.data(), e->jobs.size() * sizeof(PrepJob)));
+  e->bound = true;
   return SV_OK;
 }
 
 extern "C" int sv_gm_encoder_buffer(const sv_gm_encoder* e, const char* name, int64_t* offset, int64_t* bytes) {
-  if (!e || !name) return SV_E_BADARG;
-  auto it = e->bufs.find(name);
-  if (it == e->bufs.end()) return SV_E_BADARG;
-  if (offset) *offset = it->second.off;
-  if (bytes) *bytes = it->second.bytes;
-  return SV_OK;
+  return e ? e->bufs.lookup(name, offset, bytes) : SV_E_BADARG;
 }
 
 // fp32 HWIO masters -> MFMA-ready images of all twelve layers (one launch)
 extern "C" int sv_gm_encoder_prep(sv_gm_encoder* e, const float* params, void* stream) {
-  if (!e || !e->ws || !params) return SV_E_BADARG;
-  return svk_prep_weights(params, e->bp("warena"), e->d.dtype, (const PrepJob*)e->bp("jobs"), (int)e->jobs.size(),
+  if (!e || !e->bound || !params) return SV_E_BADARG;
+  return svk_prep_weights(params, e->bp(B_warena), e->d.dtype, (const PrepJob*)e->bp(B_jobs), (int)e->jobs.size(),
                           e->prep_blocks, (hipStream_t)stream);
 }
 
 // call_gmvae (vae/model.py:116-135).  Needs sv_gm_encoder_prep after every change of `params`.
 extern "C" int sv_gm_encoder_forward(sv_gm_encoder* e, const sv_gm_args* a, void* stream) {
-  if (!e || !e->ws || !a || !a->params || !a->in8_x || !a->zcat) return SV_E_BADARG;
+  if (!e || !e->bound || !a || !a->params || !a->in8_x || !a->zcat) return SV_E_BADARG;
   const sv_gm_desc& d = e->d;
   const int B = d.B, H = d.H, K = d.y_size, L = d.latent, dt = d.dtype, Kp = e->Kp;
   const int64_t F = e->F;
   const float* P = a->params;
   const float rate = a->training ? GM_RATE : 0.f;
   auto fwd = [&](int l, const void* x, void* y) { return sv_conv2d_nhwc_fwd(&e->conv[l], x, e->wfwd(l), e->bias(P, l), y, stream); };
-  auto elu_inplace = [&](const char* n, int64_t rows) {   // Conv2D(activation='elu') :50-52
+  auto elu_inplace = [&](int n, int64_t rows) {   // Conv2D(activation='elu') :50-52
     return sv_act_fwd(e->bp(n), dt, 128, nullptr, e->bp(n), dt, 128, rows, 128, SV_ACT_ELU, 0.f, nullptr, nullptr, 0, 0, 0, 0, 1, stream);
   };
   // h_block: three stride-2 convs with ELU
-  SV_TRY(fwd(C1, a->in8_x, e->bp("h1"))); SV_TRY(elu_inplace("h1", (int64_t)B * (H / 2) * (H / 2)));
-  SV_TRY(fwd(C2, e->bp("h1"), e->bp("h2"))); SV_TRY(elu_inplace("h2", (int64_t)B * (H / 4) * (H / 4)));
-  SV_TRY(fwd(C3, e->bp("h2"), e->bp("h3"))); SV_TRY(elu_inplace("h3", (int64_t)B * (H / 8) * (H / 8)));
+  SV_TRY(fwd(C1, a->in8_x, e->bp(B_h1))); SV_TRY(elu_inplace(B_h1, (int64_t)B * (H / 2) * (H / 2)));
+  SV_TRY(fwd(C2, e->bp(B_h1), e->bp(B_h2))); SV_TRY(elu_inplace(B_h2, (int64_t)B * (H / 4) * (H / 4)));
+  SV_TRY(fwd(C3, e->bp(B_h2), e->bp(B_h3))); SV_TRY(elu_inplace(B_h3, (int64_t)B * (H / 8) * (H / 8)));
   // y_block (:54-58) -> y_dense (:60) -> Gumbel-softmax (:121-122)
-  SV_TRY(fwd(D1, e->bp("h3"), e->bp("a1")));
-  SV_TRY(sv_act_fwd(e->bp("a1"), SV_F32, 1024, e->bp("yh1a"), e->bp("yh1"), dt, 1024, B, 1024, SV_ACT_ELU, rate, a->keep1,
-                    e->fp("keep1"), a->seed, a->step, 11, a->sample_offset, 1, stream));
-  SV_TRY(fwd(D2, e->bp("yh1"), e->bp("a2")));
-  SV_TRY(sv_act_fwd(e->bp("a2"), SV_F32, 128, nullptr, e->bp("yh2"), dt, 128, B, 128, SV_ACT_ELU, 0.f, nullptr, nullptr, 0, 0, 0, 0, 1, stream));
-  SV_TRY(fwd(YD, e->bp("yh2"), e->bp("logits")));
-  SV_TRY(sv_gumbel_softmax_fwd(e->fp("logits"), K, a->u, e->fp("u"), d.tau, e->fp("y"), e->bp("y_lp"), dt, Kp, B, K, a->seed,
+  SV_TRY(fwd(D1, e->bp(B_h3), e->bp(B_a1)));
+  SV_TRY(sv_act_fwd(e->bp(B_a1), SV_F32, 1024, e->bp(B_yh1a), e->bp(B_yh1), dt, 1024, B, 1024, SV_ACT_ELU, rate, a->keep1,
+                    e->fp(B_keep1), a->seed, a->step, 11, a->sample_offset, 1, stream));
+  SV_TRY(fwd(D2, e->bp(B_yh1), e->bp(B_a2)));
+  SV_TRY(sv_act_fwd(e->bp(B_a2), SV_F32, 128, nullptr, e->bp(B_yh2), dt, 128, B, 128, SV_ACT_ELU, 0.f, nullptr, nullptr, 0, 0, 0, 0, 1, stream));
+  SV_TRY(fwd(YD, e->bp(B_yh2), e->bp(B_logits)));
+  SV_TRY(sv_gumbel_softmax_fwd(e->fp(B_logits), K, a->u, e->fp(B_u), d.tau, e->fp(B_y), e->bp(B_y_lp), dt, Kp, B, K, a->seed,
                                a->step, a->sample_offset, stream));
   // prior (:124-125), h_top (:127), encoder block (:128-133)
-  SV_TRY(fwd(PM, e->bp("y_lp"), e->bp("a_pm")));
-  SV_TRY(fwd(PS, e->bp("y_lp"), e->bp("a_ps")));
-  SV_TRY(fwd(HT, e->bp("y_lp"), e->bp("a_t")));
-  SV_TRY(sv_act_fwd(e->bp("a_t"), SV_F32, 512, nullptr, e->bp("h_top"), dt, 512, B, 512, SV_ACT_ELU, 0.f, nullptr, nullptr, 0, 0, 0, 0, 1, stream));
-  SV_TRY(sv_act_fwd(e->bp("h3"), dt, (int)F, nullptr, e->bp("h5"), dt, (int)F, B, (int)F, SV_ACT_NONE, rate, a->keep5, e->fp("keep5"),
+  SV_TRY(fwd(PM, e->bp(B_y_lp), e->bp(B_a_pm)));
+  SV_TRY(fwd(PS, e->bp(B_y_lp), e->bp(B_a_ps)));
+  SV_TRY(fwd(HT, e->bp(B_y_lp), e->bp(B_a_t)));
+  SV_TRY(sv_act_fwd(e->bp(B_a_t), SV_F32, 512, nullptr, e->bp(B_h_top), dt, 512, B, 512, SV_ACT_ELU, 0.f, nullptr, nullptr, 0, 0, 0, 0, 1, stream));
+  SV_TRY(sv_act_fwd(e->bp(B_h3), dt, (int)F, nullptr, e->bp(B_h5), dt, (int)F, B, (int)F, SV_ACT_NONE, rate, a->keep5, e->fp(B_keep5),
                     a->seed, a->step, 15, a->sample_offset, 1, stream));
-  SV_TRY(fwd(E1, e->bp("h5"), e->bp("a_e")));
-  SV_TRY(sv_act_fwd(e->bp("a_e"), SV_F32, 512, nullptr, e->bp("he"), dt, 512, B, 512, SV_ACT_ELU, 0.f, nullptr, nullptr, 0, 0, 0, 0, 1, stream));
-  SV_TRY(sv_add(e->bp("he"), e->bp("h_top"), e->bp("hh"), dt, (int64_t)B * 512, stream));
-  SV_TRY(fwd(ZM, e->bp("hh"), e->bp("a_m")));
-  SV_TRY(fwd(ZS, e->bp("hh"), e->bp("a_s")));
-  SV_TRY(sv_gm_head_fwd(e->fp("a_m"), e->fp("a_s"), e->fp("a_pm"), e->fp("a_ps"), a->eps, e->fp("eps"), e->fp("zm"), e->fp("zs"),
-                        e->fp("z"), e->fp("pm"), e->fp("ps"), a->zcat, dt, a->ldz, 0, e->fp("kl2"), B, L, a->seed, a->step,
+  SV_TRY(fwd(E1, e->bp(B_h5), e->bp(B_a_e)));
+  SV_TRY(sv_act_fwd(e->bp(B_a_e), SV_F32, 512, nullptr, e->bp(B_he), dt, 512, B, 512, SV_ACT_ELU, 0.f, nullptr, nullptr, 0, 0, 0, 0, 1, stream));
+  SV_TRY(sv_add(e->bp(B_he), e->bp(B_h_top), e->bp(B_hh), dt, (int64_t)B * 512, stream));
+  SV_TRY(fwd(ZM, e->bp(B_hh), e->bp(B_a_m)));
+  SV_TRY(fwd(ZS, e->bp(B_hh), e->bp(B_a_s)));
+  SV_TRY(sv_gm_head_fwd(e->fp(B_a_m), e->fp(B_a_s), e->fp(B_a_pm), e->fp(B_a_ps), a->eps, e->fp(B_eps), e->fp(B_zm), e->fp(B_zs),
+                        e->fp(B_z), e->fp(B_pm), e->fp(B_ps), a->zcat, dt, a->ldz, 0, e->fp(B_kl2), B, L, a->seed, a->step,
                         a->sample_offset, stream));
   e->rate = rate;
   return SV_OK;
@@ -297,17 +297,13 @@ extern "C" int sv_gm_encoder_forward(sv_gm_encoder* e, const sv_gm_args* a, void
 // The adjoint (tape.gradient, vae/trainer.py:167): gz [B, >= L] fp32 = dL/dz_x from the decoder (columns [0, L)).
 // ACCUMULATES the 24 gradients into `grads` (zero them first) and fills ykl (the per-image categorical KL term).
 extern "C" int sv_gm_encoder_backward(sv_gm_encoder* e, const sv_gm_args* a, void* stream) {
-  if (!e || !e->ws || !a || !a->params || !a->grads || !a->in8_x || !a->gz) return SV_E_BADARG;
+  if (!e || !e->bound || !a || !a->params || !a->grads || !a->in8_x || !a->gz) return SV_E_BADARG;
   const sv_gm_desc& d = e->d;
   const int B = d.B, H = d.H, K = d.y_size, L = d.latent, dt = d.dtype, Kp = e->Kp;
   const int64_t F = e->F;
   const float rate = e->rate;
   hipStream_t st = (hipStream_t)stream;
-  {
-    char* z0 = e->bp("g_hh");
-    char* z1 = e->bp("acc_end");
-    if (hipMemsetAsync(z0, 0, (size_t)(z1 - z0), st) != hipSuccess) return (int)hipGetLastError();
-  }
+  SV_TRY(e->bufs.zero(B_g_hh, B_acc_end, st));
   // The weight gradients feed only Adam: they go to the library's shared side stream 0 behind a "dY is ready" event, the input-gradient chain (the critical
   // path: 12 layers, one after the other) continues at once; joined at the end of the call.  Every dY buffer is written once per call, the forward activations
   // are read-only here, each layer's variable gradients have one writer.  SV_GM_WGRAD_SIDE=0: everything on `stream` (A/B).  profiles/r06_gm_streams.txt
@@ -323,45 +319,45 @@ extern "C" int sv_gm_encoder_backward(sv_gm_encoder* e, const sv_gm_args* a, voi
       wst = (void*)ws2;
       forked = true;
     }
-    return sv_conv2d_nhwc_wgrad_ws(&e->conv[l], x, dy, a->grads + e->params[2 * l].off, a->grads + e->params[2 * l + 1].off, e->bp("wgrad_ws"),
-                                   e->bufs.at("wgrad_ws").bytes, wst);
+    return sv_conv2d_nhwc_wgrad_ws(&e->conv[l], x, dy, a->grads + e->params[2 * l].off, a->grads + e->params[2 * l + 1].off, e->bp(B_wgrad_ws),
+                                   e->bufs.bytes[B_wgrad_ws], wst);
   };
-  auto dg_acc = [&](int l, const void* dy, const char* acc) {   // split-K input gradient added into an fp32 buffer
+  auto dg_acc = [&](int l, const void* dy, int acc) {   // split-K input gradient added into an fp32 buffer
     return sv_conv2d_nhwc_dgrad(&e->conv[l], dy, e->wdgrad(l), nullptr, e->bp(acc), 1, stream);
   };
-  auto dg = [&](int l, const void* dy, const char* out) { return sv_conv2d_nhwc_dgrad(&e->conv[l], dy, e->wdgrad(l), nullptr, e->bp(out), 0, stream); };
-  auto act_bwd = [&](const char* gx, int gx_dt, int ld, const char* gx2, const char* y_act, float r, const float* keep,
-                     const char* ga, int64_t rows, int C) {
-    return sv_act_bwd(e->bp(gx), gx_dt, ld, gx2 ? e->bp(gx2) : nullptr, gx2 ? SV_F32 : 0, gx2 ? ld : 0, e->bp(y_act), dt, ld,
+  auto dg = [&](int l, const void* dy, int out) { return sv_conv2d_nhwc_dgrad(&e->conv[l], dy, e->wdgrad(l), nullptr, e->bp(out), 0, stream); };
+  auto act_bwd = [&](int gx, int gx_dt, int ld, int gx2 /* a second fp32 gradient to add, or -1 */, int y_act, float r, const float* keep,
+                     int ga, int64_t rows, int C) {
+    return sv_act_bwd(e->bp(gx), gx_dt, ld, gx2 >= 0 ? e->bp(gx2) : nullptr, gx2 >= 0 ? SV_F32 : 0, gx2 >= 0 ? ld : 0, e->bp(y_act), dt, ld,
                       SV_ACT_ELU, r, keep, e->bp(ga), dt, ld, rows, C, stream);
   };
-  SV_TRY(sv_gm_head_bwd(a->gz, a->ld_gz, e->fp("zm"), e->fp("zs"), e->fp("pm"), e->fp("ps"), e->fp("eps"), a->beta / (float)B,
-                        e->bp("g_am"), e->bp("g_as"), e->bp("g_apm"), e->bp("g_aps"), dt, B, L, stream));
-  SV_TRY(wg(ZM, e->bp("hh"), e->bp("g_am"))); SV_TRY(wg(ZS, e->bp("hh"), e->bp("g_as")));
-  SV_TRY(dg_acc(ZM, e->bp("g_am"), "g_hh")); SV_TRY(dg_acc(ZS, e->bp("g_as"), "g_hh"));
-  SV_TRY(act_bwd("g_hh", SV_F32, 512, nullptr, "he", 0.f, nullptr, "g_ae", B, 512));
-  SV_TRY(act_bwd("g_hh", SV_F32, 512, nullptr, "h_top", 0.f, nullptr, "g_at", B, 512));
-  SV_TRY(wg(E1, e->bp("h5"), e->bp("g_ae")));
-  SV_TRY(dg_acc(E1, e->bp("g_ae"), "g_h5"));
-  SV_TRY(wg(HT, e->bp("y_lp"), e->bp("g_at"))); SV_TRY(dg_acc(HT, e->bp("g_at"), "g_y"));
-  SV_TRY(wg(PM, e->bp("y_lp"), e->bp("g_apm"))); SV_TRY(dg_acc(PM, e->bp("g_apm"), "g_y"));
-  SV_TRY(wg(PS, e->bp("y_lp"), e->bp("g_aps"))); SV_TRY(dg_acc(PS, e->bp("g_aps"), "g_y"));
-  SV_TRY(sv_gumbel_softmax_bwd(e->fp("g_y"), Kp, e->fp("y"), e->fp("logits"), K, d.tau, a->alpha / (float)B, e->bp("g_logits"), dt,
-                               Kp, e->fp("ykl"), B, K, stream));
-  SV_TRY(wg(YD, e->bp("yh2"), e->bp("g_logits"))); SV_TRY(dg_acc(YD, e->bp("g_logits"), "g_yh2"));
-  SV_TRY(act_bwd("g_yh2", SV_F32, 128, nullptr, "yh2", 0.f, nullptr, "g_a2", B, 128));
-  SV_TRY(wg(D2, e->bp("yh1"), e->bp("g_a2"))); SV_TRY(dg_acc(D2, e->bp("g_a2"), "g_yh1"));
-  SV_TRY(act_bwd("g_yh1", SV_F32, 1024, nullptr, "yh1a", rate, e->fp("keep1"), "g_a1", B, 1024));
-  SV_TRY(wg(D1, e->bp("h3"), e->bp("g_a1"))); SV_TRY(dg_acc(D1, e->bp("g_a1"), "g_h1"));
+  SV_TRY(sv_gm_head_bwd(a->gz, a->ld_gz, e->fp(B_zm), e->fp(B_zs), e->fp(B_pm), e->fp(B_ps), e->fp(B_eps), a->beta / (float)B,
+                        e->bp(B_g_am), e->bp(B_g_as), e->bp(B_g_apm), e->bp(B_g_aps), dt, B, L, stream));
+  SV_TRY(wg(ZM, e->bp(B_hh), e->bp(B_g_am))); SV_TRY(wg(ZS, e->bp(B_hh), e->bp(B_g_as)));
+  SV_TRY(dg_acc(ZM, e->bp(B_g_am), B_g_hh)); SV_TRY(dg_acc(ZS, e->bp(B_g_as), B_g_hh));
+  SV_TRY(act_bwd(B_g_hh, SV_F32, 512, -1, B_he, 0.f, nullptr, B_g_ae, B, 512));
+  SV_TRY(act_bwd(B_g_hh, SV_F32, 512, -1, B_h_top, 0.f, nullptr, B_g_at, B, 512));
+  SV_TRY(wg(E1, e->bp(B_h5), e->bp(B_g_ae)));
+  SV_TRY(dg_acc(E1, e->bp(B_g_ae), B_g_h5));
+  SV_TRY(wg(HT, e->bp(B_y_lp), e->bp(B_g_at))); SV_TRY(dg_acc(HT, e->bp(B_g_at), B_g_y));
+  SV_TRY(wg(PM, e->bp(B_y_lp), e->bp(B_g_apm))); SV_TRY(dg_acc(PM, e->bp(B_g_apm), B_g_y));
+  SV_TRY(wg(PS, e->bp(B_y_lp), e->bp(B_g_aps))); SV_TRY(dg_acc(PS, e->bp(B_g_aps), B_g_y));
+  SV_TRY(sv_gumbel_softmax_bwd(e->fp(B_g_y), Kp, e->fp(B_y), e->fp(B_logits), K, d.tau, a->alpha / (float)B, e->bp(B_g_logits), dt,
+                               Kp, e->fp(B_ykl), B, K, stream));
+  SV_TRY(wg(YD, e->bp(B_yh2), e->bp(B_g_logits))); SV_TRY(dg_acc(YD, e->bp(B_g_logits), B_g_yh2));
+  SV_TRY(act_bwd(B_g_yh2, SV_F32, 128, -1, B_yh2, 0.f, nullptr, B_g_a2, B, 128));
+  SV_TRY(wg(D2, e->bp(B_yh1), e->bp(B_g_a2))); SV_TRY(dg_acc(D2, e->bp(B_g_a2), B_g_yh1));
+  SV_TRY(act_bwd(B_g_yh1, SV_F32, 1024, -1, B_yh1a, rate, e->fp(B_keep1), B_g_a1, B, 1024));
+  SV_TRY(wg(D1, e->bp(B_h3), e->bp(B_g_a1))); SV_TRY(dg_acc(D1, e->bp(B_g_a1), B_g_h1));
   // h feeds y_block (g_h1) and, through do5, e1 (g_h5): combine, then ELU' of conv3
-  SV_TRY(act_bwd("g_h5", SV_F32, (int)F, "g_h1", "h3", rate, e->fp("keep5"), "g_c3", B, (int)F));
-  SV_TRY(wg(C3, e->bp("h2"), e->bp("g_c3")));
-  SV_TRY(dg(C3, e->bp("g_c3"), "g_h2"));
-  SV_TRY(act_bwd("g_h2", dt, 128, nullptr, "h2", 0.f, nullptr, "g_c2", (int64_t)B * (H / 4) * (H / 4), 128));
-  SV_TRY(wg(C2, e->bp("h1"), e->bp("g_c2")));
-  SV_TRY(dg(C2, e->bp("g_c2"), "g_h1d"));
-  SV_TRY(act_bwd("g_h1d", dt, 128, nullptr, "h1", 0.f, nullptr, "g_c1", (int64_t)B * (H / 2) * (H / 2), 128));
-  SV_TRY(wg(C1, a->in8_x, e->bp("g_c1")));
+  SV_TRY(act_bwd(B_g_h5, SV_F32, (int)F, B_g_h1, B_h3, rate, e->fp(B_keep5), B_g_c3, B, (int)F));
+  SV_TRY(wg(C3, e->bp(B_h2), e->bp(B_g_c3)));
+  SV_TRY(dg(C3, e->bp(B_g_c3), B_g_h2));
+  SV_TRY(act_bwd(B_g_h2, dt, 128, -1, B_h2, 0.f, nullptr, B_g_c2, (int64_t)B * (H / 4) * (H / 4), 128));
+  SV_TRY(wg(C2, e->bp(B_h1), e->bp(B_g_c2)));
+  SV_TRY(dg(C2, e->bp(B_g_c2), B_g_h1d));
+  SV_TRY(act_bwd(B_g_h1d, dt, 128, -1, B_h1, 0.f, nullptr, B_g_c1, (int64_t)B * (H / 2) * (H / 2), 128));
+  SV_TRY(wg(C1, a->in8_x, e->bp(B_g_c1)));
   if (forked) {
     if (!e->ev_wjoin && hipEventCreateWithFlags(&e->ev_wjoin, hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
     if (hipEventRecord(e->ev_wjoin, ws2) != hipSuccess || hipStreamWaitEvent(st, e->ev_wjoin, 0) != hipSuccess) return (int)hipGetLastError();
@@ -371,7 +367,7 @@ extern "C" int sv_gm_encoder_backward(sv_gm_encoder* e, const sv_gm_args* a, voi
 
 // evaluation: only the per-image categorical KL term ykl (no gradients)
 extern "C" int sv_gm_encoder_y_kl(sv_gm_encoder* e, void* stream) {
-  if (!e || !e->ws) return SV_E_BADARG;
-  return sv_gumbel_softmax_bwd(nullptr, 0, e->fp("y"), e->fp("logits"), e->d.y_size, e->d.tau, 0.f, nullptr, 0, 0, e->fp("ykl"),
+  if (!e || !e->bound) return SV_E_BADARG;
+  return sv_gumbel_softmax_bwd(nullptr, 0, e->fp(B_y), e->fp(B_logits), e->d.y_size, e->d.tau, 0.f, nullptr, 0, 0, e->fp(B_ykl),
                                e->d.B, e->d.y_size, stream);
 }

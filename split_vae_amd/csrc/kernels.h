@@ -296,24 +296,26 @@ struct SvDynArgs {
   float adam_alpha;       // lr * sqrt(1 - beta2^t) / (1 - beta1^t)
   float pad;
 };
-// both networks' heads in one launch (index 0 = x, 1 = x-hat; Philox stream id = the index)
-int svk_reparam_kl_fwd_twin(const float* const* pre, const float* const* bias_mean, const float* const* bias_sd,
-                            const float* const* eps, float* const* eps_out, float* const* z_mean, float* const* z_sig,
-                            float* const* z, void* z_lp, int z_dtype, int ldz, const int* z_col, float* const* kl, int B,
-                            const int* L, uint64_t seed, uint64_t step, int64_t sample_offset, hipStream_t st,
-                            const SvDynArgs* dyn = nullptr, const int* S = nullptr, const int64_t* slab_stride = nullptr);   // S: `pre` = K-slice slabs, summed in the kernel
-int svk_reparam_kl_bwd_twin(const float* const* dz, const int* ld_dz, const float* const* dz2, const int* ld_dz2,
-                            const float* const* z_mean, const float* const* z_sig, const float* const* eps, float kl_scale,
-                            void* const* g_pre, int g_dtype, int B, const int* L, hipStream_t st,
-                            const int* S = nullptr, const int64_t* stride = nullptr, const int* S2 = nullptr, const int64_t* stride2 = nullptr);   // S: dz / dz2 = K-slice slabs
+// Sampling + KL (vae/model.py:13, vae/trainer.py:12) and its adjoint: n = 1 or 2 networks per launch (blockIdx.y), one record each
+struct ReparamFwdArgs {
+  const float *pre, *bias_mean, *bias_sd, *eps;
+  float *eps_out, *z_mean, *z_sig, *z;
+  void* z_lp;
+  float* kl;
+  int ldz, z_col, L, stream_id;    // stream_id: third word of the Philox key (j, sample_offset + b, stream_id, step)
+  int S; int64_t slab_stride;      // S > 0: `pre` is the first of S K-slice slabs of the heads' GEMM (latent_gemm.hip), summed here in slice order
+};
+struct ReparamBwdArgs {
+  const float *dz, *dz2, *z_mean, *z_sig, *eps; void* g_pre; int ld_dz, ld_dz2, L;
+  int S, S2; int64_t stride, stride2;      // S > 0: dz / dz2 are the first of S / S2 K-slice slabs of d1's input gradient, summed here in slice order
+};
+int svk_reparam_kl_fwd(const ReparamFwdArgs* a, int n, int z_dtype, int B, uint64_t seed, uint64_t step, int64_t sample_offset, hipStream_t st,
+                       const SvDynArgs* dyn = nullptr);
+int svk_reparam_kl_bwd(const ReparamBwdArgs* a, int n, float kl_scale, int g_dtype, int B, hipStream_t st);
 int svk_set_dyn(SvDynArgs* dyn, uint64_t seed, uint64_t step, int64_t sample_offset, float adam_alpha, hipStream_t st);
 double svk_adam_alpha(float lr, float beta1, float beta2, int64_t t);
 int svk_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                   float eps, int64_t t, float grad_scale, const SvDynArgs* dyn, hipStream_t st);
-int svk_reparam_kl_fwd2(const float* pre, const float* bias_mean, const float* bias_sd, const float* eps,
-                        float* eps_out, float* z_mean, float* z_sig, float* z, void* z_lp, int z_dtype, int ldz,
-                        int z_col, float* kl, int B, int L, uint64_t seed, uint64_t step, int stream_id,
-                        int64_t sample_offset, hipStream_t st, const SvDynArgs* dyn = nullptr);
 // per-image sums of P partials (fixed order): the tail of svk_dlogistic_nll_multi, also used after the fused loss epilogue
 int svk_nll_rowsum(const float* partial_ws, float* nll, int B, int P, int64_t zs_part, int64_t zs_nll, int nets, hipStream_t st);
 int svk_dlogistic_nll_multi(const float* images6, int ch_off, const float* out6, int64_t zs_out, float* nll,

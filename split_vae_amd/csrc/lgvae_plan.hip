@@ -16,6 +16,7 @@
 #include "common.hip.h"
 #include "kernels.h"
 #include "conv_geom.h"
+#include "buffer_table.h"
 
 namespace {
 
@@ -26,7 +27,41 @@ __global__ void sv_plan_spin_kernel(long long ticks) {
 }
 static void sv_plan_spin(hipStream_t st, int us) { hipLaunchKernelGGL(sv_plan_spin_kernel, dim3(1), dim3(64), 0, st, (long long)us * 100); }   // wall_clock64: 100 MHz
 
-struct Buf { std::string name; int64_t off, bytes; };
+// THE workspace buffer list: id, public name (sv_lgvae_buffer) and position in the workspace, in this order.  ONE: a single buffer.  TWIN: one kind per
+// network -- id = the x network's buffer `<name>x`, id + 1 = the x-hat network's `<name>xh` right behind it (exactly `bytes` behind when the size is a multiple of
+// 256 B, so pointwise kernels can take both as one batch of 2B: the run-time `contig` test of phase_bwd_decoders).
+// A buffer that a plan's mode lacks has NO offset and a NULL pointer (build_buffers):
+//   - global_only (GMVae) has no x-hat network and no encoder of its own: none of the x-hat buffers but in8_xh, none of a1_ .. ga1_ but gz_x.  Its phases never
+//     touch them, with ONE exception that reads the nulls on purpose: phase_loss hands nll / kl / nllpart of the x-hat network and kl_x to svk_finalize_losses,
+//     which reads a null term as zero;
+//   - polycw2_ .. polycw4_ (dW' + frame slabs of the fp32 polyphase weight gradient of dec[][2 .. 4]) exist only where svk_polyc_wgrad_ws_floats() asks for
+//     them: run_wgrad_layers takes that form only where has() says so.
+// pre_ .. gz_ are zeroed every step by ONE memset (split-K / atomic accumulation targets), gz_ alone by another: BufTable::run() at creation.
+#define LGVAE_BUFFERS(ONE, TWIN) \
+  ONE(JOBS, "jobs") ONE(WARENA, "warena") ONE(WGRAD_WS, "wgrad_ws") TWIN(POLYFIX, "polyfix_") TWIN(POLYCFIX, "polycfix_") TWIN(POLYD, "polyd_") \
+  TWIN(POLYCW2, "polycw2_") TWIN(POLYCW3, "polycw3_") TWIN(POLYCW4, "polycw4_") TWIN(POLYW, "polyw_") TWIN(LAT_WS, "lat_ws_") \
+  ONE(DYN, "dyn") ONE(LOSSES, "losses") ONE(METRIC_ACC, "metric_acc") ONE(ZCAT, "zcat") TWIN(IN8, "in8_") \
+  TWIN(A1, "a1_") TWIN(A2, "a2_") TWIN(A3, "a3_") TWIN(PRE, "pre_") TWIN(GZ, "gz_") TWIN(Z_MEAN, "z_mean_") TWIN(Z_SIG, "z_sig_") TWIN(Z, "z_") \
+  TWIN(EPS, "eps_") TWIN(KL, "kl_") TWIN(GHEAD, "ghead_") TWIN(GA3, "ga3_") TWIN(GA2, "ga2_") TWIN(GA1, "ga1_") \
+  TWIN(H1, "h1_") TWIN(H2, "h2_") TWIN(U2, "u2_") TWIN(H3, "h3_") TWIN(U3, "u3_") TWIN(H4, "h4_") TWIN(U4, "u4_") TWIN(OUT6, "out6_") TWIN(NLL, "nll_") \
+  TWIN(NLLPART, "nllpart_") TWIN(G5, "g5_") TWIN(GU4, "gu4_") TWIN(G4, "g4_") TWIN(GU3, "gu3_") TWIN(G3, "g3_") TWIN(GU2, "gu2_") TWIN(G2, "g2_") TWIN(G1, "g1_")
+enum BufId {
+#define ONE(id, name) id,
+#define TWIN(id, name) id, id##_XH,
+  LGVAE_BUFFERS(ONE, TWIN)
+#undef ONE
+#undef TWIN
+  NBUF
+};
+static_assert(POLYCW4_XH < 32, "Layer::polycw is also a bit of sv_lgvae_plan::polycw_bad");
+typedef void* const* BufPair;     // {x, x-hat} of a TWIN kind
+const char* const BUF_NAMES[NBUF] = {
+#define ONE(id, name) name,
+#define TWIN(id, name) name "x", name "xh",
+  LGVAE_BUFFERS(ONE, TWIN)
+#undef ONE
+#undef TWIN
+};
 
 struct ParamInfo { std::string name; int64_t off; int ndim; int64_t shape[4]; int64_t count; };
 
@@ -94,7 +129,8 @@ struct ProfPending { int entry; hipEvent_t a, b; };
 
 // one conv-like layer instance with everything needed for fwd / dgrad / wgrad
 struct Layer {
-  std::string name;
+  std::string ln, sc_fwd, sc_dgrad, sc_wgrad, sc_reduce;   // "d4" and its profile scopes "fwd.d4", "dgrad.d4", "wgrad.d4", "wgrad.d4.reduce" (build_layers)
+  int polycw = -1;              // dec[][2 .. 4]: the TWIN id of its polyphase weight-gradient workspace (POLYCW2 ..), which the plan may lack; and its bit in polycw_bad
   sv_conv_desc d;
   int kparam, bparam;           // indices into the param table (kernel, bias); head uses two kernels
   int64_t wf_off;               // prepared forward weights (element offset in arena)
@@ -111,10 +147,7 @@ struct sv_lgvae_plan {
   sv_lgvae_desc d;
   std::vector<ParamInfo> params;
   int64_t nparams;
-  std::vector<Buf> bufs;
-  std::map<std::string, int> bufidx;
-  int64_t ws_bytes;
-  char* ws;
+  BufTable<NBUF> bufs{BUF_NAMES};
   bool bound;
   // layers: [enc_x e1,e2,e3,head][enc_xh ...][dec_x d1..d5][dec_xh ...]
   Layer enc[2][4];
@@ -129,7 +162,7 @@ struct sv_lgvae_plan {
   bool dz_slabs = false;
   bool dz_valid = false;        // the decoders' backward has run since the last encoder forward (dz is what reparam_kl_bwd may read)
   bool gz_zero_skipped = false; // that forward did not zero dz (slab path): an encoder backward WITHOUT the decoders' (KL terms only) zeroes it first
-  unsigned polycw_bad = 0;      // decoder layers (bit = index in dec[]) whose polyphase weight gradient was refused once: not tried again (one profile scope per launch)
+  unsigned polycw_bad = 0;      // decoder layers (bit = Layer::polycw) whose polyphase weight gradient was refused once: not tried again (one profile scope per launch)
   bool lat_head_ok = false, lat_d1_ok = false;     // the heads' forward / d1's input gradient of this plan run on latent_gemm.hip (shapes are fixed per plan)
   int dz_S[2] = {0, 0};
   int64_t dz_stride[2] = {0, 0};
@@ -282,19 +315,11 @@ struct sv_lgvae_plan {
   size_t esz() const { return d.dtype == SV_BF16 ? 2 : 4; }
   int ndec() const { return d.global_only ? 1 : 2; }                       // decoders (and x / x-hat networks) the plan runs
   int lc() const { return d.global_only ? d.global_latent : d.global_latent + d.local_latent; }   // decoder_x's input width = zcat / gz_x pitch
-  int64_t add_buf(const std::string& n, int64_t bytes) {
-    Buf b;
-    b.name = n; b.off = ws_bytes; b.bytes = bytes;
-    ws_bytes += (bytes + 255) / 256 * 256;
-    bufidx[n] = (int)bufs.size();
-    bufs.push_back(b);
-    return b.off;
-  }
-  void* bp(const std::string& n) const {
-    auto it = bufidx.find(n);
-    return it == bufidx.end() ? nullptr : (void*)(ws + bufs[it->second].off);
-  }
-  int64_t bbytes(const std::string& n) const { return bufs[bufidx.at(n)].bytes; }
+  // k picks the network of a TWIN buffer: 0 = x, 1 = x-hat
+  void* buf(int id, int k = 0) const { return bufs.ptr[id + k]; }
+  BufPair pair(int id) const { return &bufs.ptr[id]; }                   // as the twin launches take them
+  float* const* fpair(int id) const { return (float* const*)pair(id); }
+  int64_t bbytes(int id, int k = 0) const { return bufs.bytes[id + k]; }
 };
 
 namespace {
@@ -329,7 +354,7 @@ struct Scope {   // hipEvent bracket around one launch when profiling is on
     else (void)hipEventCreate(&e);
     return e;
   }
-  int find(const std::string& name, double flops, double bytes) {
+  int find(const char* name, double flops, double bytes) {
     auto it = p->profidx.find(name);
     if (it != p->profidx.end()) return it->second;
     const int e = (int)p->prof.size();
@@ -339,8 +364,9 @@ struct Scope {   // hipEvent bracket around one launch when profiling is on
   }
   bool marked = false;
   void issued(double fl) { if (entry >= 0) p->prof[entry].issued = fl; }      // the launch set runs a strength-reduced form: FLOPs it really multiplies
-  Scope(sv_lgvae_plan* p_, hipStream_t st_, const std::string& name, double flops, double bytes) : p(p_), st(st_), on(p_->prof_on) {
-    if (roctx().push) { roctx().push(name.c_str()); marked = true; }
+  Scope(sv_lgvae_plan* p_, hipStream_t st_, const std::string& name, double flops, double bytes) : Scope(p_, st_, name.c_str(), flops, bytes) {}
+  Scope(sv_lgvae_plan* p_, hipStream_t st_, const char* name, double flops, double bytes) : p(p_), st(st_), on(p_->prof_on) {   // (a literal or a Layer's name: no string is built unless profiling books one)
+    if (roctx().push) { roctx().push(name); marked = true; }
     if (on && !p->prof_filter.empty() && p->prof_filter != name) on = false;
     if (!on) return;
     entry = find(name, flops, bytes);
@@ -354,7 +380,7 @@ struct Scope {   // hipEvent bracket around one launch when profiling is on
     if (!p->prof_on) return;
     on2 = p->prof_filter.empty() || p->prof_filter == name2;
     if (!on && !on2) return;
-    if (on2) entry2 = find(name2, 0, bytes2);
+    if (on2) entry2 = find(name2.c_str(), 0, bytes2);
     m1 = ev[0] = get(); m2 = ev[1] = get();
     if (!b) b = get();
   }
@@ -377,7 +403,7 @@ static void build_layers(sv_lgvae_plan* p) {
   auto mk = [&](const std::string& name, int h, int w, int cin, int cout, int k, int s, int act, int ldx,
                 int ldy, int yf32, int kparam, bool need_dgrad) {
     Layer L;
-    L.name = name;
+    L.ln = name; L.sc_fwd = "fwd." + name; L.sc_dgrad = "dgrad." + name; L.sc_wgrad = "wgrad." + name; L.sc_reduce = L.sc_wgrad + ".reduce";
     L.d = sv_conv_desc{B, h, w, cin, cout, k, k, s, act, d.dtype, ldx, ldy, yf32, 0};
     L.kparam = kparam; L.bparam = kparam + 1; L.need_dgrad = need_dgrad;
     L.wf_off = 0; L.wdp_off = -1; L.polyc = false;
@@ -387,28 +413,27 @@ static void build_layers(sv_lgvae_plan* p) {
   for (int e = 0; e < 2 && !d.global_only; ++e) {
     const int pb = e * 10;
     const int L = e == 0 ? Lg : Ll;
-    const std::string pre = e == 0 ? "enc_x." : "enc_xh.";
-    p->enc[e][0] = mk(pre + "e1", H, W, 3, 32, 6, 2, SV_ACT_RELU, 8, 32, 0, pb + 0, false);
-    p->enc[e][1] = mk(pre + "e2", H / 2, W / 2, 32, 64, 6, 2, SV_ACT_RELU, 32, 64, 0, pb + 2, true);
-    p->enc[e][2] = mk(pre + "e3", H / 4, W / 4, 64, 128, 4, 2, SV_ACT_RELU, 64, 128, 0, pb + 4, true);
+    p->enc[e][0] = mk("e1", H, W, 3, 32, 6, 2, SV_ACT_RELU, 8, 32, 0, pb + 0, false);
+    p->enc[e][1] = mk("e2", H / 2, W / 2, 32, 64, 6, 2, SV_ACT_RELU, 32, 64, 0, pb + 2, true);
+    p->enc[e][2] = mk("e3", H / 4, W / 4, 64, 128, 4, 2, SV_ACT_RELU, 64, 128, 0, pb + 4, true);
     // e4_mean | e4_sd as ONE dense GEMM with N = 2L (vae/model.py:41-42,:111-112)
-    p->enc[e][3] = mk(pre + "head", 1, 1, F, 2 * L, 1, 1, SV_ACT_NONE, F, 2 * L, 1, pb + 6, true);
+    p->enc[e][3] = mk("head", 1, 1, F, 2 * L, 1, 1, SV_ACT_NONE, F, 2 * L, 1, pb + 6, true);
   }
   for (int k = 0; k < p->ndec(); ++k) {
     const int pb = d.global_only ? 0 : 20 + k * 10;
     const int Lz = k == 0 ? p->lc() : Ll;
-    const std::string pre = k == 0 ? "dec_x." : "dec_xh.";
-    p->dec[k][0] = mk(pre + "d1", 1, 1, Lz, F, 1, 1, SV_ACT_RELU, p->lc(), F, 0, pb + 0, true);
-    p->dec[k][1] = mk(pre + "d2", H / 8, W / 8, 128, 128, 4, 1, SV_ACT_RELU, 128, 128, 0, pb + 2, true);
-    p->dec[k][2] = mk(pre + "d3", H / 4, W / 4, 128, 64, 4, 1, SV_ACT_RELU, 128, 64, 0, pb + 4, true);
-    p->dec[k][3] = mk(pre + "d4", H / 2, W / 2, 64, 32, 6, 1, SV_ACT_RELU, 64, 32, 0, pb + 6, true);
-    p->dec[k][4] = mk(pre + "d5", H, W, 32, 6, 6, 1, SV_ACT_NONE, 32, 6, 1, pb + 8, true);
+    p->dec[k][0] = mk("d1", 1, 1, Lz, F, 1, 1, SV_ACT_RELU, p->lc(), F, 0, pb + 0, true);
+    p->dec[k][1] = mk("d2", H / 8, W / 8, 128, 128, 4, 1, SV_ACT_RELU, 128, 128, 0, pb + 2, true);
+    p->dec[k][2] = mk("d3", H / 4, W / 4, 128, 64, 4, 1, SV_ACT_RELU, 128, 64, 0, pb + 4, true);
+    p->dec[k][3] = mk("d4", H / 2, W / 2, 64, 32, 6, 1, SV_ACT_RELU, 64, 32, 0, pb + 6, true);
+    p->dec[k][4] = mk("d5", H, W, 32, 6, 6, 1, SV_ACT_NONE, 32, 6, 1, pb + 8, true);
     // the three bilinear resizes are fused into the staging of d3/d4/d5's forward and wgrad tiles (needs >= 16 output pixels per image for
     // the tile kernels: any H >= 16 here); fp32 since round 4 too (wgrad_tile_f32.hip; SV_F32_MATERIALISE_UPSAMPLE=1: u2 / u3 / u4 written out)
     static const bool no_fuse = SV_TUNE_FLAG("SV_NO_FUSED_UPSAMPLE");
     static const bool f32_mat = SV_TUNE_FLAG("SV_F32_MATERIALISE_UPSAMPLE");
     if ((d.dtype == SV_BF16 || !f32_mat) && !no_fuse && H >= 16)
       for (int l = 2; l <= 4; ++l) p->dec[k][l].d.ups_in = 1;
+    for (int l = 2; l <= 4; ++l) p->dec[k][l].polycw = POLYCW2 + 2 * (l - 2);
   }
 }
 
@@ -450,16 +475,6 @@ static void build_prep_jobs(sv_lgvae_plan* p) {
       jf.src_off = p->params[L.kparam].off; jf.dst_off = arena;
       arena += svg_polyc_fix_elems(&L.d);
       push(jf);
-      if (L.need_dgrad)
-        for (int c = 0; c < svg_dgrad_classes(&L.d); ++c) {
-          PrepJob jd;
-          svg_prep_job_dgrad(&L.d, c, &jd);
-          jd.src_off = p->params[L.kparam].off;
-          align(); L.wd_off[c] = arena; jd.dst_off = arena;
-          arena += (int64_t)jd.rows * jd.ntaps * jd.inner;
-          push(jd);
-        }
-      polyd_jobs(L);
     } else if (!is_head) {
       PrepJob j;
       svg_prep_job_fwd(&L.d, &j);
@@ -475,6 +490,8 @@ static void build_prep_jobs(sv_lgvae_plan* p) {
         arena += (int64_t)jf.rows * jf.ntaps * jf.inner;
         push(jf);
       }
+    }
+    if (!is_head) {                                       // the input gradient keeps its own forms whichever forward image was prepared
       if (L.need_dgrad)
         for (int c = 0; c < svg_dgrad_classes(&L.d); ++c) {
           PrepJob jd;
@@ -524,39 +541,40 @@ static void build_prep_jobs(sv_lgvae_plan* p) {
   p->prep_blocks = blocks;
 }
 
+// sizes by id; LGVAE_BUFFERS gives the positions (the order of the statements here gives nothing)
 static void build_buffers(sv_lgvae_plan* p) {
   const sv_lgvae_desc& d = p->d;
   const int64_t B = d.B, H = d.H, W = d.W, es = (int64_t)p->esz();
   const int64_t F = (H / 8) * (W / 8) * 128;
   const int Lg = d.global_latent, Ll = d.local_latent, Lc = p->lc();
   const bool go = d.global_only;           // GMVae: no x-hat network, no encoder of the plan's own -- none of their buffers
-  p->ws_bytes = 0;
-  p->add_buf("jobs", (int64_t)p->jobs.size() * sizeof(PrepJob));
-  p->add_buf("warena", p->arena_elems * es);
-  p->add_buf("wgrad_ws", SV_WGRAD_WS_BYTES * SV_WGRAD_MAX_MULTI * sv_lgvae_plan::SIDE_MAX);   // per side stream, per problem
-  p->add_buf("polyfix_x", svk_poly_fix_ws_bytes((int)B, (int)H / 2, (int)W / 2));   // border terms of the polyphase head (poly_fix.hip)
-  if (!go) p->add_buf("polyfix_xh", svk_poly_fix_ws_bytes((int)B, (int)H / 2, (int)W / 2));
+  int64_t sz[NBUF];
+  for (auto& v : sz) v = -1;
+  auto twin = [&](int id, int64_t bytes_x, int64_t bytes_xh) {
+    sz[id] = bytes_x;
+    if (!go) sz[id + 1] = bytes_xh;
+  };
+  auto same = [&](int id, int64_t bytes) { twin(id, bytes, bytes); };
+  sz[JOBS] = (int64_t)p->jobs.size() * sizeof(PrepJob);
+  sz[WARENA] = p->arena_elems * es;
+  sz[WGRAD_WS] = SV_WGRAD_WS_BYTES * SV_WGRAD_MAX_MULTI * sv_lgvae_plan::SIDE_MAX;   // per side stream, per problem
+  same(POLYFIX, svk_poly_fix_ws_bytes((int)B, (int)H / 2, (int)W / 2));   // border terms of the polyphase head (poly_fix.hip)
   {   // border terms of the per-class polyphase layers (d3, d4): one region per network, sized for the largest layer (the layers run one after the other)
     int64_t need = 256;
     for (int l = 2; l <= 4; ++l)
       if (p->dec[0][l].polyc) need = std::max<int64_t>(need, svg_polyc_fix_ws_bytes(&p->dec[0][l].d));
-    p->add_buf("polycfix_x", need);
-    if (!go) p->add_buf("polycfix_xh", need);
+    same(POLYCFIX, need);
     int64_t needd = 256;                                  // edge terms of the polyphase input gradients (d4, d5): one region per network
     for (int l = 2; l <= 4; ++l)
       if (svg_polyd(&p->dec[0][l].d)) needd = std::max<int64_t>(needd, svg_polyd_ws_bytes(&p->dec[0][l].d));
-    p->add_buf("polyd_x", needd);
-    if (!go) p->add_buf("polyd_xh", needd);
+    same(POLYD, needd);
     // polyphase weight gradients at fp32 (polyc_wgrad.hip): dW' + frame slabs per layer and network (the layers' launches may overlap across streams)
     for (int l = 2; l <= 4; ++l) {
       const int64_t fl = svk_polyc_wgrad_ws_floats(&p->dec[0][l].d);
-      if (!fl) continue;
-      p->add_buf("polycw" + std::to_string(l) + "_x", fl * 4);
-      if (!go) p->add_buf("polycw" + std::to_string(l) + "_xh", fl * 4);
+      if (fl) same(p->dec[0][l].polycw, fl * 4);
     }
   }
-  p->add_buf("polyw_x", svk_poly_wgrad_ws_floats(32, SV_POLY_WGRAD_NWG) * 4);        // polyphase weight gradient of the head: dW', dbias', frame slabs
-  if (!go) p->add_buf("polyw_xh", svk_poly_wgrad_ws_floats(32, SV_POLY_WGRAD_NWG) * 4);
+  same(POLYW, svk_poly_wgrad_ws_floats(32, SV_POLY_WGRAD_NWG) * 4);        // polyphase weight gradient of the head: dW', dbias', frame slabs
   {   // K-slice slabs of the heads' forward and d1's input gradient (latent_gemm.hip): [S][B][N] fp32 per network
     const int64_t Fd = (H / 8) * (W / 8) * 128;
     // the four launches that write them -- heads of x / x-hat (N = 2 Lg / 2 Ll), d1's input gradient of decoder_x / decoder_x-hat (N = Lg + Ll / Ll) --
@@ -569,60 +587,50 @@ static void build_buffers(sv_lgvae_plan* p) {
       need = b > need ? b : need;
     }
     if (go) need = (int64_t)svk_nt_gemm_pick_splitk((int)B, Lc, (int)Fd, 2) * B * Lc * 4;    // d1's input gradient only (N = Lg)
-    p->add_buf("lat_ws_x", need);
-    if (!go) p->add_buf("lat_ws_xh", need);
+    same(LAT_WS, need);
   }
-  p->add_buf("dyn", sizeof(SvDynArgs));
-  p->add_buf("losses", 8 * 4);
-  p->add_buf("metric_acc", 8 * 4);
-  p->add_buf("zcat", B * Lc * es);
-  // per-network buffers: the x and x-hat twins of one kind are adjacent (x-hat exactly `bytes` after x
-  // when the size is a multiple of 256 B), so pointwise kernels can take both as one batch of 2B
-  auto twin = [&](const char* kind, int64_t bytes_x, int64_t bytes_xh) {
-    p->add_buf(std::string(kind) + "x", bytes_x);
-    if (!go) p->add_buf(std::string(kind) + "xh", bytes_xh);
-  };
-  auto same = [&](const char* kind, int64_t bytes) { twin(kind, bytes, bytes); };
-  p->add_buf("in8_x", B * H * W * 8 * es);
-  p->add_buf("in8_xh", B * H * W * 8 * es);      // (global_only too: the split pass and the staged augmentation write both halves of images6)
+  sz[DYN] = sizeof(SvDynArgs);
+  sz[LOSSES] = sz[METRIC_ACC] = 8 * 4;
+  sz[ZCAT] = B * Lc * es;
+  sz[IN8] = sz[IN8_XH] = B * H * W * 8 * es;     // (global_only too: the split pass and the staged augmentation write both halves of images6)
   if (go) {
-    p->add_buf("gz_x", B * Lc * 4);              // dL/dz_x for the caller's encoder
+    sz[GZ] = B * Lc * 4;                         // dL/dz_x for the caller's encoder
   } else {
-    same("a1_", B * (H / 2) * (W / 2) * 32 * es);
-    same("a2_", B * (H / 4) * (W / 4) * 64 * es);
-    same("a3_", B * F * es);
-    // zeroed every step by ONE memset (split-K / atomic accumulation targets): pre_x .. gz_xh are adjacent
-    twin("pre_", B * 2 * Lg * 4, B * 2 * Ll * 4);
-    twin("gz_", B * Lc * 4, B * Ll * 4);
-    twin("z_mean_", B * Lg * 4, B * Ll * 4);
-    twin("z_sig_", B * Lg * 4, B * Ll * 4);
-    twin("z_", B * Lg * 4, B * Ll * 4);
-    twin("eps_", B * Lg * 4, B * Ll * 4);
-    same("kl_", B * 4);
-    twin("ghead_", B * 2 * Lg * es, B * 2 * Ll * es);
-    same("ga3_", B * F * es);
-    same("ga2_", B * (H / 4) * (W / 4) * 64 * es);
-    same("ga1_", B * (H / 2) * (W / 2) * 32 * es);
+    same(A1, B * (H / 2) * (W / 2) * 32 * es);
+    same(A2, B * (H / 4) * (W / 4) * 64 * es);
+    same(A3, B * F * es);
+    twin(PRE, B * 2 * Lg * 4, B * 2 * Ll * 4);
+    twin(GZ, B * Lc * 4, B * Ll * 4);
+    twin(Z_MEAN, B * Lg * 4, B * Ll * 4);
+    twin(Z_SIG, B * Lg * 4, B * Ll * 4);
+    twin(Z, B * Lg * 4, B * Ll * 4);
+    twin(EPS, B * Lg * 4, B * Ll * 4);
+    same(KL, B * 4);
+    twin(GHEAD, B * 2 * Lg * es, B * 2 * Ll * es);
+    same(GA3, B * F * es);
+    same(GA2, B * (H / 4) * (W / 4) * 64 * es);
+    same(GA1, B * (H / 2) * (W / 2) * 32 * es);
   }
   // decoders
-  same("h1_", B * F * es);
-  same("h2_", B * F * es);
-  same("u2_", B * (H / 4) * (W / 4) * 128 * es);
-  same("h3_", B * (H / 4) * (W / 4) * 64 * es);
-  same("u3_", B * (H / 2) * (W / 2) * 64 * es);
-  same("h4_", B * (H / 2) * (W / 2) * 32 * es);
-  same("u4_", B * H * W * 32 * es);
-  same("out6_", B * H * W * 6 * 4);
-  same("nll_", B * 4);
-  same("nllpart_", sv_dlogistic_nll_workspace_bytes((int)B, (int)H, (int)W));
-  same("g5_", B * H * W * 8 * es);
-  same("gu4_", B * H * W * 32 * es);
-  same("g4_", B * (H / 2) * (W / 2) * 32 * es);
-  same("gu3_", B * (H / 2) * (W / 2) * 64 * es);
-  same("g3_", B * (H / 4) * (W / 4) * 64 * es);
-  same("gu2_", B * (H / 4) * (W / 4) * 128 * es);
-  same("g2_", B * F * es);
-  same("g1_", B * F * es);
+  same(H1, B * F * es);
+  same(H2, B * F * es);
+  same(U2, B * (H / 4) * (W / 4) * 128 * es);
+  same(H3, B * (H / 4) * (W / 4) * 64 * es);
+  same(U3, B * (H / 2) * (W / 2) * 64 * es);
+  same(H4, B * (H / 2) * (W / 2) * 32 * es);
+  same(U4, B * H * W * 32 * es);
+  same(OUT6, B * H * W * 6 * 4);
+  same(NLL, B * 4);
+  same(NLLPART, sv_dlogistic_nll_workspace_bytes((int)B, (int)H, (int)W));
+  same(G5, B * H * W * 8 * es);
+  same(GU4, B * H * W * 32 * es);
+  same(G4, B * (H / 2) * (W / 2) * 32 * es);
+  same(GU3, B * (H / 2) * (W / 2) * 64 * es);
+  same(G3, B * (H / 4) * (W / 4) * 64 * es);
+  same(GU2, B * (H / 4) * (W / 4) * 128 * es);
+  same(G2, B * F * es);
+  same(G1, B * F * es);
+  p->bufs.layout(sz);
 }
 
 // the latent block's GEMMs on latent_gemm.hip (LDS-DMA phases, split-K through fp32 slabs summed in slice order) instead of the im2col
@@ -681,7 +689,7 @@ static int run_fwd_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void* 
   for (int i = 0; i < n; ++i) {
     svg_fwd_args(&L[i]->d, &a[i]);
     a[i].A = x[i];
-    a[i].Wt = (char*)p->bp("warena") + L[i]->wf_off * p->esz();
+    a[i].Wt = (char*)p->buf(WARENA) + L[i]->wf_off * p->esz();
     a[i].bias = params + p->params[L[i]->bparam].off;
     a[i].out = y[i];
     if (nll) {
@@ -691,7 +699,7 @@ static int run_fwd_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void* 
     fl += conv_flops(L[i]->d);
     by += conv_bytes(L[i]->d, 0, p->esz());
   }
-  Scope sc(p, st, "fwd." + L[0]->name.substr(L[0]->name.find('.') + 1), fl, by);
+  Scope sc(p, st, L[0]->sc_fwd, fl, by);
   if (latent_gemm_on(p) && !nll && L[0]->d.H == 1 && L[0]->d.W == 1 && L[0]->d.KH == 1 && !L[0]->d.y_f32) {   // Dense (d1): latent_gemm.hip
     NtGemmProb q[2];
     for (int i = 0; i < n; ++i) {
@@ -713,29 +721,22 @@ static int run_fwd_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void* 
     // per-class polyphase (d4, d3): border kernel, then the four class problems of both networks in one launch
     const void* wf[2];
     const float* bs[2];
-    void* fws[2] = {p->bp("polycfix_x"), p->bp("polycfix_xh")};
     for (int i = 0; i < n; ++i) { wf[i] = a[i].Wt; bs[i] = a[i].bias; }
-    return svk_polyc_fwd_multi(&L[0]->d, n, x, wf, bs, y, fws, st);
+    return svk_polyc_fwd_multi(&L[0]->d, n, x, wf, bs, y, p->pair(POLYCFIX), st);
   }
   if (svg_poly(&L[0]->d)) {
     { double is = 0; for (int i = 0; i < n; ++i) is += poly_issued(L[i]->d, 100, false); sc.issued(is); }
     // polyphase head: the out-of-image taps of the border rows / columns go to a workspace first; the conv's epilogue adds them
     const void* wfix[2];
-    float* fixbuf[2];
-    static const char* fb_name[2] = {"polyfix_x", "polyfix_xh"};
+    float* const* fixbuf = p->fpair(POLYFIX);
     const sv_conv_desc& d = L[0]->d;
     for (int i = 0; i < n; ++i) {
       wfix[i] = (const char*)a[i].Wt + (int64_t)32 * 25 * svg_cin_pad(&L[i]->d) * p->esz();
-      fixbuf[i] = (float*)p->bp(fb_name[i]);
       a[i].fix = fixbuf[i];
     }
     SV_TRY(svk_poly_fix_multi(n, x, wfix, nullptr, fixbuf, d.B, d.H / 2, d.W / 2, d.ldx, d.Cout, st, d.dtype));
   }
   return svk_conv_dispatch_multi(a, n, L[0]->d.dtype, svg_pick_cfg(L[0]->d.Cout), st);
-}
-static int run_fwd_layer(sv_lgvae_plan* p, Layer& L, const void* x, const float* params, void* y, hipStream_t st) {
-  Layer* Lp = &L;
-  return run_fwd_layers(p, 1, &Lp, &x, params, &y, st);
 }
 
 // all parity classes of all n twin layers in one launch (stride 2: 4 classes x 2 networks = 8 problems)
@@ -751,11 +752,11 @@ static int run_dgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
     bool ok = true;
     for (int i = 0; i < n && ok; ++i) {
       ok = svg_dgrad_merged_args(&L[i]->d, L[i]->wd_off, &a[i]);
-      a[i].A = dy[i]; a[i].Wt = (char*)p->bp("warena") + L[i]->wd_off[0] * p->esz(); a[i].out = dx[i]; a[i].mask = mask[i];
+      a[i].A = dy[i]; a[i].Wt = (char*)p->buf(WARENA) + L[i]->wd_off[0] * p->esz(); a[i].out = dx[i]; a[i].mask = mask[i];
       fl += conv_flops(L[i]->d);
     }
     if (ok) {
-      Scope sc(p, st, "dgrad." + L[0]->name.substr(L[0]->name.find('.') + 1), fl, by);
+      Scope sc(p, st, L[0]->sc_dgrad, fl, by);
       const int rc = svk_conv_dispatch_multi(a, n, L[0]->d.dtype, svg_pick_cfg(a[0].N), st);
       if (rc != SV_E_UNSUPPORTED) return rc;
     }
@@ -767,7 +768,7 @@ static int run_dgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
       uint8_t srctap[SV_MAX_TAPS];
       svg_dgrad_args(&L[i]->d, c, &a[m], srctap);
       a[m].A = dy[i];
-      a[m].Wt = (char*)p->bp("warena") + L[i]->wd_off[c] * p->esz();
+      a[m].Wt = (char*)p->buf(WARENA) + L[i]->wd_off[c] * p->esz();
       a[m].out = dx[i];
       a[m].mask = mask[i];
       a[m].adj = adj ? 1 : 0;           // dx = the LOW-RES gradient, mask = the low-res activation (row_conv.hip)
@@ -784,7 +785,7 @@ static int run_dgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
   if (adj) {                            // no fused kernel for this geometry: nothing was launched, the caller falls back
     if (!svk_row_conv_supported(a, m, L[0]->d.dtype)) return SV_E_UNSUPPORTED;
   }
-  Scope sc(p, st, "dgrad." + L[0]->name.substr(L[0]->name.find('.') + 1), fl, by);
+  Scope sc(p, st, L[0]->sc_dgrad, fl, by);
   if (mixed) {   // split-K problems whose widths pick different tiles: one launch each
     for (int i = 0; i < m; ++i) {
       int c2 = svg_pick_cfg(L[0]->d.Cin);
@@ -796,19 +797,14 @@ static int run_dgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
   // the classes of a stride-2 layer have different tap counts but plan to the same tile grid
   return svk_conv_dispatch_multi(a, m, L[0]->d.dtype, tap_cfg, st);
 }
-static int run_dgrad_layer(sv_lgvae_plan* p, Layer& L, const void* dy, const void* mask, void* dx, bool f32_atomic,
-                           hipStream_t st) {
-  Layer* Lp = &L;
-  return run_dgrad_layers(p, 1, &Lp, &dy, &mask, &dx, f32_atomic, st);
-}
 
 static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void* const* x, const void* const* dy,
                             float* grads, hipStream_t st) {
   WgradArgs a[SV_WGRAD_MAX_MULTI];
   double fl = 0, by = 0;
   for (int i = 0; i < n; ++i) by += conv_bytes(L[i]->d, 2, p->esz());
-  const int64_t wsb = p->bbytes("wgrad_ws") / (SV_WGRAD_MAX_MULTI * sv_lgvae_plan::SIDE_MAX);   // one partial-sum slab region per stream and problem
-  const std::string ln = L[0]->name.substr(L[0]->name.find('.') + 1), nm = "wgrad." + ln;
+  const int64_t wsb = p->bbytes(WGRAD_WS) / (SV_WGRAD_MAX_MULTI * sv_lgvae_plan::SIDE_MAX);   // one partial-sum slab region per stream and problem
+  const std::string &ln = L[0]->ln, &nm = L[0]->sc_wgrad;
   // layers named in SV_WGRAD_MAIN keep their weight gradient on the main stream.  Measured (B = 512, 64x64): the side stream is
   // the critical path of the backward pass (it ends ~0.3 ms after the last input gradient), and d5's weight gradient slows the
   // concurrent d4 input gradient 2.5x; with d5 and the two tail layers e1, e2 on the main stream the step is 1.4 % shorter
@@ -858,15 +854,13 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
   static const int pw_min = SV_TUNE_INT("SV_POLY_WGRAD_MIN", 512);
   if (!no_pw && L[0]->d.dtype == SV_BF16 && svg_poly(&L[0]->d) && n * L[0]->d.B >= pw_min && n <= 2 &&
       svk_poly_wgrad_supported(L[0]->d.H / 2, L[0]->d.W / 2, svg_cin_pad(&L[0]->d), L[0]->d.Cout)) {   // else: the direct form below
-    static const char* pw_name[2] = {"polyw_x", "polyw_xh"};
-    float* pw[2];
+    float* const* pw = p->fpair(POLYW);
     float *dwv[2], *dbv[2];
     const int Cin = svg_cin_pad(&L[0]->d);
     for (int i = 0; i < n; ++i) {
       svg_poly_wgrad_args(&L[i]->d, &a[i]);
-      pw[i] = (float*)p->bp(pw_name[i]);
       a[i].A = x[i]; a[i].dY = dy[i]; a[i].dW = pw[i]; a[i].dbias = pw[i] + 25 * Cin * 32;
-      a[i].ws = (float*)((char*)p->bp("wgrad_ws") + (p->side_slot * SV_WGRAD_MAX_MULTI + i) * wsb); a[i].ws_bytes = wsb;
+      a[i].ws = (float*)((char*)p->buf(WGRAD_WS) + (p->side_slot * SV_WGRAD_MAX_MULTI + i) * wsb); a[i].ws_bytes = wsb;
       dwv[i] = grads + p->params[L[i]->kparam].off; dbv[i] = grads + p->params[L[i]->bparam].off;
       fl += conv_flops(L[i]->d);
     }
@@ -878,21 +872,19 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
   }
   // fp32: the polyphase weight gradient of the upsample -> conv layers (polyc_wgrad.hip: d4 per parity class, the head merged)
   static const int pcw_min = SV_TUNE_INT("SV_POLYC_WGRAD_MIN", 0);
-  if (L[0]->d.dtype == SV_F32 && n <= 2 && n * L[0]->d.B >= pcw_min && svg_polyc_wgrad_form(&L[0]->d) && !(p->polycw_bad >> (ln[1] - '0' - 1) & 1) &&
-      p->bufidx.count("polycw" + std::to_string(ln[1] - '0' - 1) + "_x")) {
-    const std::string base = "polycw" + std::to_string(ln[1] - '0' - 1);          // layer name d<k>: index k - 1 in dec[]
-    float *dwv[2], *dbv[2], *slab[2], *pw[2];
+  if (L[0]->d.dtype == SV_F32 && n <= 2 && n * L[0]->d.B >= pcw_min && svg_polyc_wgrad_form(&L[0]->d) && L[0]->polycw >= 0 &&
+      !(p->polycw_bad >> L[0]->polycw & 1) && p->bufs.has(L[0]->polycw)) {       // (has: the one workspace a plan may lack by its shapes, see LGVAE_BUFFERS)
+    float *dwv[2], *dbv[2], *slab[2];
     for (int i = 0; i < n; ++i) {
       dwv[i] = grads + p->params[L[i]->kparam].off; dbv[i] = grads + p->params[L[i]->bparam].off;
-      slab[i] = (float*)((char*)p->bp("wgrad_ws") + (p->side_slot * SV_WGRAD_MAX_MULTI + i) * wsb);
-      pw[i] = (float*)p->bp(base + (i == 0 ? "_x" : "_xh"));
+      slab[i] = (float*)((char*)p->buf(WGRAD_WS) + (p->side_slot * SV_WGRAD_MAX_MULTI + i) * wsb);
       fl += conv_flops(L[i]->d);
     }
     Scope sc(p, st, nm, fl, by);
     { double is = 0; for (int i = 0; i < n; ++i) is += poly_issued(L[i]->d, svg_polyc_wgrad_form(&L[i]->d) == 2 ? 100 : 81, false); sc.issued(is); }
-    const int rc = svk_polyc_wgrad_multi(&L[0]->d, n, x, dy, dwv, dbv, slab, wsb, pw, st);
+    const int rc = svk_polyc_wgrad_multi(&L[0]->d, n, x, dy, dwv, dbv, slab, wsb, p->fpair(L[0]->polycw), st);
     if (rc != SV_E_UNSUPPORTED) return rc;
-    p->polycw_bad |= 1u << (ln[1] - '0' - 1);
+    p->polycw_bad |= 1u << L[0]->polycw;
     fl = 0;
   }
   // (every layer reduces its own slabs on its own stream.  One reduce for all layers after the join was measured and removed: profiles/r03_f_defer.txt,
@@ -902,26 +894,22 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
     a[i].A = x[i]; a[i].dY = dy[i];
     a[i].dW = grads + p->params[L[i]->kparam].off;
     a[i].dbias = grads + p->params[L[i]->bparam].off;
-    a[i].ws = (float*)((char*)p->bp("wgrad_ws") + (p->side_slot * SV_WGRAD_MAX_MULTI + i) * wsb); a[i].ws_bytes = wsb;
+    a[i].ws = (float*)((char*)p->buf(WGRAD_WS) + (p->side_slot * SV_WGRAD_MAX_MULTI + i) * wsb); a[i].ws_bytes = wsb;
     fl += conv_flops(L[i]->d);
   }
   Scope sc(p, st, nm, fl, by);
   sc.issued(fl);                        // (a polyphase form above may have been refused after booking its count)
-  sc.split(nm + ".reduce", 0, a[0].ev_mid);
+  sc.split(L[0]->sc_reduce, 0, a[0].ev_mid);
   return svk_wgrad_dispatch_multi(a, n, L[0]->d.dtype, svg_pick_cfg(L[0]->d.Cout), st);
-}
-static int run_wgrad_layer(sv_lgvae_plan* p, Layer& L, const void* x, const void* dy, float* grads, hipStream_t st) {
-  Layer* Lp = &L;
-  return run_wgrad_layers(p, 1, &Lp, &x, &dy, grads, st);
 }
 
 // early: side stream 0 (sv_lgvae_plan::early_stream) or nullptr -- the decoders' half of the job table goes there, the encoders' half stays in front of their forward
 static int phase_prep(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t st, hipStream_t early) {
   Scope sc(p, st, "prep_weights", 0, (double)p->nparams * (4 + 2.0 * p->esz()));
-  const PrepJob* jobs = (const PrepJob*)p->bp("jobs");
-  if (!early || p->dec_block0 == 0) return svk_prep_weights(s->params, p->bp("warena"), p->d.dtype, jobs, (int)p->jobs.size(), p->prep_blocks, st);
-  SV_TRY(svk_prep_weights(s->params, p->bp("warena"), p->d.dtype, jobs, (int)p->jobs.size(), p->prep_blocks - p->dec_block0, early, p->dec_block0));
-  return svk_prep_weights(s->params, p->bp("warena"), p->d.dtype, jobs, (int)p->jobs.size(), p->dec_block0, st);
+  const PrepJob* jobs = (const PrepJob*)p->buf(JOBS);
+  if (!early || p->dec_block0 == 0) return svk_prep_weights(s->params, p->buf(WARENA), p->d.dtype, jobs, (int)p->jobs.size(), p->prep_blocks, st);
+  SV_TRY(svk_prep_weights(s->params, p->buf(WARENA), p->d.dtype, jobs, (int)p->jobs.size(), p->prep_blocks - p->dec_block0, early, p->dec_block0));
+  return svk_prep_weights(s->params, p->buf(WARENA), p->d.dtype, jobs, (int)p->jobs.size(), p->dec_block0, st);
 }
 
 static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_enc, bool do_dec, hipStream_t st,
@@ -930,7 +918,6 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
   const sv_lgvae_desc& d = p->d;
   const int B = d.B, H = d.H, W = d.W, dt = d.dtype;
   const int Lg = d.global_latent, Ll = d.local_latent, Lc = Lg + Ll;
-  const char* en[2] = {"x", "xh"};
   const bool no_twin = no_twin_pointwise();
   bool pre_slabs = false;
   int pre_S[2] = {0, 0};
@@ -938,23 +925,13 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
   const int nd = p->ndec();
   if (do_enc && d.global_only) {
     // GMVae: the caller's encoder_x is the only encoder -- this phase zeroes dz (split-K target of d1's input gradient) and fills in8_x
-    if (hipMemsetAsync(p->bp("gz_x"), 0, (size_t)p->bbytes("gz_x"), st) != hipSuccess) return (int)hipGetLastError();
+    SV_TRY(p->bufs.zero(GZ, GZ, st));
     p->gz_clean = true;
     p->gz_zero_skipped = false;
-    p->dz_slabs = false;
-    p->dz_valid = false;
-    if (!(s->phases & SV_PHASE_INPUTS_STAGED)) {
-      Scope sc(p, st, "split_pad", 0, (double)B * H * W * (24 + 16.0 * p->esz()));
-      SV_TRY(svk_split_pad(s->images6, p->bp("in8_x"), p->bp("in8_xh"), dt, (int64_t)B * H * W, st));
-    }
-    do_enc = false;
-  }
-  // (not needed once both split-K launches of this plan have gone through latent_gemm.hip's slabs: nothing accumulates into these buffers)
-  if (do_enc && !(latent_gemm_on(p) && p->lat_head_ok && p->lat_d1_ok && !d.external_global_encoder)) {
+  } else if (do_enc && !(latent_gemm_on(p) && p->lat_head_ok && p->lat_d1_ok && !d.external_global_encoder)) {
     // the head pre-activations (split-K partial sums) and dz (split-K dgrad of d1) accumulate with atomics
-    char* z0 = (char*)p->bp("pre_x");
-    char* z1 = (char*)p->bp("gz_xh") + p->bbytes("gz_xh");
-    if (hipMemsetAsync(z0, 0, (size_t)(z1 - z0), st) != hipSuccess) return (int)hipGetLastError();
+    // (not needed once both split-K launches of this plan have gone through latent_gemm.hip's slabs: nothing accumulates into these buffers)
+    SV_TRY(p->bufs.zero(PRE, GZ_XH, st));
     p->gz_clean = true;
     p->gz_zero_skipped = false;
   } else if (do_enc) {
@@ -964,17 +941,15 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
   if (do_enc) { p->dz_slabs = false; p->dz_valid = false; }
   if (do_enc && !(s->phases & SV_PHASE_INPUTS_STAGED)) {      // (staged: sv_scramble_gather_staged filled in8_x / in8_xh for this images6)
     Scope sc(p, st, "split_pad", 0, (double)B * H * W * (24 + 16.0 * p->esz()));
-    SV_TRY(svk_split_pad(s->images6, p->bp("in8_x"), p->bp("in8_xh"), dt, (int64_t)B * H * W, st));
+    SV_TRY(svk_split_pad(s->images6, p->buf(IN8, 0), p->buf(IN8, 1), dt, (int64_t)B * H * W, st));
   }
+  if (d.global_only) do_enc = false;           // (that was all of the encoders' phase: the plan has none)
   if (do_enc) {
-    static const char* in_name[3] = {"in8_", "a1_", "a2_"};
-    static const char* out_name[3] = {"a1_", "a2_", "a3_"};
+    static const BufId in_id[3] = {IN8, A1, A2}, out_id[3] = {A1, A2, A3};
     for (int l = 0; l < 3; ++l) {
       Layer* Ls[2] = {&p->enc[0][l], &p->enc[1][l]};
-      const void* xs[2] = {p->bp(std::string(in_name[l]) + "x"), p->bp(std::string(in_name[l]) + "xh")};
-      void* ys[2] = {p->bp(std::string(out_name[l]) + "x"), p->bp(std::string(out_name[l]) + "xh")};
       const int e0 = d.external_global_encoder ? 1 : 0;     // SPLIT-GMVAE: the caller runs its own encoder_x
-      SV_TRY(run_fwd_layers(p, 2 - e0, Ls + e0, xs + e0, s->params, ys + e0, st));
+      SV_TRY(run_fwd_layers(p, 2 - e0, Ls + e0, p->pair(in_id[l]) + e0, s->params, p->pair(out_id[l]) + e0, st));
     }
   }
   if (do_enc) {
@@ -988,9 +963,9 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
       Layer& Lh = p->enc[e][3];
       TapGemmArgs& t = a[e - e0];
       svg_fwd_args(&Lh.d, &t);
-      t.A = p->bp(std::string("a3_") + en[e]);
-      t.Wt = (char*)p->bp("warena") + Lh.wf_off * p->esz();
-      t.bias = nullptr; t.out = p->bp(std::string("pre_") + en[e]); t.out_f32 = 1;
+      t.A = p->buf(A3, e);
+      t.Wt = (char*)p->buf(WARENA) + Lh.wf_off * p->esz();
+      t.bias = nullptr; t.out = p->buf(PRE, e); t.out_f32 = 1;
       cfg = svg_pick_cfg(Lh.d.Cout);
       t.splitk = svg_choose_splitk(t.M, t.N, (t.P + 7) / 8, &cfg);
       cfgs[e - e0] = cfg;
@@ -1008,14 +983,14 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
         NtGemmProb& g = q[nq];
         memset(&g, 0, sizeof(g));
         g.f32 = p->d.dtype == SV_F32;
-        g.A = p->bp(std::string("a3_") + en[e]); g.lda = Lh.d.Cin;
-        g.W = (char*)p->bp("warena") + Lh.wf_off * p->esz(); g.ldw = Lh.d.Cin;
-        g.out = p->bp(std::string("lat_ws_") + en[e]); g.ldo = Lh.d.Cout;
+        g.A = p->buf(A3, e); g.lda = Lh.d.Cin;
+        g.W = (char*)p->buf(WARENA) + Lh.wf_off * p->esz(); g.ldw = Lh.d.Cin;
+        g.out = p->buf(LAT_WS, e); g.ldo = Lh.d.Cout;
         g.M = B; g.N = Lh.d.Cout; g.K = Lh.d.Cin; g.out_f32 = 1;
         g.splitk = svk_nt_gemm_pick_splitk(B, g.N, g.K, 2);     // (as the slab buffers were sized)
         g.slab_stride = (int64_t)B * g.ldo;
-        outs[nq] = (float*)p->bp(std::string("pre_") + en[e]);
-        if ((int64_t)g.splitk * g.slab_stride * 4 > p->bbytes(std::string("lat_ws_") + en[e])) return SV_E_WORKSPACE;   // (cannot happen: sized from the same calls)
+        outs[nq] = (float*)p->buf(PRE, e);
+        if ((int64_t)g.splitk * g.slab_stride * 4 > p->bbytes(LAT_WS, e)) return SV_E_WORKSPACE;   // (cannot happen: sized from the same calls)
       }
       const int rc = svk_nt_gemm_multi(q, nq, 64, st);
       if (rc == SV_OK) {
@@ -1033,71 +1008,47 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
     else
       for (int e = 0; e < 2; ++e) SV_TRY(svk_tap_gemm(a[e], dt, cfgs[e], st));   // latent sizes with different tiles
   }
-  if (do_enc && !d.external_global_encoder && !no_twin) {
-    // both networks' Sampling + KL in one launch
-    Scope sc(p, st, "reparam_kl_fwd", 0, (double)B * (Lg + Ll) * 16);
-    const float *pre[2], *bm[2], *bs[2], *eps[2];
-    float *eo[2], *zm[2], *zs[2], *zz[2], *kl[2];
-    const int zc[2] = {0, Lg}, LL[2] = {Lg, Ll};
-    for (int e = 0; e < 2; ++e) {
-      const std::string sfx = en[e];
+  if (do_enc) {
+    // Sampling + KL: both networks in one launch; one network per launch for SPLIT-GMVAE (the caller's encoder is the x network) and under SV_NO_TWIN_POINTWISE
+    const int e0 = d.external_global_encoder ? 1 : 0, per = no_twin ? 1 : 2 - e0;
+    ReparamFwdArgs a[2];
+    for (int e = e0; e < 2; ++e) {
       const Layer& Lh = p->enc[e][3];
-      pre[e] = (const float*)p->bp((pre_slabs ? "lat_ws_" : "pre_") + sfx);
-      bm[e] = s->params + p->params[Lh.kparam + 1].off; bs[e] = s->params + p->params[Lh.kparam + 3].off;
-      eps[e] = e == 0 ? s->eps_x : s->eps_x_hat;
-      eo[e] = (float*)p->bp("eps_" + sfx); zm[e] = (float*)p->bp("z_mean_" + sfx); zs[e] = (float*)p->bp("z_sig_" + sfx);
-      zz[e] = (float*)p->bp("z_" + sfx); kl[e] = (float*)p->bp("kl_" + sfx);
+      // mean bias and sd bias are separate Keras tensors
+      a[e] = {(const float*)p->buf(pre_slabs ? LAT_WS : PRE, e), s->params + p->params[Lh.kparam + 1].off, s->params + p->params[Lh.kparam + 3].off,
+              e == 0 ? s->eps_x : s->eps_x_hat, (float*)p->buf(EPS, e), (float*)p->buf(Z_MEAN, e), (float*)p->buf(Z_SIG, e), (float*)p->buf(Z, e),
+              p->buf(ZCAT), (float*)p->buf(KL, e), Lc, e == 0 ? 0 : Lg, e == 0 ? Lg : Ll, e, pre_slabs ? pre_S[e] : 0, pre_slabs ? pre_stride[e] : 0};
     }
-    SV_TRY(svk_reparam_kl_fwd_twin(pre, bm, bs, eps, eo, zm, zs, zz, p->bp("zcat"), dt, Lc, zc, kl, B, LL, s->seed, s->step,
-                                   s->sample_offset, st, p->dyn, pre_slabs ? pre_S : nullptr, pre_stride));
-  } else
-  for (int e = d.external_global_encoder ? 1 : 0; e < 2 && do_enc; ++e) {
-    const std::string sfx = en[e];
-    const int L = e == 0 ? Lg : Ll;
-    {
-      Scope sc(p, st, "reparam_kl_fwd", 0, (double)B * L * 16);
-      const Layer& Lh = p->enc[e][3];
-      // mean bias and sd bias are separate Keras tensors: two-pointer form of sv_reparam_kl_fwd
-      const float* eps = e == 0 ? s->eps_x : s->eps_x_hat;
-      SV_TRY(svk_reparam_kl_fwd2((const float*)p->bp("pre_" + sfx), s->params + p->params[Lh.kparam + 1].off,
-                                 s->params + p->params[Lh.kparam + 3].off, eps, (float*)p->bp("eps_" + sfx),
-                                 (float*)p->bp("z_mean_" + sfx), (float*)p->bp("z_sig_" + sfx),
-                                 (float*)p->bp("z_" + sfx), p->bp("zcat"), dt, Lc, e == 0 ? 0 : Lg,
-                                 (float*)p->bp("kl_" + sfx), B, L, s->seed, s->step, e, s->sample_offset, st, p->dyn));
+    for (int e = e0; e < 2; e += per) {
+      Scope sc(p, st, "reparam_kl_fwd", 0, (double)B * (per == 2 ? Lg + Ll : a[e].L) * 16);
+      SV_TRY(svk_reparam_kl_fwd(a + e, per, dt, B, s->seed, s->step, s->sample_offset, st, p->dyn));
     }
   }
   if (do_dec) {
     SV_TRY(p->early_wait(st));               // the decoders' weight images (and the zeroed gradient buffer) of this call's early side work
-    const void* zin[2] = {p->bp("zcat"), (const char*)p->bp("zcat") + (size_t)Lg * p->esz()};
+    const void* zin[2] = {p->buf(ZCAT), (const char*)p->buf(ZCAT) + (size_t)Lg * p->esz()};
     {   // d1 differs between the twins (zcat vs local-only input): two shapes, one launch
       Layer* Ls[2] = {&p->dec[0][0], &p->dec[1][0]};
-      void* ys[2] = {p->bp("h1_x"), p->bp("h1_xh")};
-      SV_TRY(run_fwd_layers(p, nd, Ls, zin, s->params, ys, st));
+      SV_TRY(run_fwd_layers(p, nd, Ls, zin, s->params, p->pair(H1), st));
     }
     {
       Layer* Ls[2] = {&p->dec[0][1], &p->dec[1][1]};
-      const void* xs[2] = {p->bp("h1_x"), p->bp("h1_xh")};
-      void* ys[2] = {p->bp("h2_x"), p->bp("h2_xh")};
-      SV_TRY(run_fwd_layers(p, nd, Ls, xs, s->params, ys, st));
+      SV_TRY(run_fwd_layers(p, nd, Ls, p->pair(H1), s->params, p->pair(H2), st));
     }
     // d3..d5 consume the 2x bilinear upsample of the previous activation (vae/model.py:163-167).
     // Fused (bf16): the conv/wgrad tile staging interpolates from the low-res tensor, u2/u3/u4 are
     // never written.  Materialised (fp32 parity path, whose wgrad runs on the im2col kernel).
-    static const char* lo_name[3] = {"h2_", "h3_", "h4_"};
-    static const char* hi_name[3] = {"u2_", "u3_", "u4_"};
-    static const char* out_name[3] = {"h3_", "h4_", "out6_"};
+    static const BufId lo_id[3] = {H2, H3, H4}, hi_id[3] = {U2, U3, U4}, out_id[3] = {H3, H4, OUT6};
     for (int l = 0; l < 3; ++l) {
       Layer* Ls[2] = {&p->dec[0][2 + l], &p->dec[1][2 + l]};
       const void* xs[2] = {nullptr, nullptr};
-      void* ys[2] = {nullptr, nullptr};
+      const BufPair ys = p->pair(out_id[l]);
       for (int k = 0; k < nd; ++k) {
-        const std::string sfx = en[k];
-        xs[k] = p->bp(lo_name[l] + sfx);
-        ys[k] = p->bp(out_name[l] + sfx);
+        xs[k] = p->buf(lo_id[l], k);
         if (!Ls[k]->d.ups_in) {
           Scope sc(p, st, "upsample_fwd", 0, 0);
-          SV_TRY(sv_upsample2x_fwd(xs[k], p->bp(hi_name[l] + sfx), dt, B, Ls[k]->d.H / 2, Ls[k]->d.W / 2, Ls[k]->d.Cin, st));
-          xs[k] = p->bp(hi_name[l] + sfx);
+          SV_TRY(sv_upsample2x_fwd(xs[k], p->buf(hi_id[l], k), dt, B, Ls[k]->d.H / 2, Ls[k]->d.W / 2, Ls[k]->d.Cin, st));
+          xs[k] = p->buf(hi_id[l], k);
         }
       }
       if (l == 2 && want_nll && svg_poly(&Ls[0]->d) && d.H * d.W >= 1024) {
@@ -1105,8 +1056,7 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
         // g5), so dlogistic_kernel and its re-read of out6 drop out of the step (phase_loss then only sums the partials)
         FusedNll f;
         f.images6 = s->images6; f.gscale = 1.0f / (float)d.B; f.noout = (s->phases & SV_PHASE_NO_RECON) ? 1 : 0;
-        f.grad[0] = p->bp("g5_x"); f.grad[1] = p->bp("g5_xh");
-        f.part[0] = (float*)p->bp("nllpart_x"); f.part[1] = (float*)p->bp("nllpart_xh");
+        for (int k = 0; k < 2; ++k) { f.grad[k] = p->buf(G5, k); f.part[k] = (float*)p->buf(NLLPART, k); }
         const int rc = run_fwd_layers(p, nd, Ls, xs, s->params, ys, st, &f);
         if (rc == SV_OK) { p->nll_fused = true; continue; }
         if (rc != SV_E_UNSUPPORTED) return rc;
@@ -1119,63 +1069,49 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
 
 static int phase_loss(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool with_grad, hipStream_t st) {
   const sv_lgvae_desc& d = p->d;
-  const char* en[2] = {"x", "xh"};
-  auto zs0 = [&](const char* kind, int64_t esz) {
-    return (int64_t)((char*)p->bp(std::string(kind) + "xh") - (char*)p->bp(std::string(kind) + "x")) / esz;
-  };
   const bool from_parts = p->nll_fused && with_grad;   // the head's epilogue left per-tile NLL sums and g5 (phase_forward): finalize_losses
                                                        // forms the per-image sums itself (fixed order), no separate kernel
-  if (from_parts) {
-  } else {
+  if (!from_parts) {
     // algorithmic bytes: read x, m, log_scale (12 B/element) + write dm, dls (2 * esz B/element); both networks
     Scope sc(p, st, "dlogistic_nll", 0, p->ndec() * d.B * d.H * d.W * 3.0 * (12.0 + (with_grad ? 2.0 * p->esz() : 0.0)));
-    auto zs = [&](const char* kind, int64_t esz) {
-      if (d.global_only) return (int64_t)0;          // (one network: no second record)
-      return (int64_t)((char*)p->bp(std::string(kind) + "xh") - (char*)p->bp(std::string(kind) + "x")) / esz;
+    auto zs = [&](int id, int64_t esz) {               // elements from the x network's record to the x-hat network's
+      if (d.global_only) return (int64_t)0;            // (one network: no second record)
+      return (int64_t)((char*)p->buf(id, 1) - (char*)p->buf(id, 0)) / esz;
     };
-    SV_TRY(svk_dlogistic_nll_multi(s->images6, 0, (const float*)p->bp("out6_x"), zs("out6_", 4), (float*)p->bp("nll_x"),
-                                   zs("nll_", 4), with_grad ? p->bp("g5_x") : nullptr, zs("g5_", (int64_t)p->esz()), d.dtype,
-                                   1.0f / (float)d.B, d.B, d.H, d.W, (float*)p->bp("nllpart_x"), zs("nllpart_", 4), p->ndec(), st));
+    SV_TRY(svk_dlogistic_nll_multi(s->images6, 0, (const float*)p->buf(OUT6), zs(OUT6, 4), (float*)p->buf(NLL), zs(NLL, 4),
+                                   with_grad ? p->buf(G5) : nullptr, zs(G5, (int64_t)p->esz()), d.dtype, 1.0f / (float)d.B, d.B, d.H, d.W,
+                                   (float*)p->buf(NLLPART), zs(NLLPART, 4), p->ndec(), st));
   }
   const int HWp = d.H * d.W;
-  // (global_only: bp() of the absent x-hat / KL buffers is null -- finalize_losses reads those terms as zero)
-  SV_TRY(svk_finalize_losses((const float*)p->bp("nll_x"), (const float*)p->bp("nll_xh"), (const float*)p->bp("kl_x"),
-                             (const float*)p->bp("kl_xh"), d.B, d.beta, (float*)p->bp("losses"),
-                             (float*)p->bp("metric_acc"), s->accumulate_metrics, st,
-                             from_parts ? (const float*)p->bp("nllpart_x") : nullptr,
-                             from_parts ? (const float*)p->bp("nllpart_xh") : nullptr, HWp > 1024 ? HWp / 1024 : 1));
+  // NULL ON PURPOSE (global_only, see LGVAE_BUFFERS): the plan has no x-hat network and no KL buffers -- finalize_losses reads those terms as zero
+  SV_TRY(svk_finalize_losses((const float*)p->buf(NLL, 0), (const float*)p->buf(NLL, 1), (const float*)p->buf(KL, 0), (const float*)p->buf(KL, 1), d.B, d.beta,
+                             (float*)p->buf(LOSSES), (float*)p->buf(METRIC_ACC), s->accumulate_metrics, st,
+                             from_parts ? (const float*)p->buf(NLLPART, 0) : nullptr, from_parts ? (const float*)p->buf(NLLPART, 1) : nullptr,
+                             HWp > 1024 ? HWp / 1024 : 1));
   return SV_OK;
 }
 
 static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t st) {
   const int nd = p->ndec();
-  if (!p->gz_clean) {   // a second backward over the same forward: re-zero the split-K dz accumulators
-    char* z0 = (char*)p->bp("gz_x");
-    char* z1 = p->d.global_only ? z0 + p->bbytes("gz_x") : (char*)p->bp("gz_xh") + p->bbytes("gz_xh");
-    if (hipMemsetAsync(z0, 0, (size_t)(z1 - z0), st) != hipSuccess) return (int)hipGetLastError();
-  }
+  if (!p->gz_clean) SV_TRY(p->bufs.zero(GZ, GZ + nd - 1, st));   // a second backward over the same forward: re-zero the split-K dz accumulators
   p->gz_clean = false;
   const sv_lgvae_desc& d = p->d;
   const int B = d.B, H = d.H, W = d.W, dt = d.dtype;
   const int Lg = d.global_latent;
-  const char* en[2] = {"x", "xh"};
-  auto both = [&](const char* n, const void** out) { out[0] = p->bp(std::string(n) + "x"); out[1] = p->bp(std::string(n) + "xh"); };
   const void* none[2] = {nullptr, nullptr};
-  static const char* gy_name[3] = {"g5_", "g4_", "g3_"};       // gradient at the layer output
-  static const char* gu_name[3] = {"gu4_", "gu3_", "gu2_"};    // gradient at the (virtual) upsampled input
-  static const char* lo_name[3] = {"h4_", "h3_", "h2_"};       // low-res activation feeding the upsample
-  static const char* hi_name[3] = {"u4_", "u3_", "u2_"};
-  static const char* gl_name[3] = {"g4_", "g3_", "g2_"};       // gradient at the low-res activation
+  static const BufId gy_id[3] = {G5, G4, G3};       // gradient at the layer output
+  static const BufId gu_id[3] = {GU4, GU3, GU2};    // gradient at the (virtual) upsampled input
+  static const BufId lo_id[3] = {H4, H3, H2};       // low-res activation feeding the upsample
+  static const BufId hi_id[3] = {U4, U3, U2};
+  static const BufId gl_id[3] = {G4, G3, G2};       // gradient at the low-res activation
+  static const char* const ups_scope[3] = {"upsample_bwd.4", "upsample_bwd.3", "upsample_bwd.2"};
   for (int l = 0; l < 3; ++l) {                                // d5, d4, d3
     const int li = 4 - l;
     Layer* Ls[2] = {&p->dec[0][li], &p->dec[1][li]};
-    const void *gy[2], *gu[2];
-    both(gy_name[l], gy); both(gu_name[l], gu);
+    const BufPair gy = p->pair(gy_id[l]), gu = p->pair(gu_id[l]), lo = p->pair(lo_id[l]), gl = p->pair(gl_id[l]);
     const void* xin[2] = {nullptr, nullptr};
-    for (int k = 0; k < nd; ++k) xin[k] = p->bp(std::string(Ls[k]->d.ups_in ? lo_name[l] : hi_name[l]) + en[k]);
+    for (int k = 0; k < nd; ++k) xin[k] = p->buf(Ls[k]->d.ups_in ? lo_id[l] : hi_id[l], k);
     SV_TRY(run_wgrad_layers(p, nd, Ls, xin, gy, s->grads, st));
-    const void *lo[2], *gl[2];
-    both(lo_name[l], lo); both(gl_name[l], gl);
     // the input gradient lands at the LOW-RES activation in one launch where the fused kernel exists (ResizeBilinearGrad +
     // ReluGrad in the epilogue of Conv2DBackpropInput: the hi-res gradient gu never reaches HBM) ...
     // (it works on whole images -- its low-res rows straddle row bands -- so below ~one image per workgroup slot the banded
@@ -1188,49 +1124,44 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
     if (Ls[0]->wdp_off >= 0 && (nd == 1 || Ls[1]->wdp_off >= 0)) {
       // fp32: the polyphase form (polyd_dgrad.hip): conv-transpose + resize adjoint + ReLU gate as one stride-2 conv over dY, edge terms through a workspace
       const void* wp[2];
-      void* ews[2] = {p->bp("polyd_x"), p->bp("polyd_xh")};
       double fl = 0, by = 0;
       for (int k = 0; k < nd; ++k) {
-        wp[k] = (const char*)p->bp("warena") + Ls[k]->wdp_off * p->esz();
+        wp[k] = (const char*)p->buf(WARENA) + Ls[k]->wdp_off * p->esz();
         fl += conv_flops(Ls[k]->d); by += conv_bytes(Ls[k]->d, 1, p->esz());
       }
-      Scope sc(p, st, "dgrad." + Ls[0]->name.substr(Ls[0]->name.find('.') + 1), fl, by);
+      Scope sc(p, st, Ls[0]->sc_dgrad, fl, by);
       { double is = 0; for (int k = 0; k < nd; ++k) is += poly_issued(Ls[k]->d, 81, true); sc.issued(is); }
-      frc = svk_polyd_dgrad_multi(&Ls[0]->d, nd, gy, wp, lo, (void* const*)gl, ews, st);
+      frc = svk_polyd_dgrad_multi(&Ls[0]->d, nd, gy, wp, lo, gl, p->pair(POLYD), st);
     }
     if (frc == SV_E_UNSUPPORTED && Ls[0]->d.ups_in && (nd == 1 || Ls[1]->d.ups_in) && !no_adj && nd * B >= adj_min)
-      frc = run_dgrad_layers(p, nd, Ls, gy, lo, (void* const*)gl, false, st, true);
+      frc = run_dgrad_layers(p, nd, Ls, gy, lo, gl, false, st, true);
     if (frc != SV_E_UNSUPPORTED) { SV_TRY(frc); continue; }
     // ... else the hi-res gradient goes through HBM and a stand-alone adjoint pass
-    SV_TRY(run_dgrad_layers(p, nd, Ls, gy, none, (void* const*)gu, false, st));
+    SV_TRY(run_dgrad_layers(p, nd, Ls, gy, none, gu, false, st));
     {
       const int h = (H / 2) >> l, w = (W / 2) >> l, c = 32 << l;
       const int64_t lo_bytes = (int64_t)B * h * w * c * p->esz();
       const bool contig = nd == 2 && (const char*)gu[1] == (const char*)gu[0] + 4 * lo_bytes &&
                           (const char*)lo[1] == (const char*)lo[0] + lo_bytes && (const char*)gl[1] == (const char*)gl[0] + lo_bytes;
-      Scope sc(p, st, std::string("upsample_bwd.") + lo_name[l][1], 0, nd * 6.0 * lo_bytes);   // read g_hi (4x) + mask, write g_lo; both networks
-      if (contig) SV_TRY(sv_upsample2x_bwd(gu[0], lo[0], (void*)gl[0], dt, 2 * B, h, w, c, st));
+      Scope sc(p, st, ups_scope[l], 0, nd * 6.0 * lo_bytes);   // read g_hi (4x) + mask, write g_lo; both networks
+      if (contig) SV_TRY(sv_upsample2x_bwd(gu[0], lo[0], gl[0], dt, 2 * B, h, w, c, st));
       else
-        for (int k = 0; k < nd; ++k) SV_TRY(sv_upsample2x_bwd(gu[k], lo[k], (void*)gl[k], dt, B, h, w, c, st));
+        for (int k = 0; k < nd; ++k) SV_TRY(sv_upsample2x_bwd(gu[k], lo[k], gl[k], dt, B, h, w, c, st));
     }
   }
   {
     // d2 (input h1 = relu(d1): mask fused in the dgrad epilogue)
     Layer* Ls[2] = {&p->dec[0][1], &p->dec[1][1]};
-    const void *g2[2], *h1[2], *g1[2];
-    both("g2_", g2); both("h1_", h1); both("g1_", g1);
-    SV_TRY(run_wgrad_layers(p, nd, Ls, h1, g2, s->grads, st));
-    SV_TRY(run_dgrad_layers(p, nd, Ls, g2, h1, (void* const*)g1, false, st));
+    SV_TRY(run_wgrad_layers(p, nd, Ls, p->pair(H1), p->pair(G2), s->grads, st));
+    SV_TRY(run_dgrad_layers(p, nd, Ls, p->pair(G2), p->pair(H1), p->pair(G1), false, st));
   }
   {
     // d1 (dense): dz accumulated in fp32 over split K; the twins (different input widths) share the launches
     Layer Ld[2] = {p->dec[0][0], p->dec[1][0]};
     Layer* Ls[2] = {&p->dec[0][0], &p->dec[1][0]};
     Layer* Lds[2] = {&Ld[0], &Ld[1]};
-    const void* zin[2] = {p->bp("zcat"), (const char*)p->bp("zcat") + (size_t)Lg * p->esz()};
-    const void *g1[2], *none2[2] = {nullptr, nullptr};
-    void* gz[2] = {p->bp("gz_x"), p->bp("gz_xh")};
-    both("g1_", g1);
+    const void* zin[2] = {p->buf(ZCAT), (const char*)p->buf(ZCAT) + (size_t)Lg * p->esz()};
+    const BufPair g1 = p->pair(G1), gz = p->pair(GZ);
     SV_TRY(run_wgrad_layers(p, nd, Ls, zin, g1, s->grads, st));
     for (int k = 0; k < nd; ++k) Ld[k].d.ldx = Ld[k].d.Cin;   // dz has its own row pitch (Lz), not the zcat pitch
     bool done = false;
@@ -1246,12 +1177,12 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
         memset(&g, 0, sizeof(g));
         g.f32 = p->d.dtype == SV_F32;
         g.A = g1[k]; g.lda = dd.ldy;
-        g.W = (char*)p->bp("warena") + Ld[k].wd_off[0] * p->esz(); g.ldw = svg_gdy(&dd);
-        g.out = p->bp(k == 0 ? "lat_ws_x" : "lat_ws_xh"); g.ldo = dd.Cin;
+        g.W = (char*)p->buf(WARENA) + Ld[k].wd_off[0] * p->esz(); g.ldw = svg_gdy(&dd);
+        g.out = p->buf(LAT_WS, k); g.ldo = dd.Cin;
         g.M = B; g.N = dd.Cin; g.K = dd.Cout; g.out_f32 = 1;
         g.splitk = svk_nt_gemm_pick_splitk(B, g.N, g.K, 2);
         g.slab_stride = (int64_t)B * g.ldo;
-        if ((int64_t)g.splitk * g.slab_stride * 4 > p->bbytes(k == 0 ? "lat_ws_x" : "lat_ws_xh")) return SV_E_WORKSPACE;           // (cannot happen: sized from the same calls)
+        if ((int64_t)g.splitk * g.slab_stride * 4 > p->bbytes(LAT_WS, k)) return SV_E_WORKSPACE;           // (cannot happen: sized from the same calls)
         outs[k] = (float*)gz[k];
         fl += conv_flops(dd); by += conv_bytes(dd, 1, p->esz());
       }
@@ -1267,7 +1198,7 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
         } else SV_TRY(svk_nt_slab_reduce(q, outs, nd, st));
       } else if (rc != SV_E_UNSUPPORTED) return rc;
     }
-    if (!done) SV_TRY(run_dgrad_layers(p, nd, Lds, g1, none2, gz, true, st));
+    if (!done) SV_TRY(run_dgrad_layers(p, nd, Lds, g1, none, gz, true, st));
   }
   return SV_OK;
 }
@@ -1276,45 +1207,26 @@ static int phase_bwd_encoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, boo
   const sv_lgvae_desc& d = p->d;
   const int B = d.B, dt = d.dtype;
   const int Lg = d.global_latent, Ll = d.local_latent, Lc = Lg + Ll;
-  const char* en[2] = {"x", "xh"};
   const float kl_scale = d.beta / (float)B;
   const int e0 = d.external_global_encoder ? 1 : 0;
   if (d.global_only) return SV_OK;            // GMVae: the only encoder is the caller's (it reads dL/dz_x from gz_x)
   if (do_heads && !p->dz_valid && p->gz_zero_skipped) {       // KL terms only (no decoder backward since the forward): dz = 0
-    char* z0 = (char*)p->bp("gz_x");
-    char* z1 = (char*)p->bp("gz_xh") + p->bbytes("gz_xh");
-    if (hipMemsetAsync(z0, 0, (size_t)(z1 - z0), st) != hipSuccess) return (int)hipGetLastError();
+    SV_TRY(p->bufs.zero(GZ, GZ_XH, st));
     p->gz_zero_skipped = false;
   }
   if (do_heads) {
+    // the adjoint of Sampling + KL, launched as the forward is (phase_forward).  decoder_x's dz is [B, Lc]: columns [0, Lg) belong to z_x, [Lg, Lc) to z_x-hat,
+    // which also gets decoder_x-hat's dz.  dz_slabs (twin launch only): the K-slice slabs of d1's input gradient instead, summed in the kernel
     Scope sc(p, st, "reparam_kl_bwd", 0, 0);
-    const bool no_twin = no_twin_pointwise();
-    if (!e0 && !no_twin) {
-      const float* dz[2] = {(const float*)p->bp("gz_x"), (const float*)p->bp("gz_x") + Lg};
-      const float* dz2[2] = {nullptr, (const float*)p->bp("gz_xh")};
-      const int ld[2] = {Lc, Lc}, ld2[2] = {0, Ll}, LL[2] = {Lg, Ll};
-      const float* zm[2] = {(const float*)p->bp("z_mean_x"), (const float*)p->bp("z_mean_xh")};
-      const float* zs[2] = {(const float*)p->bp("z_sig_x"), (const float*)p->bp("z_sig_xh")};
-      const float* ep[2] = {(const float*)p->bp("eps_x"), (const float*)p->bp("eps_xh")};
-      void* gp[2] = {p->bp("ghead_x"), p->bp("ghead_xh")};
-      if (p->dz_slabs) {
-        const float *sx = (const float*)p->bp("lat_ws_x"), *sxh = (const float*)p->bp("lat_ws_xh");
-        const float* dzs[2] = {sx, sx + Lg};
-        const float* dz2s[2] = {nullptr, sxh};
-        const int S[2] = {p->dz_S[0], p->dz_S[0]}, S2[2] = {0, p->dz_S[1]};
-        const int64_t sd[2] = {p->dz_stride[0], p->dz_stride[0]}, sd2[2] = {0, p->dz_stride[1]};
-        SV_TRY(svk_reparam_kl_bwd_twin(dzs, ld, dz2s, ld2, zm, zs, ep, kl_scale, gp, dt, B, LL, st, S, sd, S2, sd2));
-      } else
-      SV_TRY(svk_reparam_kl_bwd_twin(dz, ld, dz2, ld2, zm, zs, ep, kl_scale, gp, dt, B, LL, st));
-    } else {
-    if (!e0)
-      SV_TRY(sv_reparam_kl_bwd((const float*)p->bp("gz_x"), Lc, nullptr, 0, (const float*)p->bp("z_mean_x"),
-                               (const float*)p->bp("z_sig_x"), (const float*)p->bp("eps_x"), kl_scale, p->bp("ghead_x"),
-                               dt, B, Lg, st));
-    SV_TRY(sv_reparam_kl_bwd((const float*)p->bp("gz_x") + Lg, Lc, (const float*)p->bp("gz_xh"), Ll,
-                             (const float*)p->bp("z_mean_xh"), (const float*)p->bp("z_sig_xh"),
-                             (const float*)p->bp("eps_xh"), kl_scale, p->bp("ghead_xh"), dt, B, Ll, st));
-    }
+    const int per = no_twin_pointwise() ? 1 : 2 - e0, src = p->dz_slabs ? LAT_WS : GZ;
+    const int S0 = p->dz_slabs ? p->dz_S[0] : 0, S1 = p->dz_slabs ? p->dz_S[1] : 0;
+    const int64_t sd0 = p->dz_slabs ? p->dz_stride[0] : 0, sd1 = p->dz_slabs ? p->dz_stride[1] : 0;
+    const float* dzx = (const float*)p->buf(src, 0);
+    const ReparamBwdArgs a[2] = {
+        {dzx, nullptr, (const float*)p->buf(Z_MEAN, 0), (const float*)p->buf(Z_SIG, 0), (const float*)p->buf(EPS, 0), p->buf(GHEAD, 0), Lc, 0, Lg, S0, 0, sd0, 0},
+        {dzx + Lg, (const float*)p->buf(src, 1), (const float*)p->buf(Z_MEAN, 1), (const float*)p->buf(Z_SIG, 1), (const float*)p->buf(EPS, 1), p->buf(GHEAD, 1),
+         Lc, Ll, Ll, S0, S1, sd0, sd1}};
+    for (int e = e0; e < 2; e += per) SV_TRY(svk_reparam_kl_bwd(a + e, per, kl_scale, dt, B, st));
   }
   if (do_heads) {
     // heads: two Keras kernels/biases per network -> wgrad problems on the column halves of ghead, all in one launch
@@ -1327,8 +1239,8 @@ static int phase_bwd_encoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, boo
       const int Lh = e == 0 ? Lg : Ll;
       for (int h = 0; h < 2; ++h, ++n) {
         svg_wgrad_args(&L[3].d, &a[n]);
-        a[n].A = p->bp(std::string("a3_") + en[e]);
-        a[n].dY = (const char*)p->bp(std::string("ghead_") + en[e]) + (size_t)h * Lh * p->esz();
+        a[n].A = p->buf(A3, e);
+        a[n].dY = (const char*)p->buf(GHEAD, e) + (size_t)h * Lh * p->esz();
         a[n].ycols = Lh; a[n].N = Lh;
         a[n].dW = s->grads + p->params[L[3].kparam + 2 * h].off;
         a[n].dbias = s->grads + p->params[L[3].kparam + 2 * h + 1].off;
@@ -1352,8 +1264,7 @@ static int phase_bwd_encoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, boo
       if (!done) SV_TRY(svk_wgrad_dispatch_multi(a, n, dt, e0 ? cl : (cg > cl ? cg : cl), ws));
     }
     Layer* Ls[2] = {&p->enc[0][3], &p->enc[1][3]};
-    const void *gh[2] = {p->bp("ghead_x"), p->bp("ghead_xh")}, *a3[2] = {p->bp("a3_x"), p->bp("a3_xh")};
-    void* ga3[2] = {p->bp("ga3_x"), p->bp("ga3_xh")};
+    const BufPair gh = p->pair(GHEAD), a3 = p->pair(A3), ga3 = p->pair(GA3);
     bool done = false;
     if (latent_gemm_on(p)) {
       NtGemmProb q[2];
@@ -1365,7 +1276,7 @@ static int phase_bwd_encoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, boo
         memset(&g, 0, sizeof(g));
         g.f32 = p->d.dtype == SV_F32;
         g.A = gh[e]; g.lda = Lh.d.Cout;
-        g.W = (char*)p->bp("warena") + Lh.wd_off[0] * p->esz(); g.ldw = Lh.d.Cout;
+        g.W = (char*)p->buf(WARENA) + Lh.wd_off[0] * p->esz(); g.ldw = Lh.d.Cout;
         g.out = ga3[e]; g.ldo = Lh.d.Cin; g.mask = a3[e];
         g.M = B; g.N = Lh.d.Cin; g.K = Lh.d.Cout; g.splitk = 1;
         fl += conv_flops(Lh.d); by += conv_bytes(Lh.d, 1, p->esz());
@@ -1379,17 +1290,13 @@ static int phase_bwd_encoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, boo
     if (buckets) SV_TRY(p->record_bucket(1, st));       // the heads' weight gradients are enqueued (main or side stream)
   }
   if (do_convs) {
-    auto both = [&](const char* n, const void** out) { out[0] = p->bp(std::string(n) + "x"); out[1] = p->bp(std::string(n) + "xh"); };
-    static const char* act_name[3] = {"in8_", "a1_", "a2_"};
-    static const char* g_name[3] = {"ga1_", "ga2_", "ga3_"};
+    static const BufId act_id[3] = {IN8, A1, A2}, g_id[3] = {GA1, GA2, GA3};
     for (int l = 2; l >= 0; --l) {
       Layer* Ls[2] = {&p->enc[0][l], &p->enc[1][l]};
-      const void *x[2], *gy[2], *gx[2];
-      both(act_name[l], x); both(g_name[l], gy);
+      const BufPair x = p->pair(act_id[l]), gy = p->pair(g_id[l]);
       SV_TRY(run_wgrad_layers(p, 2 - e0, Ls + e0, x + e0, gy + e0, s->grads, st));
       if (l == 0) break;
-      both(g_name[l - 1], gx);
-      SV_TRY(run_dgrad_layers(p, 2 - e0, Ls + e0, gy + e0, x + e0, (void* const*)gx + e0, false, st));
+      SV_TRY(run_dgrad_layers(p, 2 - e0, Ls + e0, gy + e0, x + e0, p->pair(g_id[l - 1]) + e0, false, st));
     }
     if (buckets) SV_TRY(p->record_bucket(2, st));
   }
@@ -1427,7 +1334,7 @@ extern "C" int sv_lgvae_plan_create(const sv_lgvae_desc* d, sv_lgvae_plan** out)
   if (p->d.global_only) p->d.local_latent = p->d.global_latent;   // (ignored in this mode: keep the derived sizes well defined)
   p->params = build_params(d);
   p->nparams = p->params.back().off + (p->params.back().count + 3) / 4 * 4;
-  p->ws = nullptr; p->bound = false; p->prof_on = false;
+  p->bound = false; p->prof_on = false;
   build_layers(p);
   for (int e = 0; e < 2 && !p->d.global_only; ++e)
     for (int l = 0; l < 4; ++l)
@@ -1437,6 +1344,8 @@ extern "C" int sv_lgvae_plan_create(const sv_lgvae_desc* d, sv_lgvae_plan** out)
       if ((rc = svg_check(&p->dec[k][l].d))) { delete p; return rc; }
   build_prep_jobs(p);
   build_buffers(p);
+  // the ranges the step zeroes with one memset each (phase_forward, phase_bwd_decoders, phase_bwd_encoders) hold exactly the buffers they name
+  if (p->d.global_only ? !p->bufs.run(GZ, GZ) : !p->bufs.run(PRE, GZ_XH)) { delete p; return SV_E_STATE; }
   *out = p;
   return SV_OK;
 }
@@ -1462,34 +1371,17 @@ extern "C" void sv_lgvae_plan_destroy(sv_lgvae_plan* p) {
   delete p;
 }
 
-extern "C" int64_t sv_lgvae_workspace_bytes(const sv_lgvae_plan* p) { return p ? p->ws_bytes : -1; }
+extern "C" int64_t sv_lgvae_workspace_bytes(const sv_lgvae_plan* p) { return p ? p->bufs.ws_bytes : -1; }
 
 extern "C" int sv_lgvae_plan_bind(sv_lgvae_plan* p, void* workspace, int64_t bytes, void* stream) {
-  if (!p || !workspace) return SV_E_BADARG;
-  if (bytes < p->ws_bytes) return SV_E_WORKSPACE;
-  if ((uintptr_t)workspace & 255) return SV_E_BADARG;
-  p->ws = (char*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  // The whole workspace starts from ZERO: pad channels / pad rows of the activation, gradient and weight-image buffers that no kernel ever writes are read as
-  // zeros by the MFMA kernels, and a few accumulators (metric_acc, the polyphase head's dbias') count up from zero.  The Python mirror used to hand in a zeroed
-  // tensor; a C caller's hipMalloc'd block is garbage (scripts/ws_poison_probe.py: with 0xFF bytes every loss was NaN), so the bind does it itself.
-  hipError_t e = hipMemsetAsync(workspace, 0, (size_t)p->ws_bytes, st);
-  if (e != hipSuccess) return (int)e;
-  e = hipMemcpyAsync(p->bp("jobs"), p->jobs.data(), p->jobs.size() * sizeof(PrepJob), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return (int)e;
-  e = hipStreamSynchronize(st);   // the job table lives in plan-owned host memory: finish the copy now
-  if (e != hipSuccess) return (int)e;
+  if (!p) return SV_E_BADARG;
+  SV_TRY(p->bufs.bind(workspace, bytes, (hipStream_t)stream, JOBS, p->jobs.data(), p->jobs.size() * sizeof(PrepJob)));
   p->bound = true;
   return SV_OK;
 }
 
 extern "C" int sv_lgvae_buffer(const sv_lgvae_plan* p, const char* name, int64_t* offset, int64_t* bytes) {
-  if (!p || !name) return SV_E_BADARG;
-  auto it = p->bufidx.find(name);
-  if (it == p->bufidx.end()) return SV_E_BADARG;
-  if (offset) *offset = p->bufs[it->second].off;
-  if (bytes) *bytes = p->bufs[it->second].bytes;
-  return SV_OK;
+  return p ? p->bufs.lookup(name, offset, bytes) : SV_E_BADARG;
 }
 
 static int run_phases(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t st) {
@@ -1559,7 +1451,7 @@ static std::vector<uint64_t> graph_key(const sv_lgvae_plan* p, const sv_lgvae_st
   return {(uint64_t)(uint32_t)s->phases, (uint64_t)s->params, (uint64_t)s->grads, (uint64_t)s->adam_m, (uint64_t)s->adam_v,
           (uint64_t)s->images6, (uint64_t)s->eps_x, (uint64_t)s->eps_x_hat, (uint64_t)st,
           adam ? f(s->beta1) : 0, adam ? f(s->beta2) : 0, adam ? f(s->adam_eps) : 0, adam ? f(s->grad_scale) : 0,
-          (uint64_t)s->accumulate_metrics, p->host_state_bits(), (uint64_t)p->ws};
+          (uint64_t)s->accumulate_metrics, p->host_state_bits(), (uint64_t)p->buf(JOBS)};   // (JOBS: the workspace itself, its first buffer)
 }
 
 extern "C" int sv_lgvae_step(sv_lgvae_plan* p, const sv_lgvae_step_args* s, void* stream) {
@@ -1582,11 +1474,11 @@ extern "C" int sv_lgvae_step(sv_lgvae_plan* p, const sv_lgvae_step_args* s, void
   sv_lgvae_plan::GraphEntry& e = p->graphs[key];
   if (!e.exec && e.seen++ == 0) return run_phases(p, s, st);
   const float alpha = (ph & SV_PHASE_ADAM) ? (float)svk_adam_alpha(s->lr, s->beta1, s->beta2, s->t) : 0.f;
-  SV_TRY(svk_set_dyn((SvDynArgs*)p->bp("dyn"), s->seed, s->step, s->sample_offset, alpha, st));
+  SV_TRY(svk_set_dyn((SvDynArgs*)p->buf(DYN), s->seed, s->step, s->sample_offset, alpha, st));
   if (!e.exec) {
     hipGraph_t g = nullptr;
     if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) return (int)hipGetLastError();
-    p->dyn = (const SvDynArgs*)p->bp("dyn");
+    p->dyn = (const SvDynArgs*)p->buf(DYN);
     const int rc = run_phases(p, s, st);
     p->dyn = nullptr;
     const hipError_t he = hipStreamEndCapture(st, &g);

@@ -284,14 +284,6 @@ extern "C" int sv_dlogistic_nll(const float* images6, int32_t ch_off, const floa
 }
 
 // ============================================================================ A4 + A7 reparam / KL
-struct ReparamFwdArgs {
-  const float *pre, *bias_mean, *bias_sd, *eps;
-  float *eps_out, *z_mean, *z_sig, *z;
-  void* z_lp;
-  float* kl;
-  int ldz, z_col, L, stream_id;
-  int S; int64_t slab_stride;      // S > 0: `pre` is the first of S K-slice slabs of the heads' GEMM (latent_gemm.hip), summed here in slice order
-};
 template <typename TZ>
 __device__ __forceinline__ void reparam_kl_fwd_body(const ReparamFwdArgs& g, int B, uint64_t seed, uint64_t step, int64_t sample_offset) {
   const float* __restrict__ pre = g.pre; const float* __restrict__ bias_mean = g.bias_mean; const float* __restrict__ bias_sd = g.bias_sd;
@@ -340,36 +332,21 @@ __device__ __forceinline__ void reparam_kl_fwd_body(const ReparamFwdArgs& g, int
   if (lane == 0) kl[b] = -0.5f * acc;
 }
 
-template <typename TZ>
-__global__ __launch_bounds__(256) void reparam_kl_fwd_kernel(
-    const float* __restrict__ pre, const float* __restrict__ bias_mean, const float* __restrict__ bias_sd,
-    const float* __restrict__ eps, float* __restrict__ eps_out, float* __restrict__ z_mean, float* __restrict__ z_sig,
-    float* __restrict__ z, TZ* __restrict__ z_lp, int ldz, int z_col, float* __restrict__ kl, int B,
-    int L, uint64_t seed, uint64_t step, int stream_id, int64_t sample_offset, const SvDynArgs* __restrict__ dyn) {
-  if (dyn) { seed = dyn->seed; step = dyn->step; sample_offset = dyn->sample_offset; }   // captured step (graph replay)
-  const ReparamFwdArgs g = {pre, bias_mean, bias_sd, eps, eps_out, z_mean, z_sig, z, (void*)z_lp, kl, ldz, z_col, L, stream_id, 0, 0};
-  reparam_kl_fwd_body<TZ>(g, B, seed, step, sample_offset);
-}
-
-// the x and x-hat heads in one launch (blockIdx.y picks the network): one dependent launch less on the critical path
+// n <= 2 networks in one launch (blockIdx.y picks the record): the x and x-hat heads of a step share it, one dependent launch less on the critical path
 struct ReparamFwdTwin { ReparamFwdArgs a[2]; };
 template <typename TZ>
-__global__ __launch_bounds__(256) void reparam_kl_fwd_twin_kernel(const ReparamFwdTwin t, int B, uint64_t seed, uint64_t step,
-                                                                  int64_t sample_offset, const SvDynArgs* __restrict__ dyn) {
-  if (dyn) { seed = dyn->seed; step = dyn->step; sample_offset = dyn->sample_offset; }
+__global__ __launch_bounds__(256) void reparam_kl_fwd_twin_kernel(const ReparamFwdTwin t, int B, uint64_t seed, uint64_t step, int64_t sample_offset,
+                                                             const SvDynArgs* __restrict__ dyn) {
+  if (dyn) { seed = dyn->seed; step = dyn->step; sample_offset = dyn->sample_offset; }   // captured step (graph replay)
   reparam_kl_fwd_body<TZ>(t.a[blockIdx.y], B, seed, step, sample_offset);
 }
 
-int svk_reparam_kl_fwd_twin(const float* const* pre, const float* const* bias_mean, const float* const* bias_sd,
-                            const float* const* eps, float* const* eps_out, float* const* z_mean, float* const* z_sig,
-                            float* const* z, void* z_lp, int z_dtype, int ldz, const int* z_col, float* const* kl, int B,
-                            const int* L, uint64_t seed, uint64_t step, int64_t sample_offset, hipStream_t st, const SvDynArgs* dyn,
-                            const int* S, const int64_t* slab_stride) {
+int svk_reparam_kl_fwd(const ReparamFwdArgs* a, int n, int z_dtype, int B, uint64_t seed, uint64_t step, int64_t sample_offset, hipStream_t st,
+                       const SvDynArgs* dyn) {
+  if (n < 1 || n > 2) return SV_E_BADARG;
   ReparamFwdTwin t;
-  for (int e = 0; e < 2; ++e)
-    t.a[e] = {pre[e], bias_mean[e], bias_sd[e], eps[e], eps_out[e], z_mean[e], z_sig[e], z[e], z_lp, kl[e], ldz, z_col[e], L[e], e,
-              S ? S[e] : 0, S ? slab_stride[e] : 0};
-  dim3 grid((B + 3) / 4, 2), block(256);
+  for (int e = 0; e < 2; ++e) t.a[e] = a[e < n ? e : 0];
+  dim3 grid((B + 3) / 4, n), block(256);
   if (z_dtype == SV_BF16) hipLaunchKernelGGL((reparam_kl_fwd_twin_kernel<bf16_t>), grid, block, 0, st, t, B, seed, step, sample_offset, dyn);
   else if (z_dtype == SV_F32) hipLaunchKernelGGL((reparam_kl_fwd_twin_kernel<float>), grid, block, 0, st, t, B, seed, step, sample_offset, dyn);
   else return SV_E_BADARG;
@@ -377,58 +354,17 @@ int svk_reparam_kl_fwd_twin(const float* const* pre, const float* const* bias_me
   return SV_OK;
 }
 
-int svk_reparam_kl_fwd2(const float* pre, const float* bias_mean, const float* bias_sd, const float* eps,
-                        float* eps_out, float* z_mean, float* z_sig, float* z, void* z_lp, int z_dtype, int ldz,
-                        int z_col, float* kl, int B, int L, uint64_t seed, uint64_t step, int stream_id,
-                        int64_t sample_offset, hipStream_t st, const SvDynArgs* dyn) {
-  if (!pre || !bias_mean || !bias_sd || !z_mean || !z_sig || !z || !z_lp || !kl || B <= 0 || L <= 0) return SV_E_BADARG;
-  dim3 grid((B + 3) / 4), block(256);
-  if (z_dtype == SV_BF16)
-    hipLaunchKernelGGL((reparam_kl_fwd_kernel<bf16_t>), grid, block, 0, st, pre, bias_mean, bias_sd, eps, eps_out,
-                       z_mean, z_sig, z, (bf16_t*)z_lp, ldz, z_col, kl, B, L, seed, step, stream_id, sample_offset, dyn);
-  else if (z_dtype == SV_F32)
-    hipLaunchKernelGGL((reparam_kl_fwd_kernel<float>), grid, block, 0, st, pre, bias_mean, bias_sd, eps, eps_out,
-                       z_mean, z_sig, z, (float*)z_lp, ldz, z_col, kl, B, L, seed, step, stream_id, sample_offset, dyn);
-  else
-    return SV_E_BADARG;
-  SV_LAUNCH_CHECK();
-  return SV_OK;
-}
-
+// mean bias and sd bias are the two halves of `bias`
 extern "C" int sv_reparam_kl_fwd(const float* pre, const float* bias, const float* eps, float* eps_out,
                                  float* z_mean, float* z_sig, float* z, void* z_lp, int32_t z_dtype,
                                  int32_t ldz, int32_t z_col, float* kl, int32_t B, int32_t L,
                                  uint64_t seed, uint64_t step, int32_t stream_id,
                                  int64_t sample_offset, void* stream) {
-  if (!bias) return SV_E_BADARG;
-  return svk_reparam_kl_fwd2(pre, bias, bias + L, eps, eps_out, z_mean, z_sig, z, z_lp, z_dtype, ldz, z_col, kl, B,
-                             L, seed, step, stream_id, sample_offset, (hipStream_t)stream);
+  if (!pre || !bias || !z_mean || !z_sig || !z || !z_lp || !kl || B <= 0 || L <= 0) return SV_E_BADARG;
+  const ReparamFwdArgs g = {pre, bias, bias + L, eps, eps_out, z_mean, z_sig, z, z_lp, kl, ldz, z_col, L, stream_id, 0, 0};
+  return svk_reparam_kl_fwd(&g, 1, z_dtype, B, seed, step, sample_offset, (hipStream_t)stream);
 }
 
-template <typename TG>
-__global__ __launch_bounds__(256) void reparam_kl_bwd_kernel(
-    const float* __restrict__ dz, int ld_dz, const float* __restrict__ dz2, int ld_dz2,
-    const float* __restrict__ z_mean, const float* __restrict__ z_sig, const float* __restrict__ eps,
-    float kl_scale, TG* __restrict__ g_pre, int B, int L) {
-  const int64_t total = (int64_t)B * L;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int b = (int)(i / L), j = (int)(i - (int64_t)b * L);
-    float g = dz[(int64_t)b * ld_dz + j];
-    if (dz2) g += dz2[(int64_t)b * ld_dz2 + j];
-    const float mu = z_mean[i], sg = z_sig[i], e = eps[i];
-    const float dmu = g + kl_scale * mu;
-    const float dsg = g * e + kl_scale * (sg - 1.f / sg);
-    const float dpre = dsg * softplus_der_from_out(sg);  // softplus'(pre) = 1 - exp(-softplus(pre)), without its cancellation at small sigma
-    g_pre[(int64_t)b * 2 * L + j] = from_f32<TG>(dmu);
-    g_pre[(int64_t)b * 2 * L + L + j] = from_f32<TG>(dpre);
-  }
-}
-
-struct ReparamBwdArgs {
-  const float *dz, *dz2, *z_mean, *z_sig, *eps; void* g_pre; int ld_dz, ld_dz2, L;
-  int S, S2; int64_t stride, stride2;      // S > 0: dz / dz2 are the first of S / S2 K-slice slabs of d1's input gradient, summed here in slice order
-};
 struct ReparamBwdTwin { ReparamBwdArgs a[2]; };
 template <typename TG>
 __global__ __launch_bounds__(256) void reparam_kl_bwd_twin_kernel(const ReparamBwdTwin t, float kl_scale, int B) {
@@ -458,23 +394,20 @@ __global__ __launch_bounds__(256) void reparam_kl_bwd_twin_kernel(const ReparamB
     const float mu = g.z_mean[i], sg = g.z_sig[i], e = g.eps[i];
     const float dmu = gg + kl_scale * mu;
     const float dsg = gg * e + kl_scale * (sg - 1.f / sg);
-    const float dpre = dsg * softplus_der_from_out(sg);  // as reparam_kl_bwd_kernel
+    const float dpre = dsg * softplus_der_from_out(sg);  // softplus'(pre) = 1 - exp(-softplus(pre)), without its cancellation at small sigma
     g_pre[(int64_t)b * 2 * L + j] = from_f32<TG>(dmu);
     g_pre[(int64_t)b * 2 * L + L + j] = from_f32<TG>(dpre);
   }
 }
-int svk_reparam_kl_bwd_twin(const float* const* dz, const int* ld_dz, const float* const* dz2, const int* ld_dz2,
-                            const float* const* z_mean, const float* const* z_sig, const float* const* eps, float kl_scale,
-                            void* const* g_pre, int g_dtype, int B, const int* L, hipStream_t st,
-                            const int* S, const int64_t* stride, const int* S2, const int64_t* stride2) {
+int svk_reparam_kl_bwd(const ReparamBwdArgs* a, int n, float kl_scale, int g_dtype, int B, hipStream_t st) {
+  if (n < 1 || n > 2) return SV_E_BADARG;
   ReparamBwdTwin t;
   int Lmax = 0;
   for (int e = 0; e < 2; ++e) {
-    t.a[e] = {dz[e], dz2[e], z_mean[e], z_sig[e], eps[e], g_pre[e], ld_dz[e], ld_dz2[e], L[e],
-              S ? S[e] : 0, S ? S2[e] : 0, S ? stride[e] : 0, S ? stride2[e] : 0};
-    Lmax = L[e] > Lmax ? L[e] : Lmax;
+    t.a[e] = a[e < n ? e : 0];
+    Lmax = t.a[e].L > Lmax ? t.a[e].L : Lmax;
   }
-  dim3 grid((unsigned)(((int64_t)B * Lmax + 255) / 256), 2), block(256);
+  dim3 grid((unsigned)(((int64_t)B * Lmax + 255) / 256), n), block(256);
   if (g_dtype == SV_BF16) hipLaunchKernelGGL((reparam_kl_bwd_twin_kernel<bf16_t>), grid, block, 0, st, t, kl_scale, B);
   else if (g_dtype == SV_F32) hipLaunchKernelGGL((reparam_kl_bwd_twin_kernel<float>), grid, block, 0, st, t, kl_scale, B);
   else return SV_E_BADARG;
@@ -487,55 +420,36 @@ extern "C" int sv_reparam_kl_bwd(const float* dz, int32_t ld_dz, const float* dz
                                  float kl_scale, void* g_pre, int32_t g_dtype, int32_t B, int32_t L,
                                  void* stream) {
   if (!dz || !z_mean || !z_sig || !eps || !g_pre || B <= 0 || L <= 0) return SV_E_BADARG;
-  const int64_t total = (int64_t)B * L;
-  dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (g_dtype == SV_BF16)
-    hipLaunchKernelGGL((reparam_kl_bwd_kernel<bf16_t>), grid, block, 0, st, dz, ld_dz, dz2, ld_dz2,
-                       z_mean, z_sig, eps, kl_scale, (bf16_t*)g_pre, B, L);
-  else if (g_dtype == SV_F32)
-    hipLaunchKernelGGL((reparam_kl_bwd_kernel<float>), grid, block, 0, st, dz, ld_dz, dz2, ld_dz2,
-                       z_mean, z_sig, eps, kl_scale, (float*)g_pre, B, L);
-  else
-    return SV_E_BADARG;
-  SV_LAUNCH_CHECK();
-  return SV_OK;
+  const ReparamBwdArgs g = {dz, dz2, z_mean, z_sig, eps, g_pre, ld_dz, ld_dz2, L, 0, 0, 0, 0};
+  return svk_reparam_kl_bwd(&g, 1, kl_scale, g_dtype, B, (hipStream_t)stream);
 }
 
-// the twin kernels as the plan calls them, for tests and host bindings (include/splitvae.h): argument checks + the launches above
+// the two-network launches as the plan makes them, for tests and host bindings (include/splitvae.h): argument checks, then the launchers above
 extern "C" int sv_reparam_kl_fwd_twin(const sv_reparam_twin_fwd* a, void* z_lp, int32_t z_dtype, int32_t ldz, int32_t B, uint64_t seed,
                                       uint64_t step, int64_t sample_offset, void* stream) {
   if (!a || !z_lp || B <= 0 || (z_dtype != SV_BF16 && z_dtype != SV_F32)) return SV_E_BADARG;
-  const float *pre[2], *bm[2], *bs[2], *eps[2];
-  float *eo[2], *zm[2], *zs[2], *zz[2], *kl[2];
-  int zc[2], L[2], S[2];
-  int64_t sd[2];
+  ReparamFwdArgs t[2];
   for (int e = 0; e < 2; ++e) {
     const sv_reparam_twin_fwd& g = a[e];
     if (!g.pre || !g.bias_mean || !g.bias_sd || !g.z_mean || !g.z_sig || !g.z || !g.kl || g.L <= 0 || g.S < 0 || g.z_col < 0 ||
         (int64_t)g.z_col + g.L > ldz)
       return SV_E_BADARG;
-    pre[e] = g.pre; bm[e] = g.bias_mean; bs[e] = g.bias_sd; eps[e] = g.eps; eo[e] = g.eps_out; zm[e] = g.z_mean; zs[e] = g.z_sig; zz[e] = g.z;
-    kl[e] = g.kl; zc[e] = g.z_col; L[e] = g.L; S[e] = g.S; sd[e] = g.slab_stride;
+    t[e] = {g.pre, g.bias_mean, g.bias_sd, g.eps, g.eps_out, g.z_mean, g.z_sig, g.z, z_lp, g.kl, ldz, g.z_col, g.L, e /* Philox stream id = the index */,
+            g.S, g.slab_stride};
   }
-  return svk_reparam_kl_fwd_twin(pre, bm, bs, eps, eo, zm, zs, zz, z_lp, z_dtype, ldz, zc, kl, B, L, seed, step, sample_offset,
-                                 (hipStream_t)stream, nullptr, S, sd);
+  return svk_reparam_kl_fwd(t, 2, z_dtype, B, seed, step, sample_offset, (hipStream_t)stream);
 }
 
 extern "C" int sv_reparam_kl_bwd_twin(const sv_reparam_twin_bwd* a, float kl_scale, int32_t g_dtype, int32_t B, void* stream) {
   if (!a || B <= 0 || (g_dtype != SV_BF16 && g_dtype != SV_F32)) return SV_E_BADARG;
-  const float *dz[2], *dz2[2], *zm[2], *zs[2], *ep[2];
-  void* gp[2];
-  int ld[2], ld2[2], L[2], S[2], S2[2];
-  int64_t sd[2], sd2[2];
+  ReparamBwdArgs t[2];
   for (int e = 0; e < 2; ++e) {
     const sv_reparam_twin_bwd& g = a[e];
     if (!g.dz || !g.z_mean || !g.z_sig || !g.eps || !g.g_pre || g.L <= 0 || g.S < 0 || g.ld_dz < g.L) return SV_E_BADARG;
     if (g.dz2 && (g.ld_dz2 < g.L || (g.S > 0 && g.S2 < 1))) return SV_E_BADARG;
-    dz[e] = g.dz; dz2[e] = g.dz2; zm[e] = g.z_mean; zs[e] = g.z_sig; ep[e] = g.eps; gp[e] = g.g_pre; ld[e] = g.ld_dz; ld2[e] = g.ld_dz2;
-    L[e] = g.L; S[e] = g.S; S2[e] = g.S2; sd[e] = g.stride; sd2[e] = g.stride2;
+    t[e] = {g.dz, g.dz2, g.z_mean, g.z_sig, g.eps, g.g_pre, g.ld_dz, g.ld_dz2, g.L, g.S, g.S2, g.stride, g.stride2};
   }
-  return svk_reparam_kl_bwd_twin(dz, ld, dz2, ld2, zm, zs, ep, kl_scale, gp, g_dtype, B, L, (hipStream_t)stream, S, sd, S2, sd2);
+  return svk_reparam_kl_bwd(t, 2, kl_scale, g_dtype, B, (hipStream_t)stream);
 }
 
 // ============================================================================ K14 Keras Adam

@@ -67,6 +67,37 @@ def test_plan_geometry_without_gpu(lib_built):
     lib.sv_lgvae_plan_destroy(h)
 
 
+def _layout_fixture():
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "plan_layout.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("kind,index", [("lgvae", i) for i in range(7)] + [("gm", i) for i in range(2)])
+def test_workspace_layout_is_pinned(lib_built, kind, index):
+    """The workspace layout of sv_lgvae_plan / sv_gm_encoder, buffer by buffer, against tests/golden/plan_layout.json (recorded by
+    tests/golden/make_golden_plan_layout.py from the commit before the typed buffer tables): the workspace bytes, (offset, bytes) of every buffer
+    name, and SV_E_BADARG for the names the mode lacks.  One buffer that moves, shrinks, appears or disappears fails here.  Host only."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden_plan_layout", os.path.join(ROOT, "tests", "golden", "make_golden_plan_layout.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    from split_vae_amd import _lib
+    doc = _layout_fixture()
+    assert re.fullmatch(r"[0-9a-f]{40}", doc["recorded_from_commit"])
+    assert len(doc["lgvae"]) == len(gen.LGVAE_DESCS) == 7 and len(doc["gm"]) == len(gen.GM_DESCS) == 2
+    want = doc[kind][index]
+    descs, names, layout = (gen.LGVAE_DESCS, gen.LGVAE_NAMES, gen.lgvae_layout) if kind == "lgvae" else (gen.GM_DESCS, gen.GM_NAMES, gen.gm_layout)
+    assert want["desc"] == list(descs[index]) and sorted(want["buffers"]) == sorted(names)
+    got = layout(_lib.load(), descs[index])
+    assert got["workspace_bytes"] == want["workspace_bytes"]
+    for name in names:
+        assert got["buffers"][name] == want["buffers"][name], name
+    # nothing beside the fixture's buffers: they tile the workspace (256-byte granules) exactly
+    present = [v for v in got["buffers"].values() if v != "absent"]
+    assert sum((b + 255) // 256 * 256 for _, b in present) == got["workspace_bytes"]
+
+
 @pytest.mark.parametrize("gl,ll,B", [(128, 128, 512), (64, 64, 64), (256, 256, 96), (128, 128, 70), (256, 128, 64)])
 def test_latent_slab_workspace_covers_every_split(lib_built, gl, ll, B):
     """the K-slice slabs of the latent block (lat_ws_x / lat_ws_xh) are sized from the four launches' own (split, N) pairs; a slab
