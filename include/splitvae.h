@@ -627,7 +627,8 @@ int sv_lgvae_bucket_wait(sv_lgvae_plan* plan, int32_t bucket, void* stream);
 int sv_lgvae_plan_debug(sv_lgvae_plan* plan, const char* key, int64_t value);
 /* The library's side streams: hipStream_t `index` (0 .. 2) of the CURRENT device, created once per process and shared by every plan (weight-gradient
  * streams), tape (lanes) and by the SPLIT-GMVAE step's second encoder stream -- a stream per object put a later object's stream on the hardware queue of the
- * compute stream it should run beside (csrc/streams.hip).  A host binding that wants a library-compatible side stream of its own takes it from here. */
+ * compute stream it should run beside (csrc/streams.hip).  A host binding that wants a library-compatible side stream of its own takes it from here.
+ * On failure *stream is NULL and the status is non-zero: SV_E_BADARG for an index outside 0 .. 2, SV_E_STATE when the stream cannot be created. */
 int sv_side_stream(int32_t index, void** stream);
 /* number of captured (instantiated) step graphs, or a negative SV_E_* */
 int sv_lgvae_graph_count(const sv_lgvae_plan* plan);
@@ -867,12 +868,27 @@ void sv_tape_destroy(sv_tape* t);
 int32_t sv_tape_tensor(sv_tape* t, int64_t rows, int32_t cols, int32_t ld, int32_t need_grad);       /* -> tensor id (>= 0) or SV_E_* */
 int32_t sv_tape_view(sv_tape* t, int32_t src, int64_t rows, int32_t cols, int32_t ld);               /* same storage, other 2-D shape */
 int sv_tape_add(sv_tape* t, const sv_tape_node* node);
-/* The cross-lane schedule of a finalized tape, node by node (pass 0 forward, 1 backward): returns how many nodes' events the launch of `node` waits for (their indices in
- * waits[0 .. max_waits)), *records = 1 when an event is recorded behind it for another lane.  A UNARY group is one launch (waits on its first node forwards / its last
- * backwards).  Host logic only -- no GPU needed: what tests/test_abi.py pins.  0 for a single-lane tape. */
-int sv_tape_schedule(const sv_tape* t, int32_t pass, int32_t node, int32_t* waits, int32_t max_waits, int32_t* records);
+/* What a finalized tape launches: one step list per pass (0 forward, 1 backward) in issue order; sv_tape_run walks exactly these lists (wait, launch, record).
+ *   Forward: the nodes in tape order, each one SV_TAPE_PART_ALL step on its node's lane (lanes above the SV_TAPE_LANES cap fold onto the cap); consecutive UNARY
+ *     nodes of one non-zero group and one lane, at most 8, are ONE step over nodes first..last.
+ *   Backward: the same units in reverse order, each one SV_TAPE_PART_ALL step, except the hand-off: on a tape with more than one lane, a lane-0 node whose input x
+ *     has a gradient and which is a DENSE node, or a CONV node of a bf16 tape, runs its adjoint as up to three steps, in this order --
+ *       PRE   on lane 0: the CONV's in-place ReLU gate of dY and the bf16 cast of dY (a DENSE node launches nothing here: no PRE step),
+ *       WGRAD on lane 1: the weight and bias gradients, which feed only Adam,
+ *       DGRAD on lane 0: the input gradient, the critical path of the adjoint.
+ * A step's stream first waits for the events of the steps waits[0 .. n_waits) -- indices into the same pass's list, all < k -- and, when `records` is 1, records
+ * its own event behind its launches for a later step of another lane.  sv_tape_finalize derives the waits from what every step reads and writes (activations,
+ * gradients, variable gradients, a CONV's bf16 copy of dY, a lane's weight-gradient slab region), so every pair of conflicting steps on different lanes keeps the
+ * tape's order.  A single-lane tape has step lists too: SV_TAPE_PART_ALL only, no waits, no records.  Host logic only -- no GPU needed.
+ * sv_tape_steps: the number of steps, or SV_E_BADARG (not finalized, pass outside 0..1).  sv_tape_step_info: step k into *out and its first max_waits wait indices
+ * into waits (may be NULL); SV_E_BADARG: not finalized, pass outside 0..1, k outside the list, out NULL. */
+enum { SV_TAPE_PART_ALL = 0, SV_TAPE_PART_PRE, SV_TAPE_PART_WGRAD, SV_TAPE_PART_DGRAD };
+typedef struct { int32_t first, last, part, lane, records, n_waits; } sv_tape_step;
+int sv_tape_steps(const sv_tape* t, int32_t pass);
+int sv_tape_step_info(const sv_tape* t, int32_t pass, int32_t k, sv_tape_step* out, int32_t* waits, int32_t max_waits);
 /* reported[j] = sum_i matrix[j * 16 + i] * mean_b loss_i: the `losses` list of train_step (spair/trainer.py:158-160, :208-216) */
 int sv_tape_set_report(sv_tape* t, const float* matrix, int32_t n_report);
+/* SV_E_UNSUPPORTED: two DENSE / CONV nodes name the same w_off, or the same b_off >= 0 (a layer's adjoint ASSIGNS its variables' gradients: one writer each) */
 int sv_tape_finalize(sv_tape* t);
 int64_t sv_tape_workspace_bytes(const sv_tape* t);
 int sv_tape_bind(sv_tape* t, void* workspace, int64_t bytes, void* stream);                           /* zero-fills the workspace */

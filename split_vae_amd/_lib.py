@@ -57,6 +57,11 @@ class TapeNode(C.Structure):
                                           "loss_idx", "dyn_idx", "mode", "R", "stream_id", "group", "lane")])
 
 
+class TapeStep(C.Structure):
+    """sv_tape_step (include/splitvae.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("first", "last", "part", "lane", "records", "n_waits")]
+
+
 class TapeRunArgs(C.Structure):
     """sv_tape_run_args (include/splitvae.h)."""
     _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("loss_weights", C.POINTER(C.c_float)), ("n_weights", C.c_int32),
@@ -69,6 +74,7 @@ class TapeRunArgs(C.Structure):
 TAPE_DENSE, TAPE_CONV, TAPE_UNARY, TAPE_SAMPLE, TAPE_LOGITNOISE, TAPE_UPSAMPLE, TAPE_STN, TAPE_RENDER, TAPE_ZPRES, TAPE_LOSS, TAPE_NOISE = range(11)
 TAPE_COPY, TAPE_RELU, TAPE_SIGMOID, TAPE_SOFTPLUS, TAPE_CLAMP, TAPE_SCALE = range(6)
 TAPE_PHASE_FORWARD, TAPE_PHASE_BACKWARD, TAPE_PHASE_ADAM = 1, 2, 4
+TAPE_PART_ALL, TAPE_PART_PRE, TAPE_PART_WGRAD, TAPE_PART_DGRAD = range(4)
 TAPE_MAX_LOSS = 16
 
 
@@ -229,7 +235,8 @@ SYMBOLS = {
     "sv_tape_tensor": (_i32, [_vp, _i64, _i32, _i32, _i32]),
     "sv_tape_view": (_i32, [_vp, _i32, _i64, _i32, _i32]),
     "sv_tape_add": (C.c_int, [_vp, C.POINTER(TapeNode)]),
-    "sv_tape_schedule": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp]),
+    "sv_tape_steps": (C.c_int, [_vp, _i32]),
+    "sv_tape_step_info": (C.c_int, [_vp, _i32, _i32, C.POINTER(TapeStep), _vp, _i32]),
     "sv_tape_set_report": (C.c_int, [_vp, C.POINTER(C.c_float), _i32]),
     "sv_tape_finalize": (C.c_int, [_vp]),
     "sv_tape_workspace_bytes": (_i64, [_vp]),

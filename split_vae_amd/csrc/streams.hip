@@ -38,8 +38,10 @@ hipStream_t sv_shared_stream(int k) {
 
 extern "C" int sv_side_stream(int32_t index, void** stream) {
   if (!stream) return SV_E_BADARG;
+  *stream = nullptr;
+  if (index < 0 || index >= SV_SHARED_STREAMS) return SV_E_BADARG;
   hipStream_t s = sv_shared_stream(index);
-  if (!s) return index < 0 || index >= SV_SHARED_STREAMS ? SV_E_BADARG : (int)hipGetLastError();
+  if (!s) { (void)hipGetLastError(); return SV_E_STATE; }       // (no device, or the stream could not be created: the HIP error may already be consumed, or 0)
   *stream = (void*)s;
   return SV_OK;
 }

@@ -19,9 +19,10 @@
 //
 // LANES (round 6): a node may name a lane (sv_tape_node::lane, 0 = the caller's stream).  Independent branches of the model -- LG-SPAIR's x-hat / background
 // encoders and decoders beside the object pipeline (spair/spair.py:84-104) -- then run on their own HIP streams: the step is ~240 launches of 5-30 us, bound by
-// their latency, not by any unit of the chip.  sv_tape_finalize derives every cross-lane dependency from the nodes' tensors (read-after-write, write-after-read,
-// write-after-write, and the read-modify-write of every gradient accumulation, in tape order) and sv_tape_run turns them into events: conflicting accesses keep
-// the tape's order, so the lanes compute the single-stream step bit for bit (tests/test_gpu_spair_model.py).
+// their latency, not by any unit of the chip.  sv_tape_finalize builds ONE list of steps per pass (what is launched, on which lane) and derives every cross-lane
+// dependency from what the steps touch (read-after-write, write-after-read, write-after-write, and the read-modify-write of every gradient accumulation, in tape
+// order); sv_tape_run walks the lists -- wait, launch, record -- and sv_tape_step_info reports them: conflicting accesses keep the tape's order, so the lanes
+// compute the single-stream step bit for bit (tests/test_gpu_spair_model.py).
 #include <string.h>
 #include <algorithm>
 #include <set>
@@ -307,27 +308,29 @@ struct sv_tape {
   char* ws = nullptr;
   std::vector<std::pair<int, int64_t>> zero_y;     // (tensor, floats) of the split-K Dense outputs: zeroed by ONE launch at the start of the forward pass
   bool zero_at_start = false;
-  // lanes: unit = one node or one UNARY group (units are launched in tape order; a lane's launches are stream-ordered among themselves)
+  // What a pass launches, in issue order (built once by sv_tape_finalize: build_steps, build_schedules): the run loop, the dependency derivation and sv_tape_step_info
+  // all read this list.  A step is one node or one UNARY group, or one part of a DENSE / CONV adjoint whose weight gradient is handed to lane 1.
   enum { MAX_LANES = 4 };
-  struct Sched {
-    std::vector<std::vector<int>> waits;   // [first node of a unit] -> nodes whose event the unit's stream waits for first
-    std::vector<char> rec;                 // [last node of a unit] -> record the unit's event behind it
+  struct Step {
+    int first, last, part, lane;           // nodes [first, last]; SV_TAPE_PART_*; the lane it is launched on (after the SV_TAPE_LANES cap)
+    bool records = false;                  // an event is recorded behind it for a later step of another lane
+    bool per_part = false;                 // a group whose adjoint runs one launch per part, last part first (group_sources_overlap)
+    std::vector<int> waits;                // earlier steps of the pass whose events this step's stream waits for first
   };
-  Sched fs, bs;                            // forward / backward pass
+  std::vector<Step> steps[2];              // forward / backward pass
+  std::vector<hipEvent_t> ev_step[2];      // per step: its cross-lane event (created on first use)
   int nlanes = 1;
   hipStream_t lane_st[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-  std::vector<hipEvent_t> ev_node, ev_wg;      // per node: the unit's cross-lane event; "dY is ready" for a weight gradient sent to lane 1's stream
   ~sv_tape() {
     for (int l = 1; l < MAX_LANES; ++l) {
       if (lane_st[l]) (void)hipStreamSynchronize(lane_st[l]);          // (shared: not destroyed)
       if (ev_join[l]) (void)hipEventDestroy(ev_join[l]);
     }
     if (ev_fork) (void)hipEventDestroy(ev_fork);
-    for (auto e : ev_node)
-      if (e) (void)hipEventDestroy(e);
-    for (auto e : ev_wg)
-      if (e) (void)hipEventDestroy(e);
+    for (auto& v : ev_step)
+      for (auto e : v)
+        if (e) (void)hipEventDestroy(e);
   }
 
   float* act(int t) const { return (float*)(ws + off_act) + tens[t].off; }
@@ -449,25 +452,62 @@ extern "C" int sv_tape_set_report(sv_tape* t, const float* matrix, int32_t n_rep
   return SV_OK;
 }
 
-// units of the forward pass in launch order: [first, last] node indices (a UNARY group of one lane is one launch)
-static std::vector<std::pair<int, int>> tape_units(const sv_tape* t) {
-  std::vector<std::pair<int, int>> u;
-  for (size_t i = 0; i < t->nodes.size();) {
-    const sv_tape_node& n = t->nodes[i];
-    size_t e = i + 1;
-    if (n.kind == SV_TAPE_UNARY && n.group)
-      while (e < t->nodes.size() && e - i < SV_TAPE_MAX_PARTS && t->nodes[e].kind == SV_TAPE_UNARY && t->nodes[e].group == n.group && t->nodes[e].lane == n.lane) ++e;
-    u.push_back({(int)i, (int)e - 1});
-    i = e;
+// Two parts of a group that add into overlapping columns of one gradient (a tile of z into two places) would read-modify-write them from different threads of one
+// launch, in no order: such a group runs its adjoint as one launch per part, last part first.  (Views of a root are compared by the root alone.)
+static bool group_sources_overlap(const sv_tape* t, int b, int e) {
+  auto adds = [&](const sv_tape_node& n) { return t->tens[n.y].goff >= 0 && t->tens[n.x].goff >= 0; };
+  for (int i = b; i < e; ++i) {
+    const sv_tape_node& p = t->nodes[i];
+    if (!adds(p)) continue;
+    for (int j = i + 1; j < e; ++j) {
+      const sv_tape_node& q = t->nodes[j];
+      if (!adds(q) || t->root(p.x) != t->root(q.x)) continue;
+      if (p.x != q.x || (p.xo < q.xo + q.n && q.xo < p.xo + p.n)) return true;
+    }
   }
-  return u;
+  return false;
 }
 
-// Resources: activation storage of a root tensor (id r), its gradient storage (NT + r), a layer's variable gradients (2 NT + k).  Conservative access sets per node
-// (more edges than strictly needed, never fewer): the forward pass READS a node's input activations and WRITES its outputs; loss nodes ADD into their operands'
-// gradients there; the backward pass reads activations only (never a conflict) and READ-MODIFY-WRITES the gradient of every tensor the node touches plus its own
-// variables' gradients.  An edge u -> v is kept when the two units are on different lanes; a lane's own launches are ordered by its stream, so per (unit, other lane)
-// only the latest producer is waited for, and not again if an earlier unit of the same lane already waited for it or a later one.
+// The two step lists (include/splitvae.h: sv_tape_step_info states the rule).  Forward: the nodes in tape order, a run of UNARY nodes of one non-zero group and one
+// lane (at most SV_TAPE_MAX_PARTS) as one step.  Backward: the same units in reverse.  The weight gradient of a lane-0 DENSE layer -- and of a lane-0 CONV layer at
+// bf16 -- whose input has a gradient feeds only Adam: on a tape with lanes it is a step of its own on lane 1, and the input-gradient chain, the critical path of the
+// adjoint at ~11 us per launch, continues on lane 0 at once.  Measured (profiles/r06_spair_lanes.txt, 32 images): Dense layers' weight gradients on lane 1 2.65 -> 2.49 ms
+// (fp32) / 2.60 -> 2.38 (bf16); the conv layers' too: 2.52 (fp32: the 77-85 us fp32 weight gradients of the object decoder make lane 1 the longer one) / 2.35 (bf16).
+static void build_steps(sv_tape* t) {
+  static const bool wside = SV_TUNE_INT("SV_TAPE_WGRAD_SIDE", 1) != 0;
+  const int N = (int)t->nodes.size();
+  std::vector<sv_tape::Step>&F = t->steps[0], &R = t->steps[1];
+  for (int i = 0; i < N;) {
+    const sv_tape_node& n = t->nodes[i];
+    int e = i + 1;
+    if (n.kind == SV_TAPE_UNARY && n.group)
+      while (e < N && e - i < SV_TAPE_MAX_PARTS && t->nodes[e].kind == SV_TAPE_UNARY && t->nodes[e].group == n.group && t->nodes[e].lane == n.lane) ++e;
+    sv_tape::Step s;
+    s.first = i; s.last = e - 1; s.part = SV_TAPE_PART_ALL; s.lane = n.lane;
+    s.per_part = e - i > 1 && group_sources_overlap(t, i, e);
+    F.push_back(s);
+    i = e;
+  }
+  for (size_t k = F.size(); k-- > 0;) {
+    sv_tape::Step s = F[k];
+    const sv_tape_node& n = t->nodes[s.first];
+    const bool layer = n.kind == SV_TAPE_DENSE || (n.kind == SV_TAPE_CONV && t->dtype == SV_BF16);
+    if (!(wside && layer && t->nlanes > 1 && n.lane == 0 && t->tens[n.x].goff >= 0)) { R.push_back(s); continue; }
+    if (n.kind == SV_TAPE_CONV) { s.part = SV_TAPE_PART_PRE; R.push_back(s); }       // (a DENSE adjoint launches nothing in front of its two GEMMs)
+    s.part = SV_TAPE_PART_WGRAD; s.lane = 1; R.push_back(s);
+    s.part = SV_TAPE_PART_DGRAD; s.lane = 0; R.push_back(s);
+  }
+  for (int p = 0; p < 2; ++p) t->ev_step[p].assign(t->steps[p].size(), nullptr);
+}
+
+// Resources: activation storage of a root tensor (id r), its gradient storage (NT + r), a layer's variable gradients (2 NT + k), a conv layer's bf16 copy of dY
+// (2 NT + N + node), a lane's slab region of the conv weight gradients (2 NT + 2 N + lane).  Conservative access sets per node (more edges than strictly needed, never
+// fewer): the forward pass READS a node's input activations and WRITES its outputs; loss nodes ADD into their operands' gradients there; the backward pass reads
+// activations only (never a conflict) and READ-MODIFY-WRITES the gradient of every tensor the node touches plus its own variables' gradients.  The parts of a DENSE /
+// CONV adjoint: PRE read-modify-writes G(y) (the ReLU gate) and writes the copy of dY; WGRAD reads both and writes the variables' gradients and, for CONV, the slabs of
+// the lane it runs on; DGRAD reads both and read-modify-writes G(x).  An edge u -> v is kept when the two steps are on different lanes; a lane's own launches are
+// ordered by its stream, so per (step, other lane) only the latest producer is waited for, and not again if an earlier step of the same lane already waited for it or
+// a later one.
 static void build_schedules(sv_tape* t) {
   const int NT = (int)t->tens.size(), N = (int)t->nodes.size();
   std::vector<int64_t> wkeys;
@@ -476,7 +516,8 @@ static void build_schedules(sv_tape* t) {
     wkeys.push_back(w_off);
     return 2 * NT + (int)wkeys.size() - 1;
   };
-  auto acc = [&](const sv_tape_node& n, bool backward, std::vector<int>& rd, std::vector<int>& wr) {
+  auto acc = [&](int i, const sv_tape::Step& s, bool backward, std::vector<int>& rd, std::vector<int>& wr) {
+    const sv_tape_node& n = t->nodes[i];
     const int ins[6] = {n.x, n.t2, n.t3, n.t4, n.t5, n.t6};
     auto A = [&](int id) { return t->tens[id].root; };
     auto G = [&](int id) { return NT + t->tens[id].root; };
@@ -488,32 +529,32 @@ static void build_schedules(sv_tape* t) {
       if (stn_box) wr.push_back(A(n.t3));
       if (n.kind == SV_TAPE_ZPRES || n.kind == SV_TAPE_LOSS)
         for (int k = 0; k < 3; ++k) if (hasg(ins[k])) wr.push_back(G(ins[k]));
+    } else if (n.kind == SV_TAPE_DENSE || n.kind == SV_TAPE_CONV) {
+      const bool all = s.part == SV_TAPE_PART_ALL, copy = n.kind == SV_TAPE_CONV && t->dtype == SV_BF16;
+      const int dy = 2 * NT + N + i;
+      if (hasg(n.y)) (all || s.part == SV_TAPE_PART_PRE ? wr : rd).push_back(G(n.y));
+      if (copy) (all || s.part == SV_TAPE_PART_PRE ? wr : rd).push_back(dy);
+      if (all || s.part == SV_TAPE_PART_WGRAD) {
+        wr.push_back(wres(n.w_off));
+        if (n.kind == SV_TAPE_CONV) wr.push_back(2 * NT + 2 * N + s.lane);
+      }
+      if ((all || s.part == SV_TAPE_PART_DGRAD) && hasg(n.x)) wr.push_back(G(n.x));
     } else {
-      for (int k = 0; k < 6; ++k) if (ins[k] >= 0) rd.push_back(A(ins[k]));
-      if (n.y >= 0) rd.push_back(A(n.y));
       for (int k = 0; k < 6; ++k) if (hasg(ins[k])) wr.push_back(G(ins[k]));
       if (hasg(n.y)) wr.push_back(G(n.y));
-      if ((n.kind == SV_TAPE_DENSE || n.kind == SV_TAPE_CONV) && n.w_off >= 0) wr.push_back(wres(n.w_off));
     }
   };
-  const std::vector<std::pair<int, int>> units = tape_units(t);
   for (int pass = 0; pass < 2; ++pass) {
-    sv_tape::Sched& S = pass ? t->bs : t->fs;
-    S.waits.assign(N, {});
-    S.rec.assign(N, 0);
-    const int NR = 2 * NT + N + 1;
-    std::vector<int> last_w(NR, -1);                 // unit that last wrote the resource
-    std::vector<std::vector<int>> readers(NR);       // units that read it since
-    const int U = (int)units.size();
-    std::vector<int> ulane(U), upos(U);              // (upos: position in this pass's launch order)
+    std::vector<sv_tape::Step>& S = t->steps[pass];
+    const int NR = 2 * NT + 2 * N + sv_tape::MAX_LANES;
+    std::vector<int> last_w(NR, -1);                 // step that last wrote the resource
+    std::vector<std::vector<int>> readers(NR);       // steps that read it since
     int seen[sv_tape::MAX_LANES][sv_tape::MAX_LANES];
     for (auto& r : seen) for (auto& v : r) v = -1;
-    for (int k = 0; k < U; ++k) {
-      const int u = pass ? U - 1 - k : k;
-      upos[u] = k;
-      ulane[u] = t->nodes[units[u].first].lane;
+    int nw = 0;
+    for (int u = 0; u < (int)S.size(); ++u) {
       std::vector<int> rd, wr;
-      for (int i = units[u].first; i <= units[u].second; ++i) acc(t->nodes[i], pass == 1, rd, wr);
+      for (int i = S[u].first; i <= S[u].last; ++i) acc(i, S[u], pass == 1, rd, wr);
       std::set<int> deps;
       for (int r : rd) if (last_w[r] >= 0) deps.insert(last_w[r]);
       for (int w : wr) {
@@ -523,32 +564,36 @@ static void build_schedules(sv_tape* t) {
       int latest[sv_tape::MAX_LANES];
       for (auto& v : latest) v = -1;
       for (int d : deps)
-        if (d != u && ulane[d] != ulane[u] && (latest[ulane[d]] < 0 || upos[d] > upos[latest[ulane[d]]])) latest[ulane[d]] = d;
+        if (S[d].lane != S[u].lane && d > latest[S[d].lane]) latest[S[d].lane] = d;
       for (int l = 0; l < sv_tape::MAX_LANES; ++l) {
         const int d = latest[l];
-        if (d < 0 || upos[d] <= seen[ulane[u]][l]) continue;
-        seen[ulane[u]][l] = upos[d];
-        // the producer unit's event sits behind its last launched node: forward = the unit's last node, backward = its first
-        const int evn = pass ? units[d].first : units[d].second;
-        S.waits[pass ? units[u].second : units[u].first].push_back(evn);
-        S.rec[evn] = 1;
+        if (d <= seen[S[u].lane][l]) continue;
+        seen[S[u].lane][l] = d;
+        S[u].waits.push_back(d);
+        S[d].records = true;
+        ++nw;
+      }
+      if (SV_TUNE_FLAG("SV_TAPE_LANES_DEBUG") && !S[u].waits.empty()) {   // the schedule, one line per step with a cross-lane wait
+        fprintf(stderr, "tape %s: step %d (nodes %d..%d kind %d part %d lane %d) waits for", pass ? "bwd" : "fwd", u, S[u].first, S[u].last,
+                t->nodes[S[u].first].kind, S[u].part, S[u].lane);
+        for (int d : S[u].waits) fprintf(stderr, " step %d (nodes %d..%d part %d lane %d)", d, S[d].first, S[d].last, S[d].part, S[d].lane);
+        fprintf(stderr, "\n");
       }
       for (int r : rd) readers[r].push_back(u);
       for (int w : wr) { last_w[w] = u; readers[w].clear(); }
     }
-    if (SV_TUNE_FLAG("SV_TAPE_LANES_DEBUG")) {              // the schedule, one line per unit with a cross-lane wait
-      int nw = 0;
-      for (int k = 0; k < U; ++k) {
-        const int u = pass ? U - 1 - k : k, at = pass ? units[u].second : units[u].first;
-        for (int d : S.waits[at]) { fprintf(stderr, "tape %s: unit %d (nodes %d..%d kind %d lane %d) waits for node %d (lane %d)\n", pass ? "bwd" : "fwd", k, units[u].first, units[u].second, t->nodes[units[u].first].kind, ulane[u], d, t->nodes[d].lane); ++nw; }
-      }
-      fprintf(stderr, "tape %s: %d units, %d cross-lane waits\n", pass ? "bwd" : "fwd", U, nw);
-    }
+    if (SV_TUNE_FLAG("SV_TAPE_LANES_DEBUG")) fprintf(stderr, "tape %s: %d steps, %d cross-lane waits\n", pass ? "bwd" : "fwd", (int)S.size(), nw);
   }
 }
 
 extern "C" int sv_tape_finalize(sv_tape* t) {
   if (!t || t->finalized) return SV_E_BADARG;
+  // every variable has ONE writer: the weight-gradient kernels assign (svk_dense_f32_wgrad's zeroed_once without split K, the conv layers' slab sums), so a
+  // second layer on the same variables would overwrite the first one's gradient
+  std::set<int64_t> w_seen, b_seen;
+  for (const sv_tape_node& n : t->nodes)
+    if (n.kind == SV_TAPE_DENSE || n.kind == SV_TAPE_CONV)
+      if (!w_seen.insert(n.w_off).second || (n.b_off >= 0 && !b_seen.insert(n.b_off).second)) return SV_E_UNSUPPORTED;
   auto gr = [&](int id) { return id >= 0 && t->tens[id].goff >= 0; };
   auto wr = [&](int id) { if (gr(id)) t->tens[t->root(id)].writers++; };
   // writers of every gradient (views count on their root)
@@ -650,25 +695,25 @@ extern "C" int sv_tape_finalize(sv_tape* t) {
   }
   t->nlanes = maxlane + 1;
   if (any_conv) { t->off_wgrad = o; o += al(SV_WGRAD_WS_BYTES) * t->nlanes; }
-  if (t->nlanes > 1) { build_schedules(t); t->ev_node.assign(t->nodes.size(), nullptr); t->ev_wg.assign(t->nodes.size(), nullptr); }
+  build_steps(t);
+  if (t->nlanes > 1) build_schedules(t);
   t->ws_bytes = o;
   t->finalized = true;
   return SV_OK;
 }
 
-// The cross-lane schedule sv_tape_finalize derived, one node at a time (host logic: tests/test_abi.py checks it without a GPU).  pass 0: forward, 1: backward.
-// Returns the number of nodes whose event `node`'s launch waits for (written to waits[0 .. max_waits)); *records = 1 when an event is recorded behind the node's
-// launch for a later node of another lane.  A UNARY group is one launch: its waits sit on its first node in the forward pass and on its last in the backward
-// pass, its event behind its last / first node.  SV_E_BADARG: not finalized, bad pass / node.  A single-lane tape has no schedule: 0 waits, *records = 0.
-extern "C" int sv_tape_schedule(const sv_tape* t, int32_t pass, int32_t node, int32_t* waits, int32_t max_waits, int32_t* records) {
-  if (!t || !t->finalized || pass < 0 || pass > 1 || node < 0 || node >= (int)t->nodes.size()) return SV_E_BADARG;
-  if (records) *records = 0;
-  if (t->nlanes <= 1) return 0;
-  const sv_tape::Sched& S = pass ? t->bs : t->fs;
-  if (records) *records = S.rec[node];
-  const int n = (int)S.waits[node].size();
-  for (int i = 0; i < n && i < max_waits && waits; ++i) waits[i] = S.waits[node][i];
-  return n;
+// The step lists sv_tape_finalize built: what sv_tape_run launches, on which lane, behind which events (host logic: tests/test_abi.py and tests/test_tape_host.py
+// check it without a GPU).  pass 0: forward, 1: backward.
+extern "C" int sv_tape_steps(const sv_tape* t, int32_t pass) {
+  if (!t || !t->finalized || pass < 0 || pass > 1) return SV_E_BADARG;
+  return (int)t->steps[pass].size();
+}
+extern "C" int sv_tape_step_info(const sv_tape* t, int32_t pass, int32_t k, sv_tape_step* out, int32_t* waits, int32_t max_waits) {
+  if (!t || !t->finalized || pass < 0 || pass > 1 || k < 0 || k >= (int)t->steps[pass].size() || !out) return SV_E_BADARG;
+  const sv_tape::Step& s = t->steps[pass][k];
+  out->first = s.first; out->last = s.last; out->part = s.part; out->lane = s.lane; out->records = s.records ? 1 : 0; out->n_waits = (int)s.waits.size();
+  for (int i = 0; i < out->n_waits && i < max_waits && waits; ++i) waits[i] = s.waits[i];
+  return SV_OK;
 }
 
 extern "C" int64_t sv_tape_workspace_bytes(const sv_tape* t) { return (t && t->finalized) ? t->ws_bytes : -1; }
@@ -804,69 +849,51 @@ int node_forward(sv_tape* t, size_t i, const sv_tape_run_args* a, bool with_grad
   return SV_E_BADARG;
 }
 
-hipStream_t lane_stream(sv_tape* t, int lane, hipStream_t st);
+// parts of a DENSE / CONV adjoint (a mask: a step's SV_TAPE_PART_ALL is all three); the other kinds run whole
+enum { PART_PRE = 1, PART_WGRAD = 2, PART_DGRAD = 4, PART_ALL = 7 };
 
-int node_backward(sv_tape* t, size_t i, const sv_tape_run_args* a, hipStream_t st) {
+int node_backward(sv_tape* t, size_t i, const sv_tape_run_args* a, int parts, int lane, hipStream_t st) {
   const sv_tape_node& n = t->nodes[i];
   const sv_tape::Extra& e = t->ex[i];
   auto T = [&](int id) -> const TT& { return t->tens[id]; };
   auto multi = [&](int id) { return t->tens[t->root(id)].writers > 1; };
   switch (n.kind) {
-    case SV_TAPE_DENSE: case SV_TAPE_CONV: {
+    case SV_TAPE_DENSE: {
       const TT &x = T(n.x), &y = T(n.y);
       float* gy = t->grad(n.y);
-      if (!gy) return SV_OK;
-      if (n.act == SV_ACT_RELU && n.kind == SV_TAPE_CONV) {            // this layer's ReLU: dY *= (y > 0), in place (Dense: gated on load)
-        hipLaunchKernelGGL(unary_bwd_kernel, dim3(nblk(y.rows * y.cols)), dim3(256), 0, st, (int)SV_TAPE_RELU, gy, y.ld, 0, gy, t->act(n.y), y.ld, 0,
-                           y.rows * y.cols, y.cols, 1, 0.f, 0.f, 1);
-        SV_LAUNCH_CHECK();
-      }
       float* gx = t->grad(n.x);
-      // (where a lane-0 layer's weight gradient goes: see the Dense case)
-      static const bool wside = SV_TUNE_INT("SV_TAPE_WGRAD_SIDE", 1) != 0;
-      auto wgrad_stream = [&](hipStream_t* ws, int* wlane) -> int {     // call when everything the weight gradient reads has been enqueued on st
-        *ws = st; *wlane = t->nlanes > 1 ? n.lane : 0;
-        if (!(wside && t->nlanes > 1 && n.lane == 0 && gx)) return SV_OK;
-        // conv layers: at bf16 only.  Measured (profiles/r06_spair_lanes.txt, 32 images): Dense layers' weight gradients on lane 1 2.65 -> 2.49 ms (fp32) / 2.60 -> 2.38
-        // (bf16); the conv layers' too: 2.52 (fp32: the 77-85 us fp32 weight gradients of the object decoder make lane 1 the longer one) / 2.35 (bf16)
-        if (n.kind == SV_TAPE_CONV && t->dtype != SV_BF16) return SV_OK;
-        hipStream_t s1 = lane_stream(t, 1, st);
-        if (s1 == st) return SV_OK;
-        if (!t->ev_wg[i] && hipEventCreateWithFlags(&t->ev_wg[i], hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
-        if (hipEventRecord(t->ev_wg[i], st) != hipSuccess || hipStreamWaitEvent(s1, t->ev_wg[i], 0) != hipSuccess) return (int)hipGetLastError();
-        *ws = s1; *wlane = 1;                  // (lane 1's slab workspace: its own conv layers use it in the same stream's order)
-        return SV_OK;
-      };
-      if (n.kind == SV_TAPE_DENSE) {
-        const float* gate = n.act == SV_ACT_RELU ? t->act(n.y) : nullptr;
-        // The weight gradient feeds only Adam: with lanes on, a lane-0 layer's goes to lane 1's stream behind an event (dY is final here: every consumer of y ran
-        // its adjoint already, and nothing writes the gradient buffers again before the next step's zero fill, which follows the join) and the input-gradient chain --
-        // the critical path of the adjoint, ~11 us per launch -- continues at once.  The variables' gradients are written by this launch alone.
-        hipStream_t ws;
-        int wl;
-        SV_TRY(wgrad_stream(&ws, &wl));
+      if (!gy) return SV_OK;
+      const float* gate = n.act == SV_ACT_RELU ? t->act(n.y) : nullptr;       // (this layer's ReLU: gated on load)
+      if (parts & PART_WGRAD)
         SV_TRY(svk_dense_f32_wgrad(t->act(n.x), x.ld, gy, y.ld, a->grads + n.w_off, n.b_off >= 0 ? a->grads + n.b_off : nullptr, (int)x.rows, x.cols,
-                                   y.cols, 1, gate, ws));
-        if (gx) SV_TRY(svk_dense_f32_dgrad(gy, y.ld, a->params + n.w_off, gx, x.ld, (int)x.rows, x.cols, y.cols, multi(n.x) ? 1 : 2, gate, st));
-        return SV_OK;
+                                   y.cols, 1, gate, st));
+      if ((parts & PART_DGRAD) && gx) SV_TRY(svk_dense_f32_dgrad(gy, y.ld, a->params + n.w_off, gx, x.ld, (int)x.rows, x.cols, y.cols, multi(n.x) ? 1 : 2, gate, st));
+      return SV_OK;
+    }
+    case SV_TAPE_CONV: {
+      const TT& y = T(n.y);
+      float* gy = t->grad(n.y);
+      float* gx = t->grad(n.x);
+      if (!gy) return SV_OK;
+      const bool bf = t->dtype == SV_BF16;     // bf16 operands (x was cast in the forward pass), fp32 gradients: dx is ADDED to the zeroed buffer
+      if (parts & PART_PRE) {
+        if (n.act == SV_ACT_RELU) {            // this layer's ReLU: dY *= (y > 0), in place
+          hipLaunchKernelGGL(unary_bwd_kernel, dim3(nblk(y.rows * y.cols)), dim3(256), 0, st, (int)SV_TAPE_RELU, gy, y.ld, 0, gy, t->act(n.y), y.ld, 0,
+                             y.rows * y.cols, y.cols, 1, 0.f, 0.f, 1);
+          SV_LAUNCH_CHECK();
+        }
+        if (bf) {
+          const int64_t n4 = y.rows * y.ld / 4;
+          hipLaunchKernelGGL(cast_bf16_kernel, dim3(nblk(n4)), dim3(256), 0, st, gy, (bf16_t*)t->scr(e.scratch2), n4);
+          SV_LAUNCH_CHECK();
+        }
       }
-      const size_t es = t->dtype == SV_BF16 ? 2 : 4;
-      if (t->dtype == SV_BF16) {               // bf16 operands (x was cast in the forward pass), fp32 gradients: dx is ADDED to the zeroed buffer
-        const int64_t n4 = y.rows * y.ld / 4;
-        hipLaunchKernelGGL(cast_bf16_kernel, dim3(nblk(n4)), dim3(256), 0, st, gy, (bf16_t*)t->scr(e.scratch2), n4);
-        SV_LAUNCH_CHECK();
-        hipStream_t ws;
-        int wl;
-        SV_TRY(wgrad_stream(&ws, &wl));          // (behind the cast: the weight gradient reads the bf16 copy of dY)
-        SV_TRY(sv_conv2d_nhwc_wgrad_ws(&e.cd, t->scr(e.scratch), t->scr(e.scratch2), a->grads + n.w_off, a->grads + n.b_off, t->wgrad_ws(wl), SV_WGRAD_WS_BYTES, ws));
-        if (gx) SV_TRY(sv_conv2d_nhwc_dgrad(&e.cd, t->scr(e.scratch2), t->ws + t->off_arena + e.wd_off * es, nullptr, gx, 1, st));
-        return SV_OK;
-      }
-      hipStream_t ws;
-      int wl;
-      SV_TRY(wgrad_stream(&ws, &wl));
-      SV_TRY(sv_conv2d_nhwc_wgrad_ws(&e.cd, t->act(n.x), gy, a->grads + n.w_off, a->grads + n.b_off, t->wgrad_ws(wl), SV_WGRAD_WS_BYTES, ws));
-      if (gx) SV_TRY(sv_conv2d_nhwc_dgrad(&e.cd, gy, t->ws + t->off_arena + e.wd_off * es, nullptr, gx, multi(n.x) ? 1 : 0, st));
+      const void* xin = bf ? (const void*)t->scr(e.scratch) : t->act(n.x);
+      const void* dy = bf ? (const void*)t->scr(e.scratch2) : gy;
+      // (the slab region of the lane the launch is on: conv weight gradients of two lanes may be in flight together)
+      if (parts & PART_WGRAD) SV_TRY(sv_conv2d_nhwc_wgrad_ws(&e.cd, xin, dy, a->grads + n.w_off, a->grads + n.b_off, t->wgrad_ws(lane), SV_WGRAD_WS_BYTES, st));
+      if ((parts & PART_DGRAD) && gx)
+        SV_TRY(sv_conv2d_nhwc_dgrad(&e.cd, dy, t->ws + t->off_arena + e.wd_off * (bf ? 2 : 4), nullptr, gx, bf || multi(n.x) ? 1 : 0, st));
       return SV_OK;
     }
     case SV_TAPE_UNARY: {
@@ -952,23 +979,7 @@ int node_backward(sv_tape* t, size_t i, const sv_tape_run_args* a, hipStream_t s
   }
 }
 
-// [i, end) = a run of UNARY nodes of one group (at most SV_TAPE_MAX_PARTS)
-size_t group_end(const sv_tape* t, size_t i) {
-  const sv_tape_node& n = t->nodes[i];
-  if (n.kind != SV_TAPE_UNARY || !n.group) return i + 1;
-  size_t e = i + 1;
-  while (e < t->nodes.size() && e - i < SV_TAPE_MAX_PARTS && t->nodes[e].kind == SV_TAPE_UNARY && t->nodes[e].group == n.group && t->nodes[e].lane == n.lane) ++e;
-  return e;
-}
-size_t group_begin(const sv_tape* t, size_t i) {       // the run that ENDS at i, as the forward pass cut it (scan from the group's first node)
-  const sv_tape_node& n = t->nodes[i];
-  if (n.kind != SV_TAPE_UNARY || !n.group) return i;
-  size_t f = i;
-  while (f > 0 && t->nodes[f - 1].kind == SV_TAPE_UNARY && t->nodes[f - 1].group == n.group && t->nodes[f - 1].lane == n.lane) --f;
-  size_t b = f;
-  while (b + SV_TAPE_MAX_PARTS <= i) b += SV_TAPE_MAX_PARTS;
-  return b;
-}
+// [b, e) = the UNARY nodes of one step
 int group_forward(sv_tape* t, size_t b, size_t e, hipStream_t st) {
   UMulti m;
   memset(&m, 0, sizeof(m));
@@ -986,25 +997,7 @@ int group_forward(sv_tape* t, size_t b, size_t e, hipStream_t st) {
   SV_LAUNCH_CHECK();
   return SV_OK;
 }
-// Two parts of a group that add into overlapping columns of one gradient (a tile of z into two places) would read-modify-write them from different threads of one
-// launch, in no order: such a group runs its adjoint as one launch per part, last part first.  (Views of a root are compared by the root alone.)
-bool group_sources_overlap(const sv_tape* t, size_t b, size_t e) {
-  for (size_t i = b; i < e; ++i) {
-    const sv_tape_node& p = t->nodes[i];
-    if (!t->grad(p.y) || !t->grad(p.x)) continue;
-    for (size_t j = i + 1; j < e; ++j) {
-      const sv_tape_node& q = t->nodes[j];
-      if (!t->grad(q.y) || !t->grad(q.x) || t->root(p.x) != t->root(q.x)) continue;
-      if (p.x != q.x || (p.xo < q.xo + q.n && q.xo < p.xo + p.n)) return true;
-    }
-  }
-  return false;
-}
-int group_backward(sv_tape* t, size_t b, size_t e, const sv_tape_run_args* a, hipStream_t st) {
-  if (group_sources_overlap(t, b, e)) {
-    for (size_t i = e; i-- > b;) SV_TRY(node_backward(t, i, a, st));
-    return SV_OK;
-  }
+int group_backward(sv_tape* t, size_t b, size_t e, hipStream_t st) {
   UMulti m;
   memset(&m, 0, sizeof(m));
   int64_t tot = 0;
@@ -1033,7 +1026,8 @@ hipStream_t lane_stream(sv_tape* t, int lane, hipStream_t st) {
   }
   return t->lane_st[lane];
 }
-int lanes_fork(sv_tape* t, hipStream_t st) {             // every lane behind what the caller's stream holds now
+int lanes_fork(sv_tape* t, hipStream_t st) {             // every lane behind what the caller's stream holds now (a single-lane tape: nothing)
+  if (t->nlanes < 2) return SV_OK;
   if (!t->ev_fork && hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
   if (hipEventRecord(t->ev_fork, st) != hipSuccess) return (int)hipGetLastError();
   for (int l = 1; l < t->nlanes; ++l) {
@@ -1051,14 +1045,26 @@ int lanes_join(sv_tape* t, hipStream_t st) {             // the caller's stream 
   }
   return SV_OK;
 }
-int lane_waits(sv_tape* t, const std::vector<int>& w, hipStream_t s) {
-  for (int nd : w)
-    if (t->ev_node[nd] && hipStreamWaitEvent(s, t->ev_node[nd], 0) != hipSuccess) return (int)hipGetLastError();
-  return SV_OK;
-}
-int lane_record(sv_tape* t, int nd, hipStream_t s) {
-  if (!t->ev_node[nd] && hipEventCreateWithFlags(&t->ev_node[nd], hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
-  return hipEventRecord(t->ev_node[nd], s) == hipSuccess ? SV_OK : (int)hipGetLastError();
+// One pass: the lanes fork off the caller's stream, every step waits for its events, launches and records its own, the caller's stream joins the lanes
+int run_pass(sv_tape* t, int pass, const sv_tape_run_args* a, bool with_grad, hipStream_t st) {
+  std::vector<hipEvent_t>& ev = t->ev_step[pass];
+  SV_TRY(lanes_fork(t, st));
+  for (size_t k = 0; k < t->steps[pass].size(); ++k) {
+    const sv_tape::Step& s = t->steps[pass][k];
+    hipStream_t q = lane_stream(t, s.lane, st);
+    for (int w : s.waits)
+      if (ev[w] && hipStreamWaitEvent(q, ev[w], 0) != hipSuccess) return (int)hipGetLastError();
+    const size_t b = (size_t)s.first, e = (size_t)s.last + 1;
+    if (pass == 0) SV_TRY(e - b > 1 ? group_forward(t, b, e, q) : node_forward(t, b, a, with_grad, q));
+    else if (e - b > 1 && !s.per_part) SV_TRY(group_backward(t, b, e, q));
+    else
+      for (size_t i = e; i-- > b;) SV_TRY(node_backward(t, i, a, s.part == SV_TAPE_PART_ALL ? PART_ALL : 1 << (s.part - 1), s.lane, q));
+    if (s.records) {
+      if (!ev[k] && hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
+      if (hipEventRecord(ev[k], q) != hipSuccess) return (int)hipGetLastError();
+    }
+  }
+  return lanes_join(t, st);
 }
 
 }  // namespace
@@ -1092,17 +1098,7 @@ extern "C" int sv_tape_run(sv_tape* t, const sv_tape_run_args* a, void* stream) 
       hipLaunchKernelGGL(multi_zero_kernel, dim3(nblk(tot)), dim3(256), 0, st, z);
       SV_LAUNCH_CHECK();
     }
-    const bool lanes = t->nlanes > 1;
-    if (lanes) SV_TRY(lanes_fork(t, st));
-    for (size_t i = 0; i < t->nodes.size(); ++i) {
-      const size_t e = group_end(t, i);
-      hipStream_t s = lanes ? lane_stream(t, t->nodes[i].lane, st) : st;
-      if (lanes) SV_TRY(lane_waits(t, t->fs.waits[i], s));
-      if (e > i + 1) { SV_TRY(group_forward(t, i, e, s)); i = e - 1; }
-      else SV_TRY(node_forward(t, i, a, bwd, s));
-      if (lanes && t->fs.rec[i]) SV_TRY(lane_record(t, (int)i, s));          // (i = the unit's last node by now)
-    }
-    if (lanes) SV_TRY(lanes_join(t, st));
+    SV_TRY(run_pass(t, 0, a, bwd, st));
     if (t->n_loss) {
       FinalArgs f;
       memset(&f, 0, sizeof(f));
@@ -1113,19 +1109,7 @@ extern "C" int sv_tape_run(sv_tape* t, const sv_tape_run_args* a, void* stream) 
       SV_LAUNCH_CHECK();
     }
   }
-  if (bwd) {
-    const bool lanes = t->nlanes > 1;
-    if (lanes) SV_TRY(lanes_fork(t, st));
-    for (size_t i = t->nodes.size(); i-- > 0;) {
-      const size_t b = group_begin(t, i);
-      hipStream_t s = lanes ? lane_stream(t, t->nodes[i].lane, st) : st;
-      if (lanes) SV_TRY(lane_waits(t, t->bs.waits[i], s));
-      if (b < i) { SV_TRY(group_backward(t, b, i + 1, a, s)); i = b; }
-      else SV_TRY(node_backward(t, i, a, s));
-      if (lanes && t->bs.rec[i]) SV_TRY(lane_record(t, (int)i, s));          // (i = the unit's first node by now)
-    }
-    if (lanes) SV_TRY(lanes_join(t, st));
-  }
+  if (bwd) SV_TRY(run_pass(t, 1, a, true, st));
   if (adam) {
     if (a->clipnorm > 0.f) {
       if (!a->tensor_off || !a->norm_ws || a->n_tensors < 1) return SV_E_BADARG;

@@ -399,11 +399,14 @@ class Device:
         except Exception:
             pass
 
-    def schedule(self, p, node):
-        w, rec = (C.c_int32 * 64)(), C.c_int32()
-        k = self.lib.sv_tape_schedule(self.h, p, node, w, 64, C.byref(rec))
-        assert 0 <= k <= 64, k
-        return [w[i] for i in range(k)], rec.value
+    def steps(self, p):
+        """the step list of pass p (sv_tape_steps / sv_tape_step_info): [(first, last, part, lane, records, [waits])]"""
+        out = []
+        for k in range(self.lib.sv_tape_steps(self.h, p)):
+            s, w = self._lib.TapeStep(), (C.c_int32 * 64)()
+            assert self.lib.sv_tape_step_info(self.h, p, k, C.byref(s), w, 64) == 0 and 0 <= s.n_waits <= 64
+            out.append((s.first, s.last, s.part, s.lane, s.records, [w[i] for i in range(s.n_waits)]))
+        return out
 
     def bind(self):
         from split_vae_amd.ops import _p, _stream
@@ -938,6 +941,27 @@ def lanes_graph(lanes):
     g.weights = [0.7, 0.4]
     g.add(LOSS, loss_idx=0, mode=1, x=cat, xo=0, t2=cat, o2=10, R=65, n=5, lane=ln())
     g.add(LOSS, loss_idx=1, mode=2, x=chains[0], xo=0, t2=chains[0], o2=5, R=65, n=5, p0=0.3, p1=0.5, lane=ln())
+    return g
+
+
+def conv_lanes_graph(two_lanes):
+    """The conv hand-off at bf16, B = 2 on 8 x 8 x 8 maps: Dense 8 -> 8 on lane 0 (so the convs' input has a gradient), a 3 x 3 ReLU conv on lane 0 -- with lanes its
+    adjoint is the PRE / WGRAD / DGRAD triple --, a second 3 x 3 conv reading the same Dense output on lane 1 (both weight gradients then use lane 1's slab region), a
+    COPY group joining the two and one kl loss over the join.  two_lanes False: the same nodes, all on lane 0."""
+    B, H, C = 2, 8, 8
+    g = Graph(B, bf16=True)
+    x = g.tensor(B * H * H, C, C, grad=False)
+    h = g.dense(x, C)
+    ys = []
+    for lane, act in ((0, ACT_RELU), (1 if two_lanes else 0, ACT_NONE)):
+        y = g.tensor(B * H * H, C, C)
+        g.add(CONV, x=h, y=y, w_off=g.param(3, 3, C, C, scale=math.sqrt(2.0 / (9 * C))), b_off=g.param(C, scale=0.1), B=B, H=H, W=H, C=C, Cout=C, k=3, stride=1,
+              act=act, lane=lane)
+        ys.append(y)
+    cat = g.tensor(B * H * H, 2 * C, 2 * C)
+    g.unary(COPY, ys[0], cat, C, yo=0, group=1)
+    g.unary(COPY, ys[1], cat, C, yo=C, group=1)
+    g.kl(cat, C, 0.05)
     return g
 
 

@@ -249,10 +249,12 @@ def test_tape_with_conv_layers_reserves_the_weight_gradient_slabs(lib_built):
 
 
 def test_tape_lane_schedule_without_gpu(lib_built):
-    """The cross-lane dependencies sv_tape_finalize derives from the nodes' tensors (csrc/tape.hip: build_schedules), on a diamond: x -> A (lane 0) -> ya,
-    x -> B (lane 1) -> yb, C (lane 0) = concat(ya, yb) -> z, loss on z.  Forward: C waits for B (read-after-write across lanes), nothing else crosses.  Backward
-    (reverse order: loss, C, B, A): B (lane 1) waits for C's adjoint -- it wrote grad(yb) --, and A (lane 0) waits for B: both ADD into grad(x), and conflicting
-    accumulations keep the tape's order.  Pure host code: no GPU."""
+    """The step lists sv_tape_finalize builds and the cross-lane dependencies it derives from what the steps touch (csrc/tape.hip: build_steps, build_schedules), on a
+    diamond: x -> A (lane 0) -> ya, x -> B (lane 1) -> yb, C (lane 0) = concat(ya, yb) -> z, loss on z.  Forward: C waits for B (read-after-write across lanes),
+    nothing else crosses.  Backward (reverse order: loss, C, B, A): B (lane 1) waits for C's adjoint -- it wrote grad(yb) --; A is a lane-0 Dense whose input has a
+    gradient, so its weight gradient is a step on lane 1 and its input gradient a step on lane 0, which waits for B: both ADD into grad(x), and conflicting
+    accumulations keep the tape's order.  A's weight gradient reads grad(ya), last written by C on lane 0: lane 1 already waited for C (B did), so it waits for
+    nothing.  Pure host code: no GPU."""
     import ctypes as C
     from split_vae_amd import _lib
     lib = _lib.load()
@@ -265,7 +267,7 @@ def test_tape_lane_schedule_without_gpu(lib_built):
     yb = lib.sv_tape_tensor(h, 16, 8, 8, 1)
     z = lib.sv_tape_tensor(h, 16, 16, 16, 1)
 
-    def node(kind, **kw):
+    def node(tape, kind, **kw):
         n = _lib.TapeNode()
         for f in ("x", "y", "t2", "t3", "t4", "t5", "t6"):
             setattr(n, f, -1)
@@ -274,34 +276,48 @@ def test_tape_lane_schedule_without_gpu(lib_built):
         n.rep, n.kind = 1, kind
         for k, val in kw.items():
             setattr(n, k, val)
-        assert lib.sv_tape_add(h, C.byref(n)) == 0
+        assert lib.sv_tape_add(tape, C.byref(n)) == 0
 
-    node(_lib.TAPE_DENSE, x=x, y=ya, w_off=0, b_off=256, lane=0)                      # node 0: A
-    node(_lib.TAPE_DENSE, x=x, y=yb, w_off=512, b_off=768, lane=1)                    # node 1: B
-    node(_lib.TAPE_UNARY, op=_lib.TAPE_COPY, x=ya, y=z, xo=0, yo=0, n=8, group=1)     # nodes 2, 3: C = one launch (a group)
-    node(_lib.TAPE_UNARY, op=_lib.TAPE_COPY, x=yb, y=z, xo=0, yo=8, n=8, group=1)
-    node(_lib.TAPE_LOSS, loss_idx=0, mode=1, x=z, xo=0, t2=z, o2=8, R=4, n=8)         # node 4
+    node(h, _lib.TAPE_DENSE, x=x, y=ya, w_off=0, b_off=256, lane=0)                      # node 0: A
+    node(h, _lib.TAPE_DENSE, x=x, y=yb, w_off=512, b_off=768, lane=1)                    # node 1: B
+    node(h, _lib.TAPE_UNARY, op=_lib.TAPE_COPY, x=ya, y=z, xo=0, yo=0, n=8, group=1)     # nodes 2, 3: C = one launch (a group)
+    node(h, _lib.TAPE_UNARY, op=_lib.TAPE_COPY, x=yb, y=z, xo=0, yo=8, n=8, group=1)
+    node(h, _lib.TAPE_LOSS, loss_idx=0, mode=1, x=z, xo=0, t2=z, o2=8, R=4, n=8)         # node 4
     bad = _lib.TapeNode()
     bad.kind, bad.x, bad.y, bad.lane = _lib.TAPE_UNARY, z, z, 9
     assert lib.sv_tape_add(h, C.byref(bad)) == _lib.STATUS_BADARG                     # lanes 0 .. 3
-    assert lib.sv_tape_schedule(h, 0, 0, None, 0, None) == _lib.STATUS_BADARG         # not finalized
+    one = _lib.TapeStep()
+    assert lib.sv_tape_steps(h, 0) == _lib.STATUS_BADARG and lib.sv_tape_step_info(h, 0, 0, C.byref(one), None, 0) == _lib.STATUS_BADARG      # not finalized
     assert lib.sv_tape_finalize(h) == 0
 
-    def sched(p, nd):
-        w = (C.c_int32 * 8)()
-        rec = C.c_int32()
-        k = lib.sv_tape_schedule(h, p, nd, w, 8, C.byref(rec))
-        assert k >= 0
-        return sorted(w[i] for i in range(k)), rec.value
+    def steps(p):
+        out = []
+        for k in range(lib.sv_tape_steps(h, p)):
+            s, w = _lib.TapeStep(), (C.c_int32 * 8)()
+            assert lib.sv_tape_step_info(h, p, k, C.byref(s), w, 8) == 0
+            out.append((s.first, s.last, s.part, s.lane, s.records, sorted(w[i] for i in range(s.n_waits))))
+        return out
 
-    fwd = [sched(0, i) for i in range(5)]
-    bwd = [sched(1, i) for i in range(5)]
-    # forward: B waits for nothing (x is an input); the group C (waits on its first node, 2) waits for B's event; B records, nobody else
-    assert fwd[0] == ([], 0) and fwd[1] == ([], 1) and fwd[2] == ([1], 0) and fwd[3][0] == [] and fwd[4] == ([], 0), fwd
-    # backward: the group C's waits sit on its LAST node (3): none; its event behind its FIRST node (2), which B waits for; A waits for B
-    assert bwd[4] == ([], 0) and bwd[3][0] == [] and bwd[2] == ([], 1) and bwd[1] == ([2], 1) and bwd[0] == ([1], 0), bwd
-    assert lib.sv_tape_schedule(h, 2, 0, None, 0, None) == _lib.STATUS_BADARG and lib.sv_tape_schedule(h, 0, 5, None, 0, None) == _lib.STATUS_BADARG
+    ALL, WGRAD, DGRAD = _lib.TAPE_PART_ALL, _lib.TAPE_PART_WGRAD, _lib.TAPE_PART_DGRAD
+    # forward: A, B, the group C as one step, the loss.  B waits for nothing (x is an input) and records; C (step 2) waits for B's event; nobody else waits or records
+    assert steps(0) == [(0, 0, ALL, 0, 0, []), (1, 1, ALL, 1, 1, []), (2, 3, ALL, 0, 0, [1]), (4, 4, ALL, 0, 0, [])]
+    # backward: loss, C (records: B waits for it), B (records), A's weight gradient on lane 1 (lane 1 waited for C already: nothing), A's input gradient, which waits for B
+    assert steps(1) == [(4, 4, ALL, 0, 0, []), (2, 3, ALL, 0, 1, []), (1, 1, ALL, 1, 1, [1]), (0, 0, WGRAD, 1, 0, []), (0, 0, DGRAD, 0, 0, [2])]
+    assert lib.sv_tape_steps(h, 2) == _lib.STATUS_BADARG and lib.sv_tape_step_info(h, 2, 0, C.byref(one), None, 0) == _lib.STATUS_BADARG
+    assert lib.sv_tape_step_info(h, 0, 4, C.byref(one), None, 0) == _lib.STATUS_BADARG and lib.sv_tape_step_info(h, 1, 5, C.byref(one), None, 0) == _lib.STATUS_BADARG
+    assert lib.sv_tape_step_info(h, 0, -1, C.byref(one), None, 0) == _lib.STATUS_BADARG
     lib.sv_tape_destroy(h)
+    # every variable has one writer: a second layer on the same weights (or the same bias) is refused at finalize
+    for second in (dict(w_off=0, b_off=768), dict(w_off=512, b_off=256)):
+        h = C.c_void_p()
+        assert lib.sv_tape_create(C.byref(h), 4, _lib.SV_F32) == 0
+        x = lib.sv_tape_tensor(h, 16, 32, 32, 0)
+        ya = lib.sv_tape_tensor(h, 16, 8, 8, 1)
+        yb = lib.sv_tape_tensor(h, 16, 8, 8, 1)
+        node(h, _lib.TAPE_DENSE, x=x, y=ya, w_off=0, b_off=256)
+        node(h, _lib.TAPE_DENSE, x=x, y=yb, **second)
+        assert lib.sv_tape_finalize(h) == _lib.STATUS_UNSUPPORTED
+        lib.sv_tape_destroy(h)
 
 
 def _conv_domain_rule(B, H, W, Cin, Cout, KH, KW, s, dtype, ldx, ldy, y_f32, ups):

@@ -177,6 +177,31 @@ def test_lanes_compute_the_single_stream_tape_bit_for_bit(lib_built):
         assert not bad, ("lane assignment %d changes buffers" % seed, bad)
 
 
+def test_conv_hand_off_computes_the_single_stream_tape_bit_for_bit(lib_built, deterministic):
+    """The one PRE / WGRAD / DGRAD triple (T.conv_lanes_graph: a bf16 tape whose lane-0 ReLU conv hands its weight gradient to lane 1, where a second conv's weight
+    gradient uses the same slab region), under fixed-order reductions.  The all-lane-0 recording is bit-identical over two runs; the two-lane recording equals it
+    bit for bit in activations, gradient region, variable gradients and loss block."""
+    g0 = T.conv_lanes_graph(False)
+    ins, p = g0.make_inputs(4)
+    d0 = T.Device(g0)
+    assert [s[2] for s in d0.steps(1)] == [0] * 5                            # (loss, group, conv, conv, dense: whole adjoints)
+    assert d0.run(ins, p) == 0
+    a = _snapshot(g0, d0)
+    assert d0.run(g0.make_inputs(5)[0], p) == 0                             # (other inputs in between)
+    assert d0.run(ins, p) == 0
+    b = _snapshot(g0, d0)
+    assert all(torch.equal(x, y) for x, y in zip(a, b)), "the single-lane tape is not run-to-run identical"
+    assert float(a[-2].abs().sum()) > 0
+    g1 = T.conv_lanes_graph(True)
+    d1 = T.Device(g1)
+    assert [s[2:4] for s in d1.steps(1)][2:6] == [(0, 1), (1, 0), (2, 1), (3, 0)]      # conv on lane 1, then PRE / WGRAD (lane 1) / DGRAD of the lane-0 conv
+    assert d1.run(g1.make_inputs(5)[0], p) == 0
+    assert d1.run(ins, p) == 0
+    c = _snapshot(g1, d1)
+    bad = [k for k, (x, y) in enumerate(zip(a, c)) if not torch.equal(x, y)]
+    assert not bad, ("the two-lane recording changes buffers", bad)
+
+
 # ------------------------------------------------------------------------------------------------------------------- NOISE
 def _noise_graph():
     g = T.Graph(2)

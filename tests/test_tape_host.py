@@ -101,30 +101,59 @@ def _units(g, lanes):
     return u
 
 
-def _access(g, n, backward):
-    """(reads, writes) of one node as resources ('A' | 'G', root tensor) / ('W', offset), from the documented semantics of the node kinds: the forward pass reads
-    input activations and writes outputs, LOSS / ZPRES add into their operands' gradients; the adjoint read-modify-writes the gradients it adds into, reads its
-    output's gradient and writes its variables' gradients.  Activations are only read backwards: never a conflict, left out."""
-    tens = g.tens
+ALL, PRE, WGRAD, DGRAD = range(4)
+
+
+def _expected_steps(g, lanes, backward):
+    """The step list (first, last, part, lane) as include/splitvae.h words it: forward, every unit is one ALL step on its lane.  Backward, the units in reverse; on a tape
+    with more than one lane a lane-0 DENSE node (or a CONV node of a bf16 tape) whose input has a gradient is PRE on lane 0 (CONV only), WGRAD on lane 1, DGRAD on lane 0."""
+    units = _units(g, lanes)
+    if not backward:
+        return [(a, b, ALL, lanes[a]) for a, b in units]
+    out = []
+    for a, b in reversed(units):
+        n = g.nodes[a]
+        layer = n["kind"] == T.DENSE or (n["kind"] == T.CONV and g.bf16)
+        if not (layer and max(lanes) > 0 and lanes[a] == 0 and g.tens[n["x"]]["grad"]):
+            out.append((a, b, ALL, lanes[a]))
+            continue
+        out += [(a, b, PRE, 0)] * (n["kind"] == T.CONV) + [(a, b, WGRAD, 1), (a, b, DGRAD, 0)]
+    return out
+
+
+def _access(g, i, part, lane, backward):
+    """(reads, writes) of one node's part as resources ('A' | 'G', root tensor) / ('W', offset) / ('dY', node) / ('slab', lane), from the documented semantics of the
+    node kinds: the forward pass reads input activations and writes outputs, LOSS / ZPRES add into their operands' gradients; the adjoint read-modify-writes the
+    gradients it adds into, reads its output's gradient and writes its variables' gradients.  Of a DENSE / CONV adjoint, PRE gates G(y) in place and writes the bf16
+    copy of dY, WGRAD reads both and writes the variables' gradients (CONV: through its lane's slab region), DGRAD reads both and adds into G(x); ALL is the three
+    together.  Activations are only read backwards: never a conflict, left out."""
+    tens, n = g.tens, g.nodes[i]
     A = lambda t: ("A", tens[t]["root"])
     G = lambda t: ("G", tens[t]["root"])
     hasg = lambda t: t >= 0 and tens[t]["grad"]
     k = n["kind"]
     rd, wr = set(), set()
     if not backward:
-        ins = {T.DENSE: ["x"], T.UNARY: ["x"], T.SAMPLE: ["x", "t2", "t3"], T.LOSS: ["x", "t2"], T.NOISE: []}[k]
+        ins = {T.DENSE: ["x"], T.CONV: ["x"], T.UNARY: ["x"], T.SAMPLE: ["x", "t2", "t3"], T.LOSS: ["x", "t2"], T.NOISE: []}[k]
         rd |= {A(n[f]) for f in ins}
-        if k in (T.DENSE, T.UNARY, T.SAMPLE, T.NOISE):
+        if k in (T.DENSE, T.CONV, T.UNARY, T.SAMPLE, T.NOISE):
             wr.add(A(n["y"]))
         if k == T.LOSS:
             wr |= {G(n[f]) for f in (["t2"] if n["mode"] == 0 else ["x", "t2"]) if hasg(n[f])}
         return rd, wr
     if k in (T.LOSS, T.NOISE) or not hasg(n["y"]):
         return rd, wr
-    if k == T.DENSE:
-        rd.add(G(n["y"]))
-        wr.add(("W", n["w_off"]))
-        if hasg(n["x"]):
+    if k in (T.DENSE, T.CONV):
+        dy = {G(n["y"])} | ({("dY", i)} if k == T.CONV and g.bf16 else set())
+        if part in (ALL, PRE):
+            wr |= dy
+        else:
+            rd |= dy
+        if part in (ALL, WGRAD):
+            wr.add(("W", n["w_off"]))
+            if k == T.CONV:
+                wr.add(("slab", lane))
+        if part in (ALL, DGRAD) and hasg(n["x"]):
             wr.add(G(n["x"]))
     elif k == T.UNARY:
         if hasg(n["x"]):
@@ -136,62 +165,96 @@ def _access(g, n, backward):
     return rd, wr
 
 
+def _check_schedule(g, lanes, tag):
+    """One tape: the library's step lists are the expected ones, waits point at earlier steps that record, and every pair of conflicting steps on different lanes has a
+    happens-before path (wait edges plus same-lane issue order).  -> (cross-lane conflicts, those with a WGRAD step on one side)"""
+    dev = T.Device(g, bind=False)
+    crossed = with_wgrad = 0
+    for p in (0, 1):
+        steps = dev.steps(p)
+        assert [s[:4] for s in steps] == _expected_steps(g, lanes, p == 1), (tag, p)
+        before = []                                                      # step -> bit set of the steps that happen before it
+        last_on_lane = {}
+        acc = []
+        for u, (a, b, part, ln, _, waits) in enumerate(steps):
+            hb = 0
+            if ln in last_on_lane:
+                q = last_on_lane[ln]
+                hb |= before[q] | (1 << q)
+            for d in waits:
+                assert 0 <= d < u, (tag, p, u, d, "waits for a step that is issued later")
+                assert steps[d][4] == 1, (tag, p, d, "waited for, but no event is recorded behind it")
+                hb |= before[d] | (1 << d)
+            before.append(hb)
+            last_on_lane[ln] = u
+            rd, wr = set(), set()
+            for i in range(a, b + 1):
+                r_, w_ = _access(g, i, part, ln, p == 1)
+                rd |= r_
+                wr |= w_
+            acc.append((rd, wr))
+            for q in range(u):
+                if steps[q][3] == ln:
+                    continue
+                qr, qw = acc[q]
+                if (wr & (qr | qw)) or (rd & qw):
+                    crossed += 1
+                    with_wgrad += WGRAD in (part, steps[q][2])
+                    assert (hb >> q) & 1, (tag, "backward" if p else "forward", "step", steps[u][:4], "is not ordered behind", steps[q][:4],
+                                           sorted((wr & (qr | qw)) | (rd & qw)))
+    return crossed, with_wgrad
+
+
 @pytest.mark.parametrize("block", range(8))
 def test_lane_schedule_orders_every_conflict(lib_built, block):
-    """200 seeded random tapes (25 per block).  For every pair of launches on different lanes that touch one resource, one of them writing, the reported wait edges
-    plus same-lane launch order must contain a happens-before path from the earlier to the later -- in both passes.  An event is recorded behind every node that is
-    waited for, waits sit on a launch's first node forwards / last backwards, and point at a launch that was issued earlier."""
+    """200 seeded random tapes (25 per block), each as recorded and with its lanes folded onto lanes 0 / 1 by the recording (the cap's own fold included).  The
+    library's step lists equal the ones include/splitvae.h's wording gives -- the weight gradients handed to lane 1 are steps of their own --, and for every pair of
+    steps on different lanes that touch one resource, one of them writing, the reported wait edges plus same-lane issue order contain a happens-before path from the
+    earlier to the later, in both passes.  An event is recorded behind every step that is waited for, and waits point at steps issued earlier.
+    Measured on the CPU (default cap 1): 4828 cross-lane conflicts over the 8 blocks, 85 of them with a WGRAD step (8 to 16 per block)."""
     if os.environ.get("SV_TAPE_LANES") == "0":
         pytest.skip("lanes are switched off in this environment")
     cap = int(os.environ.get("SV_TAPE_LANES", "1"))
-    crossed = 0
+    crossed = with_wgrad = 0
     for seed in range(block * 25, block * 25 + 25):
         g = _random_tape(seed)
-        dev = T.Device(g, bind=False)
-        lanes = [min(n["lane"], cap) for n in g.nodes]                      # lanes above the cap fold onto it
-        units = _units(g, lanes)
-        unit_of = {i: u for u, (a, b) in enumerate(units) for i in range(a, b + 1)}
-        for p in (0, 1):
-            order = list(range(len(units))) if p == 0 else list(range(len(units) - 1, -1, -1))
-            pos = {u: k for k, u in enumerate(order)}
-            sched = [dev.schedule(p, i) for i in range(len(g.nodes))]
-            before = {}                                                      # unit -> bit set of the units that happen before it
-            last_on_lane = {}
-            acc = {}
-            for u in order:
-                a, b = units[u]
-                wait_node, ev_node = (a, b) if p == 0 else (b, a)
-                for i in range(a, b + 1):
-                    if i != wait_node:
-                        assert sched[i][0] == [], (seed, p, i, "waits off the launch's first issued node")
-                hb = 0
-                ln = lanes[a]
-                if ln in last_on_lane:
-                    q = last_on_lane[ln]
-                    hb |= before[q] | (1 << q)
-                for d in sched[wait_node][0]:
-                    assert sched[d][1] == 1, (seed, p, d, "waited for, but no event is recorded behind it")
-                    q = unit_of[d]
-                    assert pos[q] < pos[u], (seed, p, wait_node, d, "waits for a launch that is issued later")
-                    assert d == (units[q][1] if p == 0 else units[q][0]), (seed, p, d, "the event is not behind the launch's last issued node")
-                    hb |= before[q] | (1 << q)
-                before[u] = hb
-                last_on_lane[ln] = u
-                rd, wr = set(), set()
-                for i in range(a, b + 1):
-                    r_, w_ = _access(g, g.nodes[i], p == 1)
-                    rd |= r_
-                    wr |= w_
-                acc[u] = (rd, wr)
-                for q in order[:pos[u]]:
-                    if lanes[units[q][0]] == ln:
-                        continue
-                    qr, qw = acc[q]
-                    if (wr & (qr | qw)) or (rd & qw):
-                        crossed += 1
-                        assert (hb >> q) & 1, (seed, "backward" if p else "forward", "launch of nodes", units[u], "is not ordered behind", units[q],
-                                               sorted((wr & (qr | qw)) | (rd & qw)))
+        c, w = _check_schedule(g, [min(n["lane"], cap) for n in g.nodes], seed)          # lanes above the cap fold onto it
+        crossed, with_wgrad = crossed + c, with_wgrad + w
+        for n in g.nodes:                                                                  # kind "lanes folded by the cap": recorded 0 / 3, run as 0 / cap
+            n["lane"] = 3 if n["lane"] >= 2 else 0
+        c, w = _check_schedule(g, [min(n["lane"], cap) for n in g.nodes], (seed, "folded"))
+        crossed, with_wgrad = crossed + c, with_wgrad + w
+    print("cross-lane conflicts %d, with a WGRAD step %d" % (crossed, with_wgrad))
     assert crossed > 50, crossed                                             # the tapes do produce cross-lane conflicts
+    assert with_wgrad > 0, with_wgrad                                        # ... and the handed-off weight gradients are among them
+
+
+@pytest.mark.parametrize("name", sorted(T.CASES))
+def test_single_lane_tape_has_plain_steps(lib_built, name):
+    """Every graph of tests/test_gpu_tape.py, recorded on lane 0 alone: both passes report the units as SV_TAPE_PART_ALL steps on lane 0, with no waits and no
+    records (a single-lane run records no event at all), the backward list being the forward one reversed."""
+    g = T.CASES[name]()
+    for n in g.nodes:
+        n["lane"] = 0
+    dev = T.Device(g, bind=False)
+    fwd, bwd = dev.steps(0), dev.steps(1)
+    assert fwd == [(a, b, ALL, 0, 0, []) for a, b in _units(g, [0] * len(g.nodes))]
+    assert bwd == fwd[::-1]
+
+
+def test_side_stream_failure_leaves_a_null_stream(lib_built):
+    """sv_side_stream: an index outside 0 .. 2 is SV_E_BADARG with *stream NULL; index 0 gives either status 0 and a stream (a GPU) or a non-zero status and NULL
+    (no GPU) -- never status 0 with the pointer left as it was."""
+    import ctypes as C
+    from split_vae_amd import _lib
+    lib = _lib.load()
+    for index in (-1, 3):
+        h = C.c_void_p(0xdead)
+        assert lib.sv_side_stream(index, C.byref(h)) == _lib.STATUS_BADARG and not h.value
+    h = C.c_void_p(0xdead)
+    rc = lib.sv_side_stream(0, C.byref(h))
+    assert (rc == 0 and h.value not in (None, 0xdead)) or (rc != 0 and not h.value), (rc, h.value)
+    assert lib.sv_side_stream(0, None) == _lib.STATUS_BADARG
 
 
 # ------------------------------------------------------------------------------------------------------------------- the twin against the oracle
