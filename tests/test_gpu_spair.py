@@ -3,12 +3,17 @@
 on the MFMA im2col kernels (divide-based row decode), at the reference's shape [32, 48, 48, 3] (batch 32 is hard-coded,
 spair/trainer.py:346), against the fp64 oracle restatement: forward chain, and per layer the input and weight gradients."""
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import spair_ref, torch_ref
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import spair_glue_ref as G  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 B = 32
@@ -89,108 +94,115 @@ def test_unsupported_geometries_are_refused(ops):
 
 
 # ------------------------------------------------------------------ spatial transformer (spair/utils.py:119-330)
-STN_CASES = [  # name, inverse, image extent, channels, output extent
-    ("glimpses", False, 48, 3, 32),      # STN(H_img=32...) on the [32,48,48,3] canvas: one 32x32 glimpse per cell
-    ("render", True, 32, 4, 48),         # the renderer's inverse STN: each object's rgb+alpha pasted on a 48x48 canvas
+# The STN, renderer, z_pres KL and loss kernels are compared element by element through their entry points in tests/test_gpu_spair_glue.py; the tests
+# below run the workload's own shapes through the `ops` wrappers and are judged by the same comparison (spair_glue_ref.judge: every element within the
+# bound derived from the kernel's arithmetic).
+STN_CASES = [  # name, the case of spair_glue_ref's table
+    ("glimpses", "workload_glimpse"),    # STN(H_img=32...) on the [.,48,48,3] canvas: one 32x32 glimpse per cell
+    ("render", "workload_render"),       # the renderer's inverse STN: each object's rgb+alpha pasted on a 48x48 canvas
 ]
+# What these tests asserted before the per-element bounds existed stays asserted next to them: a worst-case bound summed over a glimpse's pixels (g_img: hundreds
+# of atomic adds per image pixel) is wider in the norm than the device's error, which these hold.  out: largest absolute error and error norm / reference
+# norm; g_img, g_z_where: error norm / reference norm.
+STN_NORMWISE = {"glimpses": dict(atol=2e-5, out=1e-5, g_img=1e-5, g_z=1e-3), "render": dict(atol=2e-3, out=2e-4, g_img=1e-3, g_z=2e-2)}
 
 
-def _stn_inputs(inverse, Hi, C, seed):
-    rng = np.random.default_rng(seed)
-    Bs, Hc = 5, 4
-    shape = (Bs, Hc * Hc, Hi, Hi, C) if inverse else (Bs, Hi, Hi, C)
-    img = torch.from_numpy(rng.uniform(0, 1, shape).astype(np.float32))
-    z = torch.from_numpy((rng.standard_normal((Bs, Hc, Hc, 4)) * 1.5).astype(np.float32))
-    return img, z
+def _rel_norm(got, ref):
+    ref = torch.as_tensor(ref, dtype=torch.float64).reshape(got.shape)
+    return float((got.double().cpu() - ref).norm() / ref.norm())
+
+
+def _within(what, got, ref):
+    ref = ref if isinstance(ref, tuple) else G.exact(ref)
+    r, i = G.judge(got.detach().double().cpu().numpy(), ref)
+    print("%-28s worst error / bound %.4g" % (what, r))
+    assert r <= 1.0, (what, r, "flat index %d" % i)
+
+
+def _stn_case(table_id):
+    return next(c for c in G.stn_cases() if c[0][0] == table_id and c[2] == "normal")
 
 
 @pytest.mark.parametrize("case", STN_CASES, ids=lambda c: c[0])
 def test_stn_forward_matches_oracle(ops, case):
-    """Affine grid + 4-tap gather + obj_bbox_mask against the restatement, both STN directions.  fp32 on the device vs fp64:
-    the output is continuous in the sampling point, so a floor() that lands on the other side of an integer in fp32 moves the
-    value by O(eps) only."""
-    name, inverse, Hi, C, Ho = case
-    img, z = _stn_inputs(inverse, Hi, C, 1)
-    out, bbox = ops.stn_sample(img.cuda(), z.cuda(), Ho, Ho, inverse=inverse)
-    ref, rbox = spair_ref.stn_forward(img.double(), z.double(), Ho, Ho, inverse=inverse)
-    assert tuple(out.shape) == tuple(ref.shape)
-    # inverse form: sampling coordinates are scaled by 1/sx (up to ~1e5 when a cell's box collapses): fp32 coordinate error
-    torch.testing.assert_close(out.double().cpu(), ref, rtol=0, atol=2e-3 if inverse else 2e-5)
-    assert float((out.double().cpu() - ref).norm() / ref.norm()) < (2e-4 if inverse else 1e-5)
-    torch.testing.assert_close(bbox.double().cpu(), rbox, rtol=1e-6, atol=1e-6)
+    """Affine grid + 4-tap gather + obj_bbox_mask against the float64 restatement, both STN directions, per element."""
+    c = _stn_case(case[1])
+    img, z, g, res = G.stn_reference(c)
+    Ho, Wo = c[0][6], c[0][7]
+    out, bbox = ops.stn_sample(_dev(img), _dev(z), Ho, Wo, inverse=c[1])
+    assert tuple(out.shape) == tuple(res["out"][0].shape)
+    _within(case[0] + " out", out, res["out"])
+    _within(case[0] + " bbox", bbox, res["bbox"])
+    ref, rbox = torch.from_numpy(res["out"][0]), torch.from_numpy(res["bbox"][0])       # the random family has no fold: one reference value per element
+    torch.testing.assert_close(out.double().cpu(), ref, rtol=0, atol=STN_NORMWISE[case[0]]["atol"])
+    assert _rel_norm(out, ref) < STN_NORMWISE[case[0]]["out"]
+    torch.testing.assert_close(bbox.double().cpu(), rbox.reshape(bbox.shape), rtol=1e-6, atol=1e-6)
 
 
 @pytest.mark.parametrize("case", STN_CASES, ids=lambda c: c[0])
 def test_stn_backward_matches_autograd_of_the_oracle(ops, case):
-    """g_img (scatter of the four tap weights) and g_z_where (through the tap weights; floor / clip carry none) against
-    torch autograd of the fp64 restatement."""
-    name, inverse, Hi, C, Ho = case
-    img, z = _stn_inputs(inverse, Hi, C, 2)
-    if inverse:
-        z = z * 0.5                                       # keep 1/sx moderate: the comparison is about the chain rule
-    rng = np.random.default_rng(3)
-    g = torch.from_numpy(rng.standard_normal((img.shape[0], 16, Ho, Ho, C)).astype(np.float32))
-    ri, rz = img.double().requires_grad_(True), z.double().requires_grad_(True)
-    ref, _ = spair_ref.stn_forward(ri, rz, Ho, Ho, inverse=inverse)
-    (ref * g.double()).sum().backward()
-    g_img, g_z = ops.stn_sample_bwd(img.cuda(), z.cuda(), g.cuda(), inverse=inverse)
-    ei = float((g_img.double().cpu() - ri.grad).norm() / ri.grad.norm())
-    ez = float((g_z.double().cpu() - rz.grad).norm() / rz.grad.norm())
-    assert ei < (1e-3 if inverse else 1e-5), ei
-    assert ez < (2e-2 if inverse else 1e-3), ez          # a sampling point within fp32 eps of an integer takes the other cell's slope
-    # run-to-run: g_z_where is reduced in a fixed order
-    _, g_z2 = ops.stn_sample_bwd(img.cuda(), z.cuda(), g.cuda(), inverse=inverse)
-    assert torch.equal(g_z, g_z2)
+    """g_img (scatter of the four tap weights) and g_z_where (through the tap weights; floor / clip carry none) against the analytic float64
+    backward (itself held to torch autograd of the oracle in tests/test_spair_glue_host.py), per element."""
+    c = _stn_case(case[1])
+    img, z, g, res = G.stn_reference(c)
+    g_img, g_z = ops.stn_sample_bwd(_dev(img), _dev(z), _dev(g), inverse=c[1])
+    _within(case[0] + " g_img", g_img, res["g_img"])
+    _within(case[0] + " g_z_where", g_z, res["g_z"])
+    ei, ez = _rel_norm(g_img, res["g_img"][0]), _rel_norm(g_z, res["g_z"][0])
+    print("%s: error norm / reference norm g_img %.3g g_z_where %.3g" % (case[0], ei, ez))
+    assert ei < STN_NORMWISE[case[0]]["g_img"], ei
+    assert ez < STN_NORMWISE[case[0]]["g_z"], ez
+    # run-to-run: g_z_where is reduced in a fixed order; and the same without g_img
+    assert torch.equal(g_z, ops.stn_sample_bwd(_dev(img), _dev(z), _dev(g), inverse=c[1])[1])
+    none, g_z3 = ops.stn_sample_bwd(_dev(img), _dev(z), _dev(g), inverse=c[1], need_img=False)
+    assert none is None and torch.equal(g_z, g_z3)
 
 
 # ------------------------------------------------------------------ Renderer (spair/spair.py:534-579)
-def _render_inputs(seed, Bs=6, Bp=16, H=48, C=3):
-    rng = np.random.default_rng(seed)
-    t = lambda a: torch.from_numpy(a.astype(np.float32))
-    obj = t(rng.uniform(-0.2, 1.2, (Bs, Bp, H, H, C + 1)))          # rgb and alpha partly outside their clip ranges
-    bg = t(rng.uniform(0, 1, (Bs, H, H, C)))
-    zd = t(rng.standard_normal((Bs, 4, 4, 1)) * 2)
-    zp = t(rng.uniform(0.01, 0.99, (Bs, 4, 4, 1)))
-    zl = t(rng.standard_normal((Bs, 4, 4, 1)) * 3)
-    noise = t(rng.standard_normal((Bs, Bp, H, H, C)) * 0.01)
-    return obj, bg, zd, zp, zl, noise
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).cuda()
+
+
+RENDER_SHAPE = next(s for s in G.RENDER_SHAPES if s[0] == "workload")
 
 
 @pytest.mark.parametrize("mode", ["train", "train_noise", "test"])
 def test_renderer_forward_matches_oracle(ops, mode):
-    obj, bg, zd, zp, zl, noise = _render_inputs(4)
+    d, refs = G.render_reference(RENDER_SHAPE, mode)
     training = mode != "test"
-    nz = noise if mode == "train_noise" else None
-    out = ops.spair_render(obj.cuda(), bg.cuda(), zd.cuda(), z_pres=zp.cuda() if training else None,
-                           z_pres_logits=None if training else zl.cuda(), training=training, noise=None if nz is None else nz.cuda())
-    ref = spair_ref.renderer(obj.double(), bg.double(), zd.double(), zp.double(), zl.double(), training=training,
-                             noise=None if nz is None else nz.double())
-    torch.testing.assert_close(out.double().cpu(), ref, rtol=1e-4, atol=1e-5)
+    B, Bp = d["zd"].shape
+    z4 = lambda a: _dev(a).reshape(B, 4, 4, 1)
+    out = ops.spair_render(_dev(d["obj"]), _dev(d["bg"]), z4(d["zd"]), z_pres=z4(d["zp"]) if training else None,
+                           z_pres_logits=None if training else z4(d["zl"]), training=training, noise=None if d["noise"] is None else _dev(d["noise"]))
+    got = out.double().cpu().numpy()
+    for b in range(B):                                     # test time: a logit of +-1e-7 may round either way, per image (spair_glue_ref.render_scalars)
+        rs = [G.judge(got[b], tuple(t[b] for t in G.exact(r["out"])))[0] for r in refs]
+        print("renderer %s image %d: worst error / bound %s" % (mode, b, ["%.4g" % v for v in rs]))
+        assert min(rs) <= 1.0, (b, rs)
 
 
 @pytest.mark.parametrize("with_noise", [False, True])
 def test_renderer_backward_matches_autograd_of_the_oracle(ops, with_noise):
-    obj, bg, zd, zp, zl, noise = _render_inputs(5)
-    nz = noise if with_noise else None
-    rng = np.random.default_rng(6)
-    g = torch.from_numpy(rng.standard_normal(tuple(bg.shape)).astype(np.float32))
-    r = [t.double().requires_grad_(True) for t in (obj, bg, zd, zp)]
-    ref = spair_ref.renderer(r[0], r[1], r[2], r[3], zl.double(), training=True, noise=None if nz is None else nz.double())
-    (ref * g.double()).sum().backward()
-    got = ops.spair_render_bwd(obj.cuda(), bg.cuda(), zd.cuda(), zp.cuda(), g.cuda(), noise=None if nz is None else nz.cuda())
-    want = (r[0].grad, r[1].grad, r[3].grad.reshape(-1, 16), r[2].grad.reshape(-1, 16))
-    for name, a, b in zip(("g_obj", "g_bg", "g_z_pres", "g_z_depth"), got, want):
-        err = float((a.double().cpu() - b).norm() / b.norm())
+    d, refs = G.render_reference(RENDER_SHAPE, "train_noise" if with_noise else "train")
+    B, Bp = d["zd"].shape
+    z4 = lambda a: _dev(a).reshape(B, 4, 4, 1)
+    args = (_dev(d["obj"]), _dev(d["bg"]), z4(d["zd"]), z4(d["zp"]), _dev(d["g"]))
+    nz = None if d["noise"] is None else _dev(d["noise"])
+    got = ops.spair_render_bwd(*args, noise=nz)
+    for name, a in zip(("g_obj", "g_bg", "g_zp", "g_zd"), got):
+        _within(name, a, refs[0][name])
+        err = _rel_norm(a, refs[0][name].v)                # the z gradients sum 2304 signed pixel terms: their worst-case bound is wider than this in the norm
+        print("%-28s error norm / reference norm %.3g" % (name, err))
         assert err < 1e-4, (name, err)
-    again = ops.spair_render_bwd(obj.cuda(), bg.cuda(), zd.cuda(), zp.cuda(), g.cuda(), noise=None if nz is None else nz.cuda())
+    again = ops.spair_render_bwd(*args, noise=nz)
     assert all(torch.equal(a, b) for a, b in zip(got, again))      # fixed-order reductions: run-to-run identical
 
 
 # ------------------------------------------------------------------ z_pres KL and clipnorm Adam
 @pytest.mark.parametrize("prior_prob,temp", [(0.1, 1.0), (0.5, 2.5), (0.01, 0.5)])
 def test_zpres_kl_and_its_gradient(ops, prior_prob, temp):
-    """compute_z_pres_kl_yolo_air (spair/trainer.py:45-94) on the device: per-image sums against the fp64 restatement, the
-    gradients against its autograd (the count prior sees thresholded samples only: no gradient to z_pres)."""
+    """compute_z_pres_kl_yolo_air (spair/trainer.py:45-94) on the device: per-image sums and the gradients, per element, against the float64
+    restatement (the count prior sees thresholded samples only: no gradient to z_pres)."""
     rng = np.random.default_rng(int(prior_prob * 1000))
     Bs = 32
     pre = torch.from_numpy(rng.standard_normal((Bs, 4, 4, 1)).astype(np.float32) * 2)
@@ -198,10 +210,18 @@ def test_zpres_kl_and_its_gradient(ops, prior_prob, temp):
     zp = torch.sigmoid(pre)
     zp[0] = 0.9; zp[1] = 0.1                               # all on / all off: the count recursion's extremes
     kl, g_pre, g_log = ops.spair_zpres_kl(zp.cuda(), logits.cuda(), pre.cuda(), prior_prob, temp)
+    ref = G.zpres_kl(zp.double().numpy().reshape(Bs, 16), logits.double().numpy().reshape(Bs, 16), pre.double().numpy().reshape(Bs, 16),
+                     prior_prob, temp, 1.0 / Bs)
+    _within("kl per image", kl, ref["kl"])
+    _within("g_pre", g_pre, ref["g_pre"])
+    _within("g_logits", g_log, ref["g_logits"])
+    # the batch mean and the gradients against the oracle and its autograd, as tightly as before the per-element bounds (whose worst case through
+    # safe_log(pz) - safe_log(1 - pz) is wider than the device's error)
     rp, rl = pre.double().requires_grad_(True), logits.double().requires_grad_(True)
-    ref = spair_ref.compute_z_pres_kl_yolo_air(zp.double(), rl, rp, prior_prob, temp)
-    ref.backward()
-    assert abs(float(kl.double().mean()) - float(ref)) <= 1e-5 * abs(float(ref)) + 1e-5
+    want = spair_ref.compute_z_pres_kl_yolo_air(zp.double(), rl, rp, prior_prob, temp)
+    want.backward()
+    want = want.detach()
+    assert abs(float(kl.double().mean()) - float(want)) <= 1e-5 * abs(float(want)) + 1e-5
     torch.testing.assert_close(g_pre.double().cpu(), rp.grad, rtol=1e-4, atol=1e-7)
     torch.testing.assert_close(g_log.double().cpu(), rl.grad, rtol=1e-4, atol=1e-7)
 
@@ -285,19 +305,27 @@ def test_loss_reductions_and_their_gradients(ops, mode):
     else:
         a = torch.randn(B, *shape, generator=g)
         b = torch.nn.functional.softplus(torch.randn(B, *shape, generator=g) - 1.0)
-        pm, ps = 3.7, 0.5
+        pm, ps = float(np.float32(3.7)), 0.5                  # as the call rounds it
         f = lambda x, y: (spair_ref.tf_safe_log(torch.full_like(y, ps)) - spair_ref.tf_safe_log(y) + (y * y + (x - pm) ** 2) / (2 * ps * ps) - 0.5)
     ar, br = a.double().requires_grad_(True), b.double().requires_grad_(True)
     t = f(ar, br).reshape(B, -1).sum(dim=1)
     w = torch.rand(B, generator=g).double()
+    wv = w.view(B, 1, 1, 1)
     (t * w).sum().backward()
     sums, ga, gb = ops.spair_loss(mode, a.cuda(), b.cuda(), *((pm, ps) if mode == "kl_prior" else ()))
+    n = a[0].numel()
+    ref = G.loss(G.LOSS_MODES[mode], a.double().numpy().reshape(B, n), b.double().numpy().reshape(B, n), *((pm, ps) if mode == "kl_prior" else ()))
+    # the restatement the bounds belong to is the oracle's formula
+    assert float((torch.from_numpy(ref["sums"][0]) - t.detach()).abs().max()) <= 1e-12 * float(t.detach().abs().max())
+    assert float((torch.from_numpy(ref["gb"].v).reshape(b.shape) * wv - br.grad).abs().max()) <= 1e-12 * float(br.grad.abs().max())
+    _within(mode + " sums", sums, ref["sums"])             # (n / 256 + 10) u sum|t|
+    _within(mode + " gb", gb, ref["gb"])
     torch.testing.assert_close(sums.double().cpu(), t.detach(), rtol=2e-5, atol=1e-4)
-    wv = w.view(B, 1, 1, 1)
     torch.testing.assert_close(gb.double().cpu() * wv, br.grad, rtol=2e-5, atol=1e-5 * float(br.grad.abs().max()))
     if mode == "xent":
         assert ga is None
     else:
+        _within(mode + " ga", ga, ref["ga"])
         torch.testing.assert_close(ga.double().cpu() * wv, ar.grad, rtol=2e-5, atol=1e-5 * float(ar.grad.abs().max()))
 
 

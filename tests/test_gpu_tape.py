@@ -3,7 +3,7 @@
 Every tape case is a hand-built graph of 2 to 12 nodes (tests/tape_ref.py: CASES) run TWICE with different inputs; the second run's activations, tensor
 gradients, flat variable gradients and loss block are compared with the float64 twin that interprets the same node list on the CPU.  One rule for every
 compared tensor: e = |gpu - ref64| / |ref64| <= max(floor, 3 * e32), e32 = the float32 twin's own error against ref64; floor = 2e-6 (the Dense figure below),
-or the bound the kernel's own test states for graphs built on the STN / renderer / z_pres / conv kernels (tests/test_gpu_spair.py).  The assembled step is
+or, for graphs built on the STN / renderer / z_pres kernels, the norm of the per-element bounds of tests/spair_glue_ref.py over the norm of the reference (conv kernels: tests/test_gpu_spair.py).  The assembled step is
 under the oracle in tests/test_gpu_spair_model.py."""
 import os
 import sys
