@@ -690,6 +690,61 @@ int sv_iw_advance(const float* z_mean_x, const float* z_sig_x, const float* z_me
  * zero it once per test set, read it back once.  SV_E_BADARG: state or out3 NULL, K or B <= 0. */
 int sv_iw_finish(const double* state, int32_t K, float* out3, double* acc, int32_t B, void* stream);
 
+/* ---------------------------------------------------------------- IW for the mixture models: LGGMVae (SPLIT-GMVAE) and GMVae
+ * No reference counterpart.  The same K-sample bound for the two models whose global latent has the y-conditional mixture prior,
+ * with y marginalised on both sides (Rao-Blackwellised) instead of weighting (y, z) pairs (csrc/iw_gm.hip).  `n` below is the number
+ * of mixture components (y_size, 1 .. 128); K stays the number of importance samples.
+ *
+ * Generative model (the discrete-y model visualizer.generate samples from):
+ *   y ~ Uniform{0 .. n-1}                                   (the y-KL of vae/trainer.py:161 is against 1/n)
+ *   z_g | y ~ N(pm[y], ps[y]),  pm[y] = W_pm[y,:] + b_pm,  ps[y] = softplus(W_ps[y,:] + b_ps)       (encode_y of a one-hot)
+ *   z_l ~ N(0, I)                                           (LGGMVae only)
+ * Proposal per image b: the encoder of vae/model.py:116-135 evaluated at one-hot y:
+ *   pi_b = softmax(logits[b]);  h_top[c] = elu(W_ht[c,:] + b_ht)  (does not depend on the image);
+ *   zm[b,c,:] = (he[b] + h_top[c]) . W_zm + b_zm,   zs[b,c,:] = softplus((he[b] + h_top[c]) . W_zs + b_zs),
+ *   he = the GM encoder's buffer of that name (elu of e1) in test mode (no dropout); q(z_l | x_hat) = N(mu_l, sig_l) as in LGVae.
+ * Sample k:  c ~ Cat(pi_b);  z_g = zm[b,c] + zs[b,c] * eps_g;  z_l = mu_l + sig_l * eps_l   (the fp32 expression of sv_iw_advance),
+ * stored to zcat in the plan's dtype.  With z the STORED latent (SV_F32: z as drawn; SV_BF16: z~ = bf16(z), the existing rule) and
+ *   g(z; m, s) = sum_d [ -((z_d - m_d) / s_d)^2 / 2 - log s_d ]     (log N without the -Lg/2 log 2 pi both mixtures share)
+ *   r = logsumexp_c [ -log n + g(z_g; pm[c], ps[c]) ] - logsumexp_c [ log pi_b,c + g(z_g; zm[b,c], zs[b,c]) ]
+ *       + sum_j [ (t_j^2 - z_l,j^2) / 2 + log sig_l,j ],   t_j = (z_l,j - mu_l,j) / sig_l,j,
+ * all in fp32, both log-sum-exps with their maximum subtracted (components hundreds of sigmas away underflow to 0, never to -inf or
+ * NaN), log pi_b,c = (logits[b,c] - max) - log sum_c' exp(logits[b,c'] - max) with the sum cumulated in index order.
+ *   lw_joint = -nll_x - nll_xh + r,  lw_x = -nll_x + r;  per-image L_K, elbo and bits/dim exactly as sv_iw_advance / sv_iw_finish define
+ * them: the state is the same [B,5] fp64 layout and sv_iw_finish is the finish of both.  GMVae is the one-branch mode: Ll = 0, no
+ * nll_xh, joint == x.  `elbo` here is the MEAN LOG-WEIGHT OF THIS MARGINAL ESTIMATOR, mean_k lw_joint -- not the training loss, whose
+ * y is relaxed (Gumbel-softmax) and whose KL terms are taken per y sample.
+ * The component pick when `comp` is NULL: a Philox uniform u in (0, 1] with the key constant of sv_iw_advance and counter (0, global
+ * image index sample_offset + b, 'iw' tag | 2, sample k) -- a pure function of (seed, image, sample); inverse CDF over the fp32
+ * e_c = exp(logits[b,c] - max), cumulated in index order: the first c whose cumulated mass is >= u * total, the last component
+ * catching rounding.  sv_iw_gm_uniform_host is the host mirror of u.  eps_g / eps_l: `eps` [B, Lg + Ll] pins them, NULL draws them
+ * as sv_iw_advance does (tags 0 / 1).  comp [B] int32 pins the component (clamped to 0 .. n-1); comp_out [B] always receives it.
+ *
+ * sv_iw_gm_advance has the contract of sv_iw_advance (k, SV_IW_ACCUMULATE, SV_IW_DRAW, a draw-only first and an accumulate-only last
+ * call, no atomics, no host round trip, bit-reproducible).  logits [B,n], zm_all / zs_all [B,n,Lg], pm / ps [n,Lg], all fp32.
+ * One 256-thread workgroup per image: wave 0 takes the softmax and the pick; all threads draw z (z_g kept in LDS); for the densities
+ * thread (c, s) owns component c and the dimensions d = s, s + S, ... with S = min(64, 256 / pow2ceil(n)) adjacent lanes per
+ * component, so ONE log2(S)-step shuffle reduction finishes all 2 n sums at once, and wave 0 takes both log-sum-exps over n together.
+ * Lg and Ll may be any positive size (Ll = 0: one branch).  SV_E_BADARG: B or Lg <= 0, Ll < 0, n outside 1 .. 128, k < 0, flags 0 or
+ * with an unknown bit, a z_dtype outside sv_dtype, r NULL; with ACCUMULATE: nll_x / state NULL, nll_xh NULL while Ll > 0, k < 1; with
+ * DRAW: a null logits / zm_all / zs_all / pm / ps / zcat / comp_out, a null z_mean_xh / z_sig_xh while Ll > 0, ldz < Lg + Ll. */
+int sv_iw_gm_advance(const float* logits, const float* zm_all, const float* zs_all, const float* pm, const float* ps,
+                     const float* z_mean_xh, const float* z_sig_xh, const float* eps, const int32_t* comp, int32_t* comp_out,
+                     void* zcat, int32_t z_dtype, int32_t ldz, float* r, const float* nll_x, const float* nll_xh, double* state,
+                     int32_t B, int32_t n, int32_t Lg, int32_t Ll, int32_t k, uint64_t seed, int64_t sample_offset, int32_t flags,
+                     void* stream);
+/* the uniform of the component pick of (seed, global image index, sample k): no device needed */
+float sv_iw_gm_uniform_host(uint64_t seed, int64_t image, int32_t sample);
+/* The component tables of one batch, once per batch, in exact fp32 (sequential fma-free multiply-adds over the hidden index in
+ * ascending order): h_top[c] = elu(w_ht[c,:] + b_ht); zm_all[b,c,:] = (he[b] + h_top[c]) . w_zm + b_zm; zs_all = softplus(the same
+ * with w_zs, b_zs); pm[c,:] = w_pm[c,:] + b_pm; ps[c,:] = softplus(w_ps[c,:] + b_ps).  he [B, hidden] in he_dtype (the GM encoder's
+ * buffer, row pitch hidden); w_ht [n, hidden], w_zm / w_zs [hidden, L], w_pm / w_ps [n, L]: the Keras kernels as they lie in the
+ * flat parameter buffer.  SV_E_BADARG: a null pointer, B, L or hidden <= 0, n outside 1 .. 128, hidden > 1024, a he_dtype outside
+ * sv_dtype. */
+int sv_iw_gm_tables(const void* he, int32_t he_dtype, const float* w_ht, const float* b_ht, const float* w_zm, const float* b_zm,
+                    const float* w_zs, const float* b_zs, const float* w_pm, const float* b_pm, const float* w_ps, const float* b_ps,
+                    float* zm_all, float* zs_all, float* pm, float* ps, int32_t B, int32_t n, int32_t hidden, int32_t L, void* stream);
+
 /* ---------------------------------------------------------------- k-NN label probe of the latents (csrc/knn.hip)
  * No reference counterpart: the probe classifier of vae/trainer.py:81-97 needs a weights blob that is missing upstream.  This is
  * the parameter-free representation metric instead: classify each query latent q [Nq, L] (row pitch ldq) by the majority label of

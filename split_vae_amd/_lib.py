@@ -269,6 +269,9 @@ SYMBOLS = {
     "sv_lgvae_profile_read_issued": (C.c_int, [_vp, _i32, _vp]),
     "sv_iw_advance": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _u64, _i64, _i32, _vp]),
     "sv_iw_finish": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp]),
+    "sv_iw_gm_advance": (C.c_int, [_vp] * 11 + [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _u64, _i64, _i32, _vp]),
+    "sv_iw_gm_uniform_host": (C.c_float, [_u64, _i64, _i32]),
+    "sv_iw_gm_tables": (C.c_int, [_vp, _i32] + [_vp] * 14 + [_i32, _i32, _i32, _i32, _vp]),
     "sv_knn_chunk_rows": (C.c_int, []),
     "sv_knn_workspace_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
     "sv_knn_classify": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

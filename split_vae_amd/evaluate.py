@@ -1,5 +1,6 @@
-"""Measure a saved model without training: the importance-weighted test log-likelihood of split_vae_amd/iw.py (LGVae) and / or
-the k-NN label probe of the latents of split_vae_amd/probe.py (every model).
+"""Measure a saved model without training: the importance-weighted test log-likelihood of split_vae_amd/iw.py (--iw_samples:
+LGVae; --gm_iw_samples: the mixture bound of LGGMVae / GMVae) and / or the k-NN label probe of the latents of
+split_vae_amd/probe.py (every model).
 
     python -m split_vae_amd.evaluate --weights models/20260101-120000.h5 --dataset svhn --iw_samples 64 -no_label
     python -m split_vae_amd.evaluate --weights models/20260101-120000.h5 --dataset svhn --knn_probe 5
@@ -20,7 +21,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     from . import iw, probe
     iw.check_model_name(args.model, args.iw_samples)     # before any data or device work
-    if args.iw_samples <= 0 and args.knn_probe == 0:
+    iw.check_mixture_model_name(args.model, args.gm_iw_samples)
+    if args.iw_samples <= 0 and args.gm_iw_samples <= 0 and args.knn_probe == 0:
         raise SystemExit("nothing to measure: pass --iw_samples K (importance samples per image, K >= 1) and / or --knn_probe K "
                          "(neighbours of the latent label probe, 1 <= K <= 32)")
     probe.check_flags(args.knn_probe, args.knn_refs, args.no_label)
@@ -46,6 +48,9 @@ def main(argv=None):
     if config.iw_samples > 0:
         res = iw.evaluate(model, test_batches, config.iw_samples)
         print(iw.report_line(config.iw_samples, res))
+    if config.gm_iw_samples > 0:
+        res = iw.mixture_evaluate(model, test_batches, config.gm_iw_samples)
+        print(iw.mixture_report_line(config.gm_iw_samples, res))
     if config.knn_probe:
         refs = make_probe_references(train_ds, config)
         pr = probe.knn_probe(model, refs, test_batches, config.knn_probe)

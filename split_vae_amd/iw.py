@@ -96,3 +96,120 @@ def evaluate(model, batches, K, seed=None):
 
 def report_line(K, res):
     return REPORT.format(int(K), res["iw_joint"], res["iw_x"], res["bits_per_dim_x"])
+
+
+# ---------------------------------------------------------------- the mixture models: LGGMVae and GMVae (sv_iw_gm_advance)
+# The estimator is pinned in include/splitvae.h: y is marginalised on both sides, so a sample is a component pick c ~ Cat(pi_b), a
+# draw from the posterior component c, and two n-component mixture log-densities.  Per batch the encoders run once (the GM encoder
+# in test mode and, for LGGMVae, the plan's local encoder) and sv_iw_gm_tables builds the component tables once; then K decoder +
+# loss passes with K + 1 launches of sv_iw_gm_advance between them, all on one stream.
+MIXTURE_REPORT = 'Test IW-{} mixture bound: joint {:.4f}, x {:.4f} nats; x bits/dim {:.4f}'
+MIXTURE_MODELS = ('lggmvae', 'gmvae')
+MIXTURE_HISTORY_KEYS = ("gm_iw_joint", "gm_iw_x", "gm_bits_per_dim_x")
+
+
+def check_mixture_model_name(model_name, gm_iw_samples):
+    """--gm_iw_samples against --model, before any data or device work (main.py, evaluate.py)."""
+    if gm_iw_samples < 0:
+        raise SystemExit("--gm_iw_samples must be >= 0")
+    if gm_iw_samples and model_name not in MIXTURE_MODELS:
+        raise SystemExit("--model %s: --gm_iw_samples covers --model lggmvae / gmvae only (the mixture estimator); for lgvae use "
+                         "--iw_samples." % model_name)
+
+
+def _mixture_kind(model):
+    from .gm import LGGMVae
+    from .gmvae import GMVae
+    if type(model) is LGGMVae:
+        return True
+    if type(model) is GMVae:
+        return False
+    raise TypeError("the mixture bound covers LGGMVae and GMVae only; LGVae has log_likelihood (got %s)" % type(model).__name__)
+
+
+def _gm_params(model):
+    """(kernel, bias) views into model.gm_flat of the five Dense layers the component tables need."""
+    from .gm import GM_LAYERS
+    views = model._gm_views(model.gm_flat)
+    return {n: (views[2 * GM_LAYERS.index(n)], views[2 * GM_LAYERS.index(n) + 1]) for n in ("ht", "zm", "zs", "pm", "ps")}
+
+
+def mixture_log_likelihood(model, images, K, eps=None, comp=None, seed=None, sample_offset=0, acc=None, prep=True):
+    """Per-image device tensors (L_joint, L_x, elbo) [B] fp32 of the K-sample mixture bound of LGGMVae / GMVae for one batch
+    [B,H,W,6] (GMVae also takes the 9-channel high_low_pass batch: it scores channels 0-2, as test_step_gm_vae does).  eps
+    [K,B,Lg+Ll] fp32 and comp [K,B] int32 pin the noise and the components (Ll = 0 for GMVae); otherwise sample k of image
+    sample_offset + b is keyed by (seed, image, k).  GMVae: L_joint == L_x.  `elbo` is the mean log-weight of this estimator, not
+    the training loss.  acc, prep: as log_likelihood.  Leaves model._calls alone."""
+    split = _mixture_kind(model)
+    if int(K) < 1:
+        raise ValueError("K must be >= 1, got %r" % (K,))
+    K = int(K)
+    if not split:
+        from .gmvae import _images6
+        images = _images6(images)
+    elif torch.is_tensor(images) and images.dim() == 4 and images.shape[-1] == 9:
+        raise ValueError("LGGMVae cannot score a high_low_pass batch (9 channels: x | x - low | low): its x_hat decoder has 3 channels")
+    from .trainer import _check_images
+    _check_images(model, images)
+    B = images.shape[0]
+    Lg, Ll = model.global_latent_dims, (model.local_latent_dims if split else 0)
+    n = model.y_size
+    f32, i32, dev = torch.float32, torch.int32, images.device
+    if eps is not None and (tuple(eps.shape) != (K, B, Lg + Ll) or eps.dtype != f32 or not eps.is_cuda or not eps.is_contiguous()):
+        raise ValueError("eps must be a contiguous [K=%d, B=%d, %d] fp32 device tensor" % (K, B, Lg + Ll))
+    if comp is not None and (tuple(comp.shape) != (K, B) or comp.dtype != i32 or not comp.is_cuda or not comp.is_contiguous()):
+        raise ValueError("comp must be a contiguous [K=%d, B=%d] int32 device tensor" % (K, B))
+    seed = model.seed if seed is None else seed
+    plan, enc = model.plan(B), model.encoder(B)
+    zcat = plan.buffer("zcat", model.dtype, (B, Lg + Ll))
+    nll_x = plan.buffer("nll_x", f32, (B,))
+    zm_h = zs_h = nll_xh = None
+    if split:
+        zm_h, zs_h = plan.buffer("z_mean_xh", f32, (B, Ll)), plan.buffer("z_sig_xh", f32, (B, Ll))
+        nll_xh = plan.buffer("nll_xh", f32, (B,))
+    state = torch.empty((B, 5), dtype=torch.float64, device=dev)
+    r = torch.empty((B,), dtype=f32, device=dev)
+    comp_out = torch.empty((B,), dtype=i32, device=dev)
+    P = _gm_params(model)
+    images = images.contiguous()
+    with ops.hold_stream():
+        plan.step((PHASE_PREP if prep else 0) | PHASE_FWD_ENCODERS, params=model.flat, images6=images, seed=model.seed)
+        if prep:
+            enc.prep(model.gm_flat)
+        enc.forward(model.gm_flat, plan.buffer("in8_x", model.dtype, (B, model.H, model.W, 8)), zcat, False, seed=model.seed)
+        zm_all, zs_all, pm, ps = ops.iw_gm_tables(enc.buf["he"], *P["ht"], *P["zm"], *P["zs"], *P["pm"], *P["ps"])
+        logits = enc.buf["logits"]
+        for k in range(K + 1):
+            flags = (IW_ACCUMULATE if k > 0 else 0) | (IW_DRAW if k < K else 0)
+            ops.iw_gm_advance(logits, zm_all, zs_all, pm, ps, zm_h, zs_h, zcat, r, comp_out, k, flags, nll_x=nll_x, nll_xh=nll_xh,
+                              state=state, eps=None if eps is None or k == K else eps[k],
+                              comp=None if comp is None or k == K else comp[k], seed=seed, sample_offset=sample_offset)
+            if k < K:
+                plan.step(PHASE_FWD_DECODERS | PHASE_LOSS, params=model.flat, images6=images)
+        out = ops.iw_finish(state, K, acc=acc)
+    return out[:, 0], out[:, 1], out[:, 2]
+
+
+def mixture_evaluate(model, batches, K, seed=None):
+    """Means over a test set: {gm_iw_joint, gm_iw_x, gm_elbo (nats per image), gm_bits_per_dim_x, n_images}; as evaluate: one
+    read-back per test set, the weight preparation once per plan, image i of the set draws with sample_offset = i."""
+    _mixture_kind(model)
+    acc = torch.zeros((4,), dtype=torch.float64, device=model.device)
+    prepped, offset = set(), 0
+    for batch in batches:
+        images = batch[0] if isinstance(batch, (tuple, list)) else batch
+        B = images.shape[0]
+        mixture_log_likelihood(model, images, K, seed=seed, sample_offset=offset, acc=acc, prep=B not in prepped)
+        prepped.add(B)
+        offset += B
+    a = acc.cpu().tolist()
+    n = int(a[3])
+    if n == 0:
+        raise ValueError("mixture_evaluate: no test batches")
+    out = dict(gm_iw_joint=a[0] / n, gm_iw_x=a[1] / n, gm_elbo=a[2] / n, n_images=n)
+    out["gm_bits_per_dim_x"] = bits_per_dim(out["gm_iw_x"], model.H, model.W)
+    return out
+
+
+def mixture_report_line(K, res):
+    return MIXTURE_REPORT.format(int(K), res["gm_iw_joint"], res["gm_iw_x"], res["gm_bits_per_dim_x"])

@@ -4,7 +4,7 @@
     python -m split_vae_amd.main --model gmvae --beta 40 --patch_size 4       (GMVAE baseline, Table 2)
 
 Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout, --mix_per_image,
---resident_data, --iw_samples, --knn_probe, --knn_refs.
+--resident_data, --iw_samples, --gm_iw_samples, --knn_probe, --knn_refs.
 """
 import argparse
 
@@ -48,6 +48,9 @@ def build_parser():
     ap.add_argument("--iw_samples", type=int, default=0,
                     help="K > 0: after the report of every evaluation, the K-sample importance-weighted bound of the test log-likelihood "
                          "(joint and x-only, nats) and the bits per dimension of x (split_vae_amd/iw.py); --model lgvae only")
+    ap.add_argument("--gm_iw_samples", type=int, default=0,
+                    help="K > 0: after the report of every evaluation, the K-sample importance-weighted bound of the mixture models' "
+                         "test log-likelihood, y marginalised (split_vae_amd/iw.py: mixture_evaluate); --model lggmvae / gmvae only")
     ap.add_argument("--knn_probe", type=int, default=0,
                     help="K > 0: after the report of every evaluation, the accuracy of a K-nearest-neighbour classifier of the test "
                          "set's latent means over --knn_refs training images, for z_g and z_l separately (split_vae_amd/probe.py); "
@@ -125,8 +128,9 @@ def make_model(model_name, config, input_shape):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    from .iw import check_model_name
+    from .iw import check_mixture_model_name, check_model_name
     check_model_name(args.model, args.iw_samples)    # before any data or device work
+    check_mixture_model_name(args.model, args.gm_iw_samples)
     from .probe import check_flags
     check_flags(args.knn_probe, args.knn_refs, args.no_label)
     from . import configure_hw_queues

@@ -721,6 +721,53 @@ def iw_finish(state, K, out3=None, acc=None):
     return out3
 
 
+def iw_gm_advance(logits, zm_all, zs_all, pm, ps, z_mean_xh, z_sig_xh, zcat, r, comp_out, k, flags, nll_x=None, nll_xh=None,
+                  state=None, eps=None, comp=None, seed=0, sample_offset=0):
+    """sv_iw_gm_advance, the mixture models' sv_iw_advance: logits [B,n], zm_all / zs_all [B,n,Lg], pm / ps [n,Lg] fp32; z_mean_xh /
+    z_sig_xh [B,Ll] or None (one branch, Ll = 0); eps [B,Lg+Ll] fp32 and comp [B] int32 pin the draw; comp_out [B] int32 receives
+    the component drawn."""
+    B, n, Lg = zm_all.shape
+    Ll = 0 if z_mean_xh is None else z_mean_xh.shape[1]
+    i32 = torch.int32
+    assert tuple(logits.shape) == (B, n) and tuple(zs_all.shape) == (B, n, Lg) and tuple(pm.shape) == (n, Lg) and tuple(ps.shape) == (n, Lg)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (logits, zm_all, zs_all, pm, ps, r))
+    assert z_mean_xh is None or (tuple(z_mean_xh.shape) == tuple(z_sig_xh.shape) == (B, Ll) and z_mean_xh.is_contiguous() and z_sig_xh.is_contiguous())
+    assert state is None or (state.dtype == torch.float64 and tuple(state.shape) == (B, 5))
+    assert eps is None or (eps.dtype == torch.float32 and tuple(eps.shape) == (B, Lg + Ll) and eps.is_contiguous())
+    assert comp_out.dtype == i32 and comp_out.numel() == B and (comp is None or (comp.dtype == i32 and comp.numel() == B))
+    assert zcat.shape[0] == B and zcat.stride(1) == 1 and r.numel() == B
+    check(_lib.load().sv_iw_gm_advance(_p(logits), _p(zm_all), _p(zs_all), _p(pm), _p(ps), _p(z_mean_xh), _p(z_sig_xh), _p(eps), _p(comp),
+                                       _p(comp_out), _p(zcat), sv_dtype(zcat.dtype), zcat.stride(0), _p(r), _p(nll_x), _p(nll_xh),
+                                       _p(state), B, n, Lg, Ll, int(k), int(seed), int(sample_offset), int(flags), _stream()),
+          "sv_iw_gm_advance")
+
+
+def iw_gm_uniform_host(seed, image, sample):
+    """sv_iw_gm_uniform_host: the uniform in (0, 1] behind the component pick of (seed, global image index, sample).  No device."""
+    return float(_lib.load().sv_iw_gm_uniform_host(int(seed), int(image), int(sample)))
+
+
+def iw_gm_tables(he, w_ht, b_ht, w_zm, b_zm, w_zs, b_zs, w_pm, b_pm, w_ps, b_ps, out=None):
+    """sv_iw_gm_tables: (zm_all, zs_all [B,n,L], pm, ps [n,L]) fp32 from the GM encoder's he [B,hidden] and the Keras kernels / biases
+    of h_top_dense, z_mean, z_sig, z_prior_mean, z_prior_sig (views of the flat parameter buffer)."""
+    B, hidden = he.shape
+    n, L = w_pm.shape
+    f32 = torch.float32
+    assert he.is_contiguous() and tuple(w_ht.shape) == (n, hidden) and tuple(w_zm.shape) == tuple(w_zs.shape) == (hidden, L) and tuple(w_ps.shape) == (n, L)
+    assert b_ht.numel() == hidden and b_zm.numel() == b_zs.numel() == b_pm.numel() == b_ps.numel() == L
+    assert all(t.dtype == f32 and t.is_contiguous() for t in (w_ht, b_ht, w_zm, b_zm, w_zs, b_zs, w_pm, b_pm, w_ps, b_ps))
+    if out is None:
+        e = lambda *s: torch.empty(s, dtype=f32, device=he.device)      # noqa: E731
+        out = (e(B, n, L), e(B, n, L), e(n, L), e(n, L))
+    zm_all, zs_all, pm, ps = out
+    assert tuple(zm_all.shape) == tuple(zs_all.shape) == (B, n, L) and tuple(pm.shape) == tuple(ps.shape) == (n, L)
+    assert all(t.dtype == f32 and t.is_contiguous() for t in out)
+    check(_lib.load().sv_iw_gm_tables(_p(he), sv_dtype(he.dtype), _p(w_ht), _p(b_ht), _p(w_zm), _p(b_zm), _p(w_zs), _p(b_zs), _p(w_pm),
+                                      _p(b_pm), _p(w_ps), _p(b_ps), _p(zm_all), _p(zs_all), _p(pm), _p(ps), B, n, hidden, L, _stream()),
+          "sv_iw_gm_tables")
+    return out
+
+
 # ------------------------------------------------------------------ k-NN label probe of the latents (include/splitvae.h)
 def knn_chunk_rows():
     return int(_lib.load().sv_knn_chunk_rows())

@@ -239,6 +239,21 @@ def _knn_probe_report(model, test_dataset, config, step):
     return res
 
 
+def _gm_iw_report(model, test_dataset, config, step):
+    """--gm_iw_samples K: the mixture models' importance-weighted bound (iw.mixture_evaluate) behind an evaluation's report; the
+    figures are kept in config.gm_iw_history: one dict(step, gm_iw_joint, gm_iw_x, gm_bits_per_dim_x) per evaluation."""
+    k = int(config.get("gm_iw_samples") or 0)
+    if k <= 0:
+        return None
+    from . import iw
+    res = iw.mixture_evaluate(model, test_dataset, k)
+    print(iw.mixture_report_line(k, res))
+    if config.get("gm_iw_history") is None:
+        config.gm_iw_history = []
+    config.gm_iw_history.append(dict(step=step, **{key: res[key] for key in iw.MIXTURE_HISTORY_KEYS}))
+    return res
+
+
 def _save(model, run_name):
     """vae/trainer.py:421: model.save_weights('models/'+RUN_NAME+'.h5') -- Keras HDF5 when libhdf5 is present, else .npz."""
     from . import h5io
@@ -308,6 +323,7 @@ def _train_lggmvae(model, optimizer, train_dataset, test_dataset, config):
                       '{}Y KL loss: {:.4f}'.format(tag, v[0], tag, v[1], tag, v[2], tag, v[3], tag, v[4]))
             if cluster is not None:
                 print('            Classifier cluster acc: {:.4f}'.format(cluster.result()))
+            _gm_iw_report(model, test_dataset, config, step)
             _knn_probe_report(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             acc, n_acc = None, 0
@@ -364,6 +380,7 @@ def _train_gmvae(model, optimizer, train_dataset, test_dataset, config):
             if cluster is not None:
                 print('            Classifier cluster acc: {:.4f}'.format(cluster.result()))
             print('            Y KL train loss: {:.4f}, Y KL test loss: {:.4f}'.format(tr[2], te[2]))
+            _gm_iw_report(model, test_dataset, config, step)
             _knn_probe_report(model, test_dataset, config, step)
             acc, n_acc = None, 0
             start = time.time()
