@@ -428,9 +428,9 @@ void svg_dgrad_args(const sv_conv_desc* d, int cls, TapGemmArgs* a, uint8_t srct
 // grid in every class) run as ONE problem: the class weight images, laid back to back, are a [4*Cin][ntaps*gdy] image
 // of a stride-1 conv dY -> 4*Cin columns on the class grid, and column n = (class, channel) is stored to the class's
 // sub-pixel (TapGemmArgs::cls_n).  One staging of the dY tile and one A fragment then serve four classes.
-// -> false when the classes differ (k = 4: windows {0,-1} and {1,0}), the widths do not fit a 128-column tile, or the
-// caller's images are not contiguous (class_stride = elements between consecutive class images).
-bool svg_dgrad_merged_args(const sv_conv_desc* d, const int64_t* class_off, TapGemmArgs* a) {
+// -> false when the classes differ (k = 4: windows {0,-1} and {1,0}) or the widths do not fit a 128-column tile.  (The class
+// images are back to back in every input-gradient image: svg_wimage_dgrad.)
+bool svg_dgrad_merged_args(const sv_conv_desc* d, TapGemmArgs* a) {
   const bool off = sv_knob_no_cls_merge();        // A/B: one problem per parity class
   if (off || d->stride != 2 || (d->Cin & 7) || 4 * d->Cin > 128 || (4 * d->Cin) % 32) return false;
   uint8_t srctap[SV_MAX_TAPS];
@@ -439,7 +439,6 @@ bool svg_dgrad_merged_args(const sv_conv_desc* d, const int64_t* class_off, TapG
     TapGemmArgs b;
     svg_dgrad_args(d, c, &b, srctap);
     if (b.ntaps != a->ntaps || memcmp(b.dy, a->dy, a->ntaps) || memcmp(b.dx, a->dx, a->ntaps)) return false;
-    if (class_off[c] - class_off[c - 1] != svg_wprep_elems_class(d, 1, c - 1)) return false;
   }
   a->N = 4 * d->Cin; a->cls_n = d->Cin; a->ooy = 0; a->oox = 0;
   return true;
@@ -498,9 +497,9 @@ void svg_wgrad_args(const sv_conv_desc* d, WgradArgs* a, bool plain) {
 // m-splits of the im2col wgrad: every split adds one atomic pass over dW (~1.3 TB/s chip-wide), so use only as
 // many as it takes to put `target_wgs` workgroups (~2 per CU; SV_WGRAD_WGS overrides for tuning) on the chip
 void svg_wgrad_set_msplit(WgradArgs* a, int cfg, int dtype, int target_wgs) {
-  static const int BRt[4] = {64, 128, 256, 256}, BNt[4] = {128, 64, 32, 16};
+  static const int BRt[4] = {64, 128, 256, 256};
   const int ms = dtype == SV_BF16 ? 64 : 32;
-  const int tiles = ((a->Nrows + BRt[cfg] - 1) / BRt[cfg]) * ((a->N + BNt[cfg] - 1) / BNt[cfg]);
+  const int tiles = ((a->Nrows + BRt[cfg] - 1) / BRt[cfg]) * ((a->N + svg_BNt[cfg] - 1) / svg_BNt[cfg]);
   int z = target_wgs / (tiles > 0 ? tiles : 1);
   const int maxz = (a->M + ms - 1) / ms;
   if (z < 1 || sv_deterministic()) z = 1;      // deterministic: no m-split, the kernel's plain (non-atomic) epilogue
@@ -508,23 +507,21 @@ void svg_wgrad_set_msplit(WgradArgs* a, int cfg, int dtype, int target_wgs) {
   a->msplit = round_up((a->M + z - 1) / z, ms);
 }
 
-void svg_prep_job_fwd(const sv_conv_desc* d, PrepJob* j) {
+// ---- the jobs of the image parts (svg_wimage_*, below, places them and counts their blocks)
+static void svg_prep_job_fwd(const sv_conv_desc* d, PrepJob* j) {
   memset(j, 0, sizeof(*j));
-  static const int BNt[4] = {128, 64, 32, 16};
   j->ntaps = d->KH * d->KW;
   j->Cin = d->Cin; j->Cout = d->Cout;
-  j->rows = round_up(d->Cout, BNt[svg_pick_cfg(d->Cout)]);
+  j->rows = svg_rows_pad(d->Cout);
   j->inner = svg_cin_pad(d);
   j->inner_ld = j->inner; j->inner_off = 0;
   j->transpose = 0;
   if (svg_s2d3(d)) {
     j->ntaps = 9; j->inner = 16; j->inner_ld = 16; j->s2d3 = 1;
-    j->nblocks = (j->rows * 144 + 256 * SV_PREP_UNITS - 1) / (256 * SV_PREP_UNITS);
     return;
   }
   if (svg_poly(d)) {
-    j->ntaps = 25; j->rows = 32; j->poly = 1;
-    j->nblocks = (j->rows * j->ntaps * j->inner + 256 * SV_PREP_UNITS - 1) / (256 * SV_PREP_UNITS);
+    j->ntaps = 25; j->rows = 32; j->poly = SV_PREP_POLY_MAIN;
     return;
   }
   if (svg_packx(d)) {
@@ -536,15 +533,13 @@ void svg_prep_job_fwd(const sv_conv_desc* d, PrepJob* j) {
   if (!j->packx_kw)
     for (int kh = 0; kh < d->KH; ++kh)
       for (int kw = 0; kw < d->KW; ++kw) j->srctap[svg_fwd_tap(d, kh, kw)] = (uint8_t)(kh * d->KW + kw);
-  j->nblocks = svg_prep_nblocks(j);
 }
 
-void svg_prep_job_polyfix(const sv_conv_desc* d, PrepJob* j) {
+static void svg_prep_job_polyfix(const sv_conv_desc* d, PrepJob* j) {
   memset(j, 0, sizeof(*j));
   j->Cin = d->Cin; j->Cout = d->Cout;
-  j->rows = 160; j->ntaps = 6; j->inner = svg_cin_pad(d); j->inner_ld = j->inner;     // [10][6][16][Cin] (SV_POLY_FIX_ELEMS)
-  j->poly = 2;
-  j->nblocks = (j->rows * j->ntaps * j->inner + 256 * SV_PREP_UNITS - 1) / (256 * SV_PREP_UNITS);
+  j->rows = 160; j->ntaps = 6; j->inner = svg_cin_pad(d); j->inner_ld = j->inner;     // [10 border classes][6 taps][16 columns][Cin]
+  j->poly = SV_PREP_POLY_FIX;
 }
 
 // ---- per-class polyphase (conv_geom.h: svg_polyc)
@@ -567,32 +562,23 @@ void svg_polyc_fwd_args(const sv_conv_desc* d, int cls, TapGemmArgs* a) {
     for (int tyi = 0; tyi < nty; ++tyi) { a->dy[txi * nty + tyi] = (int8_t)(ty0 + tyi); a->dx[txi * nty + tyi] = (int8_t)(tx0 + txi); }
 }
 
-void svg_prep_job_polyc(const sv_conv_desc* d, int cls, PrepJob* j) {
+static void svg_prep_job_polyc(const sv_conv_desc* d, int cls, PrepJob* j) {
   memset(j, 0, sizeof(*j));
-  static const int BNt[4] = {128, 64, 32, 16};
   int t0;
   j->Cin = d->Cin; j->Cout = d->Cout;
-  j->rows = round_up(d->Cout, BNt[svg_pick_cfg(d->Cout)]);
+  j->rows = svg_rows_pad(d->Cout);
   j->inner = svg_cin_pad(d); j->inner_ld = j->inner;
   j->ntaps = svg_polyc_taps(d->KH, cls >> 1, &t0) * svg_polyc_taps(d->KH, cls & 1, &t0);
-  j->poly = 3; j->pk = d->KH; j->pcls = cls;
-  j->nblocks = (j->rows * j->ntaps * j->inner + 256 * SV_PREP_UNITS - 1) / (256 * SV_PREP_UNITS);
+  j->poly = SV_PREP_POLYC_CLASS; j->pk = d->KH; j->pcls = cls;
 }
 
-void svg_prep_job_polyc_fix(const sv_conv_desc* d, PrepJob* j) {
+static void svg_prep_job_polyc_fix(const sv_conv_desc* d, PrepJob* j) {
   memset(j, 0, sizeof(*j));
   j->Cin = d->Cin; j->Cout = d->Cout;
-  j->rows = d->Cout; j->inner = svg_cin_pad(d); j->inner_ld = j->inner; j->ntaps = d->KH;
-  j->poly = 4; j->pk = d->KH;
-  j->nblocks = (int)((svg_polyc_fix_elems(d) + 256 * SV_PREP_UNITS - 1) / (256 * SV_PREP_UNITS));
+  j->rows = d->Cout; j->inner = svg_cin_pad(d); j->inner_ld = j->inner; j->ntaps = d->KH;     // (once per border class: svg_prep_job_elems)
+  j->poly = SV_PREP_POLYC_FIX; j->pk = d->KH;
 }
 
-int64_t svg_polyc_class_elems(const sv_conv_desc* d, int cls) {
-  PrepJob j;
-  svg_prep_job_polyc(d, cls, &j);
-  return ((int64_t)j.rows * j.ntaps * j.inner + 127) / 128 * 128;      // every class image 128-element aligned
-}
-int64_t svg_polyc_fix_elems(const sv_conv_desc* d) { return (int64_t)2 * (d->KH - 1) * d->KH * d->Cout * svg_cin_pad(d); }
 // row-class terms [B][K-1][W][Cout] + column-class terms [B][H][K-1][Cout], fp32 (H, W: the hi-res extent)
 int64_t svg_polyc_fix_ws_bytes(const sv_conv_desc* d) { return (int64_t)d->B * (d->KH - 1) * (d->H + d->W) * d->Cout * 4; }
 
@@ -613,68 +599,72 @@ void svg_polyd_args(const sv_conv_desc* d, TapGemmArgs* a) {
     for (int dyi = 0; dyi < NT; ++dyi) { a->dy[dxi * NT + dyi] = (int8_t)(dyi - R); a->dx[dxi * NT + dyi] = (int8_t)(dxi - R); }
 }
 
-void svg_prep_job_polyd(const sv_conv_desc* d, int which, PrepJob* j) {
+static void svg_prep_job_polyd(const sv_conv_desc* d, int poly, PrepJob* j) {       // poly: SV_PREP_POLYD_MAIN / _EDGE / _CORNER
   memset(j, 0, sizeof(*j));
-  static const int BNt[4] = {128, 64, 32, 16};
   const int NT = 2 * svg_polyd_radius(d->KH) + 1;
-  j->Cin = d->Cin; j->Cout = d->Cout; j->pk = d->KH; j->poly = 5 + which;
-  if (which == 0) { j->rows = round_up(d->Cin, BNt[svg_pick_cfg(d->Cin)]); j->inner = svg_gdy(d); j->ntaps = NT * NT; }
-  else { j->rows = svg_cin_pad(d); j->inner = svg_polyd_cop(d); j->ntaps = which == 1 ? 16 * NT : 64; }
+  j->Cin = d->Cin; j->Cout = d->Cout; j->pk = d->KH; j->poly = poly;
+  if (poly == SV_PREP_POLYD_MAIN) { j->rows = svg_rows_pad(d->Cin); j->inner = svg_gdy(d); j->ntaps = NT * NT; }
+  else { j->rows = svg_cin_pad(d); j->inner = svg_polyd_cop(d); j->ntaps = poly == SV_PREP_POLYD_EDGE ? 16 * NT : 64; }
   j->inner_ld = j->inner;
-  j->nblocks = (int)(((int64_t)j->rows * j->ntaps * j->inner + 256 * SV_PREP_UNITS - 1) / (256 * SV_PREP_UNITS));
-}
-int64_t svg_polyd_elems(const sv_conv_desc* d, int which) {
-  PrepJob j;
-  svg_prep_job_polyd(d, which, &j);
-  return ((int64_t)j.rows * j.ntaps * j.inner + 127) / 128 * 128;
 }
 int64_t svg_polyd_ws_bytes(const sv_conv_desc* d) { return (int64_t)d->B * 2 * (d->H / 2 + d->W / 2) * svg_cin_pad(d) * 4; }
 
-void svg_prep_job_dgrad(const sv_conv_desc* d, int cls, PrepJob* j) {
+static void svg_prep_job_dgrad(const sv_conv_desc* d, int cls, PrepJob* j) {
   memset(j, 0, sizeof(*j));
-  static const int BNt[4] = {128, 64, 32, 16};
   TapGemmArgs a;
   svg_dgrad_args(d, cls, &a, j->srctap);
   j->ntaps = a.ntaps;
   j->Cin = d->Cin; j->Cout = d->Cout;
-  j->rows = round_up(d->Cin, BNt[svg_pick_cfg(d->Cin)]);
+  j->rows = svg_rows_pad(d->Cin);
   j->inner = svg_gdy(d);
   j->inner_ld = j->inner; j->inner_off = 0;
   j->transpose = 1;
-  j->nblocks = svg_prep_nblocks(j);
 }
 
-// stand-alone forward image of a per-class polyphase layer: the four class images, the border-class image, and -- 128-element aligned behind them -- the DIRECT
-// (fused-resize) image, which the forward falls back to when the caller brings no workspace for the border terms (the plan's arena keeps the class images only)
-static int64_t svg_polyc_direct_off(const sv_conv_desc* d) {
-  int64_t n = svg_polyc_fix_elems(d);
-  for (int c = 0; c < 4; ++c) n += svg_polyc_class_elems(d, c);
-  return (n + 127) / 128 * 128;
+// ---- the layout table (conv_geom.h: WImage)
+// appends a part at the image's end; the caller fills its job, wimage_close sizes it
+static PrepJob* wimage_open(WImage* w, int role, int cls = 0) {
+  WImagePart& p = w->part[w->n++];
+  p.role = role; p.cls = cls; p.off = w->elems;
+  return &p.job;
 }
-int64_t svg_wprep_elems_class(const sv_conv_desc* d, int for_dgrad, int cls) {
-  PrepJob j;
-  if (!for_dgrad && svg_polyc(d)) {
-    svg_prep_job_fwd(d, &j);
-    return svg_polyc_direct_off(d) + (int64_t)j.rows * j.ntaps * j.inner;
+static void wimage_close(WImage* w) {
+  WImagePart& p = w->part[w->n - 1];
+  p.job.dst_off = p.off;
+  p.job.nblocks = svg_prep_nblocks(&p.job);
+  p.elems = svg_prep_job_elems(&p.job);
+  // the class images of a per-class polyphase layer and the parts of a polyphase input gradient fill whole 128-element blocks
+  if (p.job.poly == SV_PREP_POLYC_CLASS || p.job.poly >= SV_PREP_POLYD_MAIN) p.elems = (p.elems + 127) / 128 * 128;
+  w->elems = p.off + p.elems;
+}
+
+void svg_wimage_fwd(const sv_conv_desc* d, bool polyc_classes, bool direct, WImage* w) {
+  w->n = 0; w->elems = 0;
+  if (polyc_classes) {
+    for (int c = 0; c < 4; ++c) { svg_prep_job_polyc(d, c, wimage_open(w, SV_WP_POLYC_CLASS, c)); wimage_close(w); }
+    svg_prep_job_polyc_fix(d, wimage_open(w, SV_WP_POLYC_FIX)); wimage_close(w);
+    if (!direct) return;
+    w->elems = (w->elems + 127) / 128 * 128;
   }
-  if (for_dgrad) svg_prep_job_dgrad(d, cls, &j); else svg_prep_job_fwd(d, &j);
-  return (int64_t)j.rows * j.ntaps * j.inner + (!for_dgrad && svg_poly(d) ? SV_POLY_FIX_ELEMS(svg_cin_pad(d)) : 0);
+  svg_prep_job_fwd(d, wimage_open(w, SV_WP_FWD)); wimage_close(w);
+  if (svg_poly(d)) { svg_prep_job_polyfix(d, wimage_open(w, SV_WP_POLY_FIX)); wimage_close(w); }
+}
+
+void svg_wimage_dgrad(const sv_conv_desc* d, WImage* w) {
+  w->n = 0; w->elems = 0;
+  for (int c = 0; c < svg_dgrad_classes(d); ++c) { svg_prep_job_dgrad(d, c, wimage_open(w, SV_WP_DGRAD_CLASS, c)); wimage_close(w); }
+  if (!svg_polyd(d)) return;
+  w->elems = (w->elems + 127) / 128 * 128;
+  static const int role[3] = {SV_WP_POLYD_MAIN, SV_WP_POLYD_EDGE, SV_WP_POLYD_CORNER};
+  for (int k = 0; k < 3; ++k) { svg_prep_job_polyd(d, SV_PREP_POLYD_MAIN + k, wimage_open(w, role[k])); wimage_close(w); }
 }
 
 // ============================================================================ public API
-// (for_dgrad: the direct-form class images; a layer with a polyphase input gradient -- svg_polyd -- keeps its main / edge / corner images behind them, 128-element aligned)
-static int64_t svg_polyd_base(const sv_conv_desc* d) {
-  int64_t n = 0;
-  for (int c = 0; c < svg_dgrad_classes(d); ++c) n += svg_wprep_elems_class(d, 1, c);
-  return (n + 127) / 128 * 128;
-}
 extern "C" int64_t sv_conv2d_wprep_elems(const sv_conv_desc* d, int32_t for_dgrad) {
   if (svg_check(d) != SV_OK) return -1;
-  if (!for_dgrad) return svg_wprep_elems_class(d, 0, 0);
-  int64_t n = 0;
-  for (int c = 0; c < svg_dgrad_classes(d); ++c) n += svg_wprep_elems_class(d, 1, c);
-  if (svg_polyd(d)) n = svg_polyd_base(d) + svg_polyd_elems(d, 0) + svg_polyd_elems(d, 1) + svg_polyd_elems(d, 2);
-  return n;
+  WImage w;
+  if (for_dgrad) svg_wimage_dgrad(d, &w); else svg_wimage_fwd_api(d, &w);
+  return w.elems;
 }
 
 extern "C" int sv_conv2d_prep_weights(const sv_conv_desc* d, const float* w_hwio, void* w_fwd, void* w_dgrad,
@@ -682,58 +672,14 @@ extern "C" int sv_conv2d_prep_weights(const sv_conv_desc* d, const float* w_hwio
   int rc = svg_check(d);
   if (rc != SV_OK) return rc;
   if (!w_hwio) return SV_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  if (w_fwd && svg_polyc(d)) {
-    PrepJob j;
-    int64_t off = 0;
-    for (int c = 0; c < 4; ++c) {
-      svg_prep_job_polyc(d, c, &j);
-      j.dst_off = off;
-      rc = prep_single(w_hwio, w_fwd, d->dtype, j, st);
+  void* const image[2] = {w_fwd, w_dgrad};
+  for (int k = 0; k < 2; ++k) {
+    if (!image[k]) continue;
+    WImage w;
+    if (k) svg_wimage_dgrad(d, &w); else svg_wimage_fwd_api(d, &w);
+    for (int i = 0; i < w.n; ++i) {
+      rc = prep_single(w_hwio, image[k], d->dtype, w.part[i].job, (hipStream_t)stream);
       if (rc) return rc;
-      off += svg_polyc_class_elems(d, c);
-    }
-    svg_prep_job_polyc_fix(d, &j);
-    j.dst_off = off;
-    rc = prep_single(w_hwio, w_fwd, d->dtype, j, st);
-    if (rc) return rc;
-    svg_prep_job_fwd(d, &j);                             // the direct image (no-workspace forward)
-    j.dst_off = svg_polyc_direct_off(d);
-    rc = prep_single(w_hwio, w_fwd, d->dtype, j, st);
-    if (rc) return rc;
-  } else if (w_fwd) {
-    PrepJob j;
-    svg_prep_job_fwd(d, &j);
-    rc = prep_single(w_hwio, w_fwd, d->dtype, j, st);
-    if (rc) return rc;
-    if (svg_poly(d)) {                                   // the border-fix image follows the composite image
-      const int64_t main_elems = (int64_t)j.rows * j.ntaps * j.inner;
-      svg_prep_job_polyfix(d, &j);
-      j.dst_off = main_elems;
-      rc = prep_single(w_hwio, w_fwd, d->dtype, j, st);
-      if (rc) return rc;
-    }
-  }
-  if (w_dgrad) {
-    int64_t off = 0;
-    for (int c = 0; c < svg_dgrad_classes(d); ++c) {
-      PrepJob j;
-      svg_prep_job_dgrad(d, c, &j);
-      j.dst_off = off;
-      rc = prep_single(w_hwio, w_dgrad, d->dtype, j, st);
-      if (rc) return rc;
-      off += (int64_t)j.rows * j.ntaps * j.inner;
-    }
-    if (svg_polyd(d)) {
-      off = svg_polyd_base(d);
-      for (int which = 0; which < 3; ++which) {
-        PrepJob j;
-        svg_prep_job_polyd(d, which, &j);
-        j.dst_off = off;
-        rc = prep_single(w_hwio, w_dgrad, d->dtype, j, st);
-        if (rc) return rc;
-        off += svg_polyd_elems(d, which);
-      }
     }
   }
   return SV_OK;
@@ -747,19 +693,19 @@ extern "C" int64_t sv_conv2d_fwd_workspace_bytes(const sv_conv_desc* d) {
   return svg_poly(d) ? svk_poly_fix_ws_bytes(d->B, d->H / 2, d->W / 2) : 0;
 }
 
-// the four class problems + the border kernel of n <= 2 per-class polyphase layers (svg_polyc) of one geometry; w_fwd[i] = the image
-// sv_conv2d_prep_weights / the plan's jobs laid out (classes 0..3, then the border classes), fixws[i] = svg_polyc_fix_ws_bytes(d) bytes
+// the four class problems + the border kernel of n <= 2 per-class polyphase layers (svg_polyc) of one geometry; w_fwd[i] = a forward image
+// with the class parts (svg_wimage_fwd: they lead it, with or without the direct image), fixws[i] = svg_polyc_fix_ws_bytes(d) bytes
 int svk_polyc_fwd_multi(const sv_conv_desc* d, int n, const void* const* x, const void* const* w_fwd, const float* const* bias, void* const* y,
                         void* const* fixws, hipStream_t st) {
   if (n < 1 || n > 2) return SV_E_BADARG;
   const size_t esz = d->dtype == SV_BF16 ? 2 : 4;
   const int K = d->KH, nc = svg_polyc_nclass(K);
-  int64_t coff[5] = {0, 0, 0, 0, 0};
-  for (int c = 0; c < 4; ++c) coff[c + 1] = coff[c] + svg_polyc_class_elems(d, c);
+  WImage img;
+  svg_wimage_fwd(d, true, false, &img);
   const void* wfix[2];
   float *frow[2], *fcol[2];
   for (int i = 0; i < n; ++i) {
-    wfix[i] = (const char*)w_fwd[i] + coff[4] * esz;
+    wfix[i] = (const char*)w_fwd[i] + img.off(SV_WP_POLYC_FIX) * esz;
     frow[i] = (float*)fixws[i];
     fcol[i] = frow[i] + (int64_t)d->B * nc * d->W * d->Cout;
   }
@@ -770,7 +716,7 @@ int svk_polyc_fwd_multi(const sv_conv_desc* d, int n, const void* const* x, cons
     for (int c = 0; c < 4; ++c) {
       TapGemmArgs& t = a[i * 4 + c];
       svg_polyc_fwd_args(d, c, &t);
-      t.A = x[i]; t.Wt = (const char*)w_fwd[i] + coff[c] * esz; t.bias = bias ? bias[i] : nullptr; t.out = y[i];
+      t.A = x[i]; t.Wt = (const char*)w_fwd[i] + img.off(SV_WP_POLYC_CLASS, c) * esz; t.bias = bias ? bias[i] : nullptr; t.out = y[i];
       t.fix = frow[i]; t.fix2 = fcol[i];
     }
   return svk_conv_dispatch_multi(a, 4 * n, d->dtype, svg_pick_cfg(d->Cout), st);
@@ -795,9 +741,8 @@ bool svk_polyc_fwd_plannable(const sv_conv_desc* d) {
 // 128-row tiles of svg_pick_cfg leave most of the 256 CUs idle, 64 x 32 tiles (tap-GEMM cfg 4) give 8x the workgroups.
 static int svg_im2col_cfg(const TapGemmArgs& a, int cfg) {
   static const bool off = SV_TUNE_FLAG("SV_NO_SMALL_IM2COL");
-  static const int BMt[4] = {128, 128, 256, 256}, BNt[4] = {128, 64, 32, 16};
   if (off || cfg > 2 || (a.N % 32) || a.splitk > 1) return cfg;
-  const int64_t tiles = (int64_t)((a.M + BMt[cfg] - 1) / BMt[cfg]) * ((a.N + BNt[cfg] - 1) / BNt[cfg]);
+  const int64_t tiles = (int64_t)((a.M + svg_BMt[cfg] - 1) / svg_BMt[cfg]) * ((a.N + svg_BNt[cfg] - 1) / svg_BNt[cfg]);
   return tiles < 256 ? 4 : cfg;
 }
 
@@ -816,11 +761,13 @@ extern "C" int sv_conv2d_nhwc_fwd_ws(const sv_conv_desc* d, const void* x, const
   const bool polyc = svg_polyc(d);
   if (polyc && ws && ws_bytes >= svg_polyc_fix_ws_bytes(d))                    // the border terms travel through the workspace
     return svg_traced(svk_polyc_fwd_multi(d, 1, &x, &w_fwd, &bias, &y, &ws, (hipStream_t)stream), "fwd", "polyc");
+  const int64_t esz = d->dtype == SV_BF16 ? 2 : 4;
+  WImage img;
+  svg_wimage_fwd(d, polyc, true, &img);
   TapGemmArgs a;
   svg_fwd_args(d, &a);
-  a.A = x; a.Wt = w_fwd; a.bias = bias; a.out = y;
-  // (per-class polyphase layer without a workspace: the direct fused-resize form on the direct image sv_conv2d_prep_weights keeps behind the class images)
-  if (polyc) a.Wt = (const char*)w_fwd + svg_polyc_direct_off(d) * (int64_t)(d->dtype == SV_BF16 ? 2 : 4);
+  // (per-class polyphase layer without a workspace: the direct fused-resize form on the direct image the layout keeps behind the class images)
+  a.A = x; a.Wt = (const char*)w_fwd + img.off(SV_WP_FWD) * esz; a.bias = bias; a.out = y;
   if (!svg_poly(d)) {
     // dense layers (1x1 on a 1x1 grid) with an fp32 pre-activation output: a [B, Cin] x [Cin, Cout] GEMM whose tile grid is a
     // handful of workgroups (SPLIT-GMVAE's y_block / prior / posterior layers, vae/model.py:54-75) -- split K into the zeroed output
@@ -853,7 +800,7 @@ extern "C" int sv_conv2d_nhwc_fwd_ws(const sv_conv_desc* d, const void* x, const
     rc = svk_conv_dispatch(a, d->dtype, svg_im2col_cfg(a, svg_pick_cfg(d->Cout)), (hipStream_t)stream);
     return svg_traced(rc, "fwd", polyc ? "polyc_direct" : nullptr);
   }
-  const void* wfix = (const char*)w_fwd + (int64_t)32 * 25 * svg_cin_pad(d) * (d->dtype == SV_BF16 ? 2 : 4);
+  const void* wfix = (const char*)w_fwd + img.off(SV_WP_POLY_FIX) * esz;
   float* yf = (float*)y;
   float* fixbuf = ws && ws_bytes >= svk_poly_fix_ws_bytes(d->B, d->H / 2, d->W / 2) ? (float*)ws : nullptr;
   if (fixbuf) {
@@ -880,14 +827,13 @@ extern "C" int sv_conv2d_nhwc_dgrad(const sv_conv_desc* d, const void* dy, const
   if (dx_f32_atomic && relu_mask) return SV_E_BADARG;
   if (ilog2_exact(svg_gdy(d)) < 0) return SV_E_UNSUPPORTED;
   const size_t esz = d->dtype == SV_BF16 ? 2 : 4;
-  int64_t off = 0;
+  WImage img;
+  svg_wimage_dgrad(d, &img);
   sv_trace_note(nullptr);
   if (!dx_f32_atomic && svg_dgrad_classes(d) == 4) {      // classes with one shared window: one launch (cls_n)
-    int64_t coff[4] = {0, 0, 0, 0};
-    for (int c = 1; c < 4; ++c) coff[c] = coff[c - 1] + svg_wprep_elems_class(d, 1, c - 1);
     TapGemmArgs a;
-    if (svg_dgrad_merged_args(d, coff, &a)) {
-      a.A = dy; a.Wt = w_dgrad; a.out = dx; a.mask = relu_mask;
+    if (svg_dgrad_merged_args(d, &a)) {
+      a.A = dy; a.Wt = (const char*)w_dgrad + img.off(SV_WP_DGRAD_CLASS, 0) * esz; a.out = dx; a.mask = relu_mask;
       rc = svk_conv_dispatch(a, d->dtype, svg_pick_cfg(a.N), (hipStream_t)stream);
       if (rc != SV_E_UNSUPPORTED) return svg_traced(rc, "dgrad", "merged");
     }
@@ -896,13 +842,11 @@ extern "C" int sv_conv2d_nhwc_dgrad(const sv_conv_desc* d, const void* dy, const
     // the parity classes of a stride-2 layer as ONE launch (they plan to the same tile grid; lgvae_plan.hip: run_dgrad_layers does the same): SPLIT-GMVAE's 128-channel
     // encoder layers -- too wide for the merged form above -- went out as four launches of 32 / 128 workgroups each (4 x 21 + 4 x 36 us of its 64-image fp32 step)
     TapGemmArgs a[4];
-    int64_t o2 = 0;
     const int ncls = svg_dgrad_classes(d);
     for (int c = 0; c < ncls; ++c) {
       uint8_t srctap[SV_MAX_TAPS];
       svg_dgrad_args(d, c, &a[c], srctap);
-      a[c].A = dy; a[c].Wt = (const char*)w_dgrad + o2 * esz; a[c].out = dx; a[c].mask = relu_mask;
-      o2 += svg_wprep_elems_class(d, 1, c);
+      a[c].A = dy; a[c].Wt = (const char*)w_dgrad + img.off(SV_WP_DGRAD_CLASS, c) * esz; a[c].out = dx; a[c].mask = relu_mask;
     }
     rc = svk_conv_dispatch_multi(a, ncls, d->dtype, svg_im2col_cfg(a[0], svg_pick_cfg(d->Cin)), (hipStream_t)stream);
     if (rc != SV_E_UNSUPPORTED) return svg_traced(rc, "dgrad", "multi_class");
@@ -911,7 +855,7 @@ extern "C" int sv_conv2d_nhwc_dgrad(const sv_conv_desc* d, const void* dy, const
     TapGemmArgs a;
     uint8_t srctap[SV_MAX_TAPS];
     svg_dgrad_args(d, c, &a, srctap);
-    a.A = dy; a.Wt = (const char*)w_dgrad + off * esz; a.out = dx; a.mask = relu_mask;
+    a.A = dy; a.Wt = (const char*)w_dgrad + img.off(SV_WP_DGRAD_CLASS, c) * esz; a.out = dx; a.mask = relu_mask;
     int cfg = svg_pick_cfg(d->Cin);
     if (dx_f32_atomic) {
       a.out_f32 = 1;
@@ -920,7 +864,6 @@ extern "C" int sv_conv2d_nhwc_dgrad(const sv_conv_desc* d, const void* dy, const
     } else cfg = svg_im2col_cfg(a, cfg);
     rc = svk_conv_dispatch(a, d->dtype, cfg, (hipStream_t)stream);
     if (rc) return rc;
-    off += svg_wprep_elems_class(d, 1, c);
   }
   return svg_traced(SV_OK, "dgrad", dx_f32_atomic ? "atomic_splitk" : "per_class");
 }
@@ -955,10 +898,8 @@ extern "C" int sv_conv2d_nhwc_dgrad_lowres_ws(const sv_conv_desc* d, const void*
   int rc = svg_check(d);
   if (rc != SV_OK) return rc;
   if (!dy || !w_dgrad || !dx_lo) return SV_E_BADARG;
-  if (svg_polyd(d) && workspace && workspace_bytes >= svg_polyd_ws_bytes(d)) {
-    const void* wp = (const char*)w_dgrad + svg_polyd_base(d) * (d->dtype == SV_BF16 ? 2 : 4);
-    return svg_traced(svk_polyd_dgrad_multi(d, 1, &dy, &wp, &relu_mask_lo, &dx_lo, &workspace, (hipStream_t)stream), "dgrad_lowres", "lowres_polyd");
-  }
+  if (svg_polyd(d) && workspace && workspace_bytes >= svg_polyd_ws_bytes(d))
+    return svg_traced(svk_polyd_dgrad_multi(d, 1, &dy, &w_dgrad, &relu_mask_lo, &dx_lo, &workspace, (hipStream_t)stream), "dgrad_lowres", "lowres_polyd");
   return sv_conv2d_nhwc_dgrad_lowres(d, dy, w_dgrad, relu_mask_lo, dx_lo, stream);
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <stdlib.h>
 #include <string.h>
+#include <vector>
 #include "../../include/splitvae.h"
 #include "kernels.h"
 #include "common.hip.h"
@@ -93,7 +94,6 @@ static inline __host__ __device__ bool svg_polyc_excl(int K, int c, int k) {
   const int below = K - 1 - pad - (c - pad);                          // rows from Y to the last row, inclusive (nb .. 1)
   return k > below - 1 + pad;                                         // Y + k - pad > 2h - 1  <=>  k > (2h - 1 - Y) + pad, 2h - 1 - Y = below - 1
 }
-#define SV_POLY_FIX_ELEMS(cin) (10 * 6 * 16 * (cin))                 // [10 border classes][6 taps][16 columns][Cin]
 // SPACE-TO-DEPTH form of the first encoder layer at fp32 (e1: Conv2D(32, 6, strides 2) over RGB, vae/model.py:36).  The padded 8-channel pixels make 62 % of every
 // fp32 MFMA zeros (3 of 8 channels: K = 36 x 8 = 288 for 108 real products).  Input row 2 oy + ky - 2 = 2 (oy + t) + py with t in {-1, 0, 1}: over the space-to-depth view
 // [B, H/2, W/2, (py, px, c)] the layer is a 3 x 3 stride-1 SAME conv with 12 (padded to 16) channels: K = 9 x 16 = 144, half the MFMAs, and the stride-1 tile path.  The
@@ -110,6 +110,10 @@ static inline int svg_pick_cfg(int N) {
   if (N % 32 == 0) return 2;
   return 3;
 }
+// rows x columns of the tap GEMM's tile, by svg_pick_cfg
+static const int svg_BMt[4] = {128, 128, 256, 256}, svg_BNt[4] = {128, 64, 32, 16};
+// rows of a prepared image with n real ones: whole N tiles
+static inline int svg_rows_pad(int n) { const int t = svg_BNt[svg_pick_cfg(n)]; return (n + t - 1) / t * t; }
 // Position of filter tap (kh, kw) in the K order of the forward weight image / tap tables.  Stride-1 layers run
 // x-major, y-minor (t = kw*KH + kh): the KH taps of one filter column are consecutive, which is what the row-window
 // reuse of the tile kernel (tile_conv.hip, YR) walks.  Stride 2 keeps the HWIO order.
@@ -120,10 +124,9 @@ static inline int svg_fwd_tap(const sv_conv_desc* d, int kh, int kw) {
 // tap-GEMM tile: a split-K problem on 128-column tiles drops to 64 columns (twice the workgroups for
 // the same number of atomic passes; prepared weight rows are padded to 128, so either tile fits).
 static inline int svg_choose_splitk(int M, int N, int nk, int* cfg_io = nullptr) {
-  static const int BMt[4] = {128, 128, 256, 256}, BNt[4] = {128, 64, 32, 16};
   static const bool narrow = !SV_TUNE_FLAG("SV_SPLITK_NO_NARROW");
   int cfg = svg_pick_cfg(N);
-  int tiles = ((M + BMt[cfg] - 1) / BMt[cfg]) * ((N + BNt[cfg] - 1) / BNt[cfg]);
+  int tiles = ((M + svg_BMt[cfg] - 1) / svg_BMt[cfg]) * ((N + svg_BNt[cfg] - 1) / svg_BNt[cfg]);
   if (tiles >= 128) return 1;
   if (sv_deterministic()) return 1;        // one workgroup per output tile: a single add per element, whatever the launch order
   static const bool small = !SV_TUNE_FLAG("SV_SPLITK_NO_SMALL");   // 64 x 32 tiles (tap-GEMM cfg 4): +0.8 % on the step; knob restores 128 x 64
@@ -150,9 +153,13 @@ static inline int svg_choose_splitk(int M, int N, int nk, int* cfg_io = nullptr)
 #else
 #define SV_PREP_UNITS 2      // re-measured (round 2): 8 -> 2 takes the weight preparation from 39 to 29 us (more workgroups in flight)
 #endif
+// elements a job writes: [rows][ntaps][inner], the border-class image of a per-class polyphase layer once per border class
+static inline int64_t svg_prep_job_elems(const PrepJob* j) {
+  return (int64_t)j->rows * j->ntaps * j->inner * (j->poly == SV_PREP_POLYC_FIX ? 2 * (j->pk - 1) : 1);
+}
 static inline int svg_prep_nblocks(const PrepJob* j) {
   int64_t units;
-  if (j->packx_kw) units = ((int64_t)j->rows * j->ntaps * j->inner + 255) / 256;
+  if (j->packx_kw || j->poly || j->s2d3) units = (svg_prep_job_elems(j) + 255) / 256;        // one element per thread
   else if (!j->transpose) units = (int64_t)j->ntaps * ((j->rows + 63) / 64) * ((j->inner + 63) / 64);
   else if (j->transpose && !(j->inner & 7) && !(j->Cout & 7) && !(j->inner_off & 7) && !(j->inner_ld & 7))
     units = ((int64_t)j->rows * j->ntaps * (j->inner >> 3) + 255) / 256;          // 8 channels per thread
@@ -160,24 +167,70 @@ static inline int svg_prep_nblocks(const PrepJob* j) {
   return (int)((units + SV_PREP_UNITS - 1) / SV_PREP_UNITS);
 }
 
+// LAYOUT OF A PREPARED WEIGHT IMAGE: its parts, in order, each with its element offset from the image's start and the job that writes it.  The forward
+// image (svg_wimage_fwd) and the input-gradient image (svg_wimage_dgrad) of a descriptor are described HERE ONLY: sv_conv2d_wprep_elems,
+// sv_conv2d_prep_weights, the dispatchers and the arenas of the plan, the tape and the SPLIT-GMVAE encoder all read this table, and off() is the only
+// way a consumer obtains an offset.
+enum {
+  SV_WP_FWD,            // forward main: the direct, x-packed (svg_packx), space-to-depth (svg_s2d3) or composite polyphase (svg_poly) image
+  SV_WP_POLY_FIX,       // border-fix image of the polyphase head (svg_poly), behind its composite image
+  SV_WP_POLYC_CLASS,    // per-class polyphase (svg_polyc): class image cls = py*2 + px, each from a 128-element boundary
+  SV_WP_POLYC_FIX,      // ... and its border-class image
+  SV_WP_DGRAD_CLASS,    // input gradient: image of parity class cls (svg_dgrad_classes), back to back
+  SV_WP_POLYD_MAIN, SV_WP_POLYD_EDGE, SV_WP_POLYD_CORNER   // polyphase input gradient (svg_polyd), from the next 128-element boundary behind the classes
+};
+struct WImagePart { int role, cls; int64_t off, elems; PrepJob job; };     // off, elems: elements of dtype; job.dst_off = off, job.src_off = 0
+struct WImage {
+  int n;
+  int64_t elems;
+  WImagePart part[12];                                                     // (stride 3: nine classes; svg_polyd has one class and three parts)
+  const WImagePart* find(int role, int cls = 0) const {
+    for (int i = 0; i < n; ++i)
+      if (part[i].role == role && part[i].cls == cls) return &part[i];
+    return nullptr;
+  }
+  int64_t off(int role, int cls = 0) const { return find(role, cls)->off; }   // (a part the image has)
+};
+// forward image.  polyc_classes: the per-class polyphase form (classes, fix); direct: ... and, 128-element aligned behind them, the direct (fused-resize)
+// image.  Without polyc_classes: the direct image alone (with the border-fix image of a svg_poly head).
+void svg_wimage_fwd(const sv_conv_desc* d, bool polyc_classes, bool direct, WImage* w);
+void svg_wimage_dgrad(const sv_conv_desc* d, WImage* w);
+// The forward image of the stand-alone API, which the tape and the SPLIT-GMVAE encoder prepare too (they run their layers through sv_conv2d_nhwc_fwd): a
+// svg_polyc layer keeps both forms -- the forward takes the class form with a workspace for the border terms and the direct form without.  (The plan
+// latches one form at creation instead: (true, false) where svk_polyc_fwd_plannable, (false, -) otherwise.)
+static inline void svg_wimage_fwd_api(const sv_conv_desc* d, WImage* w) { svg_wimage_fwd(d, svg_polyc(d) != 0, true, w); }
+
+// the weight arena of a plan: images placed one behind the other from 128-element boundaries, their jobs appended to one table (svk_prep_weights)
+struct PrepArena {
+  int64_t elems = 0;
+  int blocks = 0;
+  std::vector<PrepJob> jobs;
+  void align() { elems = (elems + 127) / 128 * 128; }
+  void push(PrepJob j) { j.first_block = blocks; blocks += j.nblocks; jobs.push_back(j); }
+  int64_t place(const WImage& w, int64_t src_off) {         // -> the image's base; src_off: its HWIO master in the parameter buffer
+    align();
+    const int64_t base = elems;
+    for (int i = 0; i < w.n; ++i) {
+      PrepJob j = w.part[i].job;
+      j.src_off = src_off; j.dst_off += base;
+      push(j);
+    }
+    elems = base + w.elems;
+    return base;
+  }
+};
+
 int svg_check(const sv_conv_desc* d);
 void svg_fwd_args(const sv_conv_desc* d, TapGemmArgs* a);
 int svg_dgrad_classes(const sv_conv_desc* d);
 void svg_dgrad_args(const sv_conv_desc* d, int cls, TapGemmArgs* a, uint8_t srctap[SV_MAX_TAPS]);
-bool svg_dgrad_merged_args(const sv_conv_desc* d, const int64_t* class_off, TapGemmArgs* a);   // all 4 classes as one problem
+bool svg_dgrad_merged_args(const sv_conv_desc* d, TapGemmArgs* a);   // all 4 classes as one problem
 void svg_wgrad_args(const sv_conv_desc* d, WgradArgs* a, bool plain = false);   // plain: the direct HWIO form, no space-to-depth / x-packed view
 void svg_poly_wgrad_args(const sv_conv_desc* d, WgradArgs* a);      // main term of the polyphase weight gradient (svg_poly layers)
 #define SV_POLY_WGRAD_NWG 256
 void svg_wgrad_set_msplit(WgradArgs* a, int cfg, int dtype, int target_wgs);
-void svg_prep_job_fwd(const sv_conv_desc* d, PrepJob* j);
-void svg_prep_job_dgrad(const sv_conv_desc* d, int cls, PrepJob* j);
-void svg_prep_job_polyfix(const sv_conv_desc* d, PrepJob* j);     // second forward job of a svg_poly layer (follows the main image)
-// per-class polyphase (svg_polyc): forward problem of class cls = py*2 + px; its composite-weight image; the border-class image; element counts
+// per-class polyphase (svg_polyc): forward problem of class cls = py*2 + px; the workspace of its border terms
 void svg_polyc_fwd_args(const sv_conv_desc* d, int cls, TapGemmArgs* a);
-void svg_prep_job_polyc(const sv_conv_desc* d, int cls, PrepJob* j);
-void svg_prep_job_polyc_fix(const sv_conv_desc* d, PrepJob* j);
-int64_t svg_polyc_class_elems(const sv_conv_desc* d, int cls);
-int64_t svg_polyc_fix_elems(const sv_conv_desc* d);
 int64_t svg_polyc_fix_ws_bytes(const sv_conv_desc* d);
 // POLYPHASE INPUT GRADIENT of an upsample -> conv layer, delivered at the LOW-RES tensor (ResizeBilinearGrad o Conv2DBackpropInput o ReluGrad in one pass;
 // polyd_dgrad.hip, tests/test_polyphase_math.py).  The transposed per-class polyphase conv reads dy[2(i'-ty)+py, 2(j'-tx)+px] for (class, offset) pairs: every
@@ -228,10 +281,8 @@ static inline __host__ __device__ void svg_polyd_kpm(int K, int hi_edge, int q, 
 }
 static inline int svg_polyd_cop(const sv_conv_desc* d) { const int g = svg_gdy(d), m = d->dtype == SV_BF16 ? 32 : 16; return g < m ? m : g; }   // dY channels per edge operand (padded to one MFMA group)
 void svg_polyd_args(const sv_conv_desc* d, TapGemmArgs* a);
-void svg_prep_job_polyd(const sv_conv_desc* d, int which, PrepJob* j);          // which: 0 main, 1 edges, 2 corners
-int64_t svg_polyd_elems(const sv_conv_desc* d, int which);                      // (128-element aligned)
 int64_t svg_polyd_ws_bytes(const sv_conv_desc* d);                              // row terms [B][2][w][Cin] + column terms [B][h][2][Cin], fp32
-int svk_polyd_dgrad_multi(const sv_conv_desc* d, int n, const void* const* dy, const void* const* w_polyd, const void* const* mask_lo, void* const* dx_lo,
+int svk_polyd_dgrad_multi(const sv_conv_desc* d, int n, const void* const* dy, const void* const* w_dgrad, const void* const* mask_lo, void* const* dx_lo,
                           void* const* edgews, hipStream_t st);
 // polyphase weight gradient at fp32 (polyc_wgrad.hip): 0 none, 1 per class (svg_polyc), 2 merged head (svg_poly); workspace floats per problem; class problem
 int svg_polyc_wgrad_form(const sv_conv_desc* d);
@@ -243,4 +294,3 @@ int svk_polyc_wgrad_multi(const sv_conv_desc* d, int n, const void* const* x_lo,
 bool svk_polyc_fwd_plannable(const sv_conv_desc* d);
 int svk_polyc_fwd_multi(const sv_conv_desc* d, int n, const void* const* x, const void* const* w_fwd, const float* const* bias, void* const* y,
                         void* const* fixws, hipStream_t st);
-int64_t svg_wprep_elems_class(const sv_conv_desc* d, int for_dgrad, int cls);

@@ -171,31 +171,18 @@ extern "C" int sv_gm_encoder_create(const sv_gm_desc* d, sv_gm_encoder** out) {
   for (int l = 0; l < NLAYER; ++l)
     if ((rc = svg_check(&e->conv[l])) != SV_OK) { delete e; return rc; }
 
-  // weight-preparation jobs: one launch re-lays all 24 images per step (layout of sv_conv2d_prep_weights: the classes of
-  // an input-gradient image are contiguous)
-  int64_t arena = 0;
-  int blocks = 0;
-  auto push = [&](PrepJob j) { j.first_block = blocks; blocks += j.nblocks; e->jobs.push_back(j); };
+  // weight-preparation jobs: one launch re-lays all 24 images per step (the images of sv_conv2d_prep_weights, from the same layout table: conv_geom.h)
+  PrepArena ar;
   for (int l = 0; l < NLAYER; ++l) {
-    PrepJob j;
-    svg_prep_job_fwd(&e->conv[l], &j);
-    j.src_off = e->params[2 * l].off;
-    arena = (arena + 127) / 128 * 128;
-    e->wf_off[l] = arena; j.dst_off = arena;
-    arena += (int64_t)j.rows * j.ntaps * j.inner;
-    push(j);
-    arena = (arena + 127) / 128 * 128;
-    e->wd_off[l] = arena;
-    for (int c = 0; c < svg_dgrad_classes(&e->conv[l]); ++c) {
-      PrepJob jd;
-      svg_prep_job_dgrad(&e->conv[l], c, &jd);
-      jd.src_off = e->params[2 * l].off;
-      jd.dst_off = arena;
-      arena += (int64_t)jd.rows * jd.ntaps * jd.inner;
-      push(jd);
-    }
+    WImage w;
+    svg_wimage_fwd_api(&e->conv[l], &w);
+    e->wf_off[l] = ar.place(w, e->params[2 * l].off);
+    svg_wimage_dgrad(&e->conv[l], &w);
+    e->wd_off[l] = ar.place(w, e->params[2 * l].off);
   }
-  e->prep_blocks = blocks;
+  const int64_t arena = ar.elems;
+  e->prep_blocks = ar.blocks;
+  e->jobs = std::move(ar.jobs);
 
   const int64_t es = (int64_t)e->esz(), Kp = e->Kp;
   const int64_t P1 = (int64_t)B * (H / 2) * (H / 2) * 128, P2 = (int64_t)B * (H / 4) * (H / 4) * 128, BF = (int64_t)B * F;

@@ -242,6 +242,16 @@ bool svk_tn_wgrad_supported(const TnWgradProb& p);
 int svk_tn_wgrad_multi(const TnWgradProb* p, int n, hipStream_t st);
 
 // ---- batched weight preparation (fp32 HWIO master -> MFMA-ready images), job table in device memory
+// PrepJob::poly (the device code compares the numbers: they do not change)
+enum {
+  SV_PREP_POLY_MAIN = 1,     // polyphase forward image of (2x bilinear upsample -> 6x6 conv) [32][25][Cin] (conv_geom.h: svg_poly)
+  SV_PREP_POLY_FIX = 2,      // its border-fix image [10 classes][6 taps][16][Cin]
+  SV_PREP_POLYC_CLASS = 3,   // per-class polyphase image [rows][nty*ntx (x-major)][Cin] of class pcls of a pk x pk kernel (conv_geom.h: svg_polyc)
+  SV_PREP_POLYC_FIX = 4,     // its border-class image [2*(pk-1) classes][pk taps][rows][Cin] = -(sum over the taps that leave the image)
+  SV_PREP_POLYD_MAIN = 5,    // main image of the polyphase INPUT gradient [rows = ci][(2R+1)^2 hi-res taps (x-major)][co] (conv_geom.h: svg_polyd)
+  SV_PREP_POLYD_EDGE = 6,    // its edge images [4 edges: top, bottom, left, right][4 rows from the edge][2R+1][ci][co]
+  SV_PREP_POLYD_CORNER = 7   // its corner images [4 corners][4][4][ci][co]
+};
 struct PrepJob {
   int64_t src_off;     // element offset into the flat fp32 parameter buffer
   int64_t dst_off;     // element offset (of dtype) into the prepared-weight arena
@@ -252,13 +262,8 @@ struct PrepJob {
   int32_t transpose;   // 0: rows=co, inner=ci (forward); 1: rows=ci, inner=co (dgrad)
   int32_t packx_kw;    // > 0: forward image of the x-packed conv of a KH x packx_kw kernel: row n = px*8 + co,
                        // tap (ky, tx) of KH x (KW+1) <- source tap (ky, tx - px), zero outside the kernel
-  int32_t poly;        // 1: polyphase forward image of (2x bilinear upsample -> 6x6 conv) [32][25][Cin]; 2: its border-fix image
-                       // [10 classes][6 taps][16][Cin] (conv_api.hip: prep_poly)
-                       // 3: per-class polyphase image [rows][nty*ntx (x-major)][Cin] of class pcls of a pk x pk kernel (conv_geom.h: svg_polyc)
-                       // 4: its border-class image [2*(pk-1) classes][pk taps][rows][Cin] = -(sum over the taps that leave the image)
-                       // 5: main image of the polyphase INPUT gradient [rows = ci][(2R+1)^2 hi-res taps (x-major)][co]; 6: its edge images
-                       // [4 edges: top, bottom, left, right][4 rows from the edge][2R+1][ci][co]; 7: its corner images [4 corners][4][4][ci][co] (conv_geom.h: svg_polyd)
-  int32_t pk, pcls;    // poly 3 .. 7: kernel size; poly 3: parity class py*2 + px
+  int32_t poly;        // 0 or a SV_PREP_POLY* value (below): the polyphase image this job forms
+  int32_t pk, pcls;    // SV_PREP_POLYC_CLASS .. SV_PREP_POLYD_CORNER: kernel size; SV_PREP_POLYC_CLASS: parity class py*2 + px
   int32_t s2d3;        // forward image of the space-to-depth form (svg_s2d3): [co][t = tx*3 + ty][16] <- the 6 x 6 x 3 master
   int32_t first_block; // first block of this job in the launch
   int32_t nblocks;

@@ -133,9 +133,11 @@ struct Layer {
   int polycw = -1;              // dec[][2 .. 4]: the TWIN id of its polyphase weight-gradient workspace (POLYCW2 ..), which the plan may lack; and its bit in polycw_bad
   sv_conv_desc d;
   int kparam, bparam;           // indices into the param table (kernel, bias); head uses two kernels
-  int64_t wf_off;               // prepared forward weights (element offset in arena)
-  int64_t wd_off[4];            // prepared dgrad weights per parity class
-  int64_t wdp_off;              // polyphase input gradient (svg_polyd): main / edge / corner images, or -1
+  // element offsets in the arena, filled from the layout table (conv_geom.h: WImage) when the images are placed (build_prep_jobs)
+  int64_t wf_off;               // forward image
+  int64_t wfix_off;             // border-fix image of the polyphase head (svg_poly), or -1
+  int64_t wd_off[4];            // input-gradient image: per parity class (wd_off[0] = the image's base)
+  bool polyd;                   // the input-gradient image has the polyphase parts (svg_polyd: main / edge / corner), LATCHED like polyc
   bool need_dgrad;
   bool polyc;                   // forward in per-class polyphase form (conv_geom.h: svg_polyc), LATCHED when the plan is created: the arena then holds the class images
                                 // only, and a later change of the tuning environment must not send the direct kernel to them
@@ -406,7 +408,7 @@ static void build_layers(sv_lgvae_plan* p) {
     L.ln = name; L.sc_fwd = "fwd." + name; L.sc_dgrad = "dgrad." + name; L.sc_wgrad = "wgrad." + name; L.sc_reduce = L.sc_wgrad + ".reduce";
     L.d = sv_conv_desc{B, h, w, cin, cout, k, k, s, act, d.dtype, ldx, ldy, yf32, 0};
     L.kparam = kparam; L.bparam = kparam + 1; L.need_dgrad = need_dgrad;
-    L.wf_off = 0; L.wdp_off = -1; L.polyc = false;
+    L.wf_off = 0; L.wfix_off = -1; L.polyd = false; L.polyc = false;
     for (int i = 0; i < 4; ++i) L.wd_off[i] = 0;
     return L;
   };
@@ -438,107 +440,60 @@ static void build_layers(sv_lgvae_plan* p) {
 }
 
 static void build_prep_jobs(sv_lgvae_plan* p) {
-  int64_t arena = 0;
-  int blocks = 0;
-  auto push = [&](PrepJob j) {
-    j.first_block = blocks;
-    blocks += j.nblocks;
-    p->jobs.push_back(j);
-  };
-  auto align = [&]() { arena = (arena + 127) / 128 * 128; };
-  auto polyd_jobs = [&](Layer& L) {                       // polyphase input gradient (conv_geom.h: svg_polyd): main, edge and corner images
-    if (!L.need_dgrad || !svg_polyd(&L.d)) return;
-    align(); L.wdp_off = arena;
-    for (int which = 0; which < 3; ++which) {
-      PrepJob j;
-      svg_prep_job_polyd(&L.d, which, &j);
-      j.src_off = p->params[L.kparam].off; j.dst_off = arena;
-      arena += svg_polyd_elems(&L.d, which);
-      push(j);
-    }
-  };
+  PrepArena ar;
   auto do_layer = [&](Layer& L, bool is_head) {
-    L.polyc = !is_head && svg_polyc(&L.d) && svk_polyc_fwd_plannable(&L.d);     // (the class problems must plan on the tile kernel: else the direct form is prepared)
-    if (L.polyc) {
-      // per-class polyphase forward (conv_geom.h: svg_polyc): four class images + the border-class image, contiguous from wf_off in the
-      // order svk_polyc_fwd_multi expects; the input / weight gradients keep their own forms
-      align(); L.wf_off = arena;
-      for (int c = 0; c < 4; ++c) {
-        PrepJob j;
-        svg_prep_job_polyc(&L.d, c, &j);
-        j.src_off = p->params[L.kparam].off; j.dst_off = arena;
-        arena += svg_polyc_class_elems(&L.d, c);
-        push(j);
-      }
-      PrepJob jf;
-      svg_prep_job_polyc_fix(&L.d, &jf);
-      jf.src_off = p->params[L.kparam].off; jf.dst_off = arena;
-      arena += svg_polyc_fix_elems(&L.d);
-      push(jf);
-    } else if (!is_head) {
-      PrepJob j;
-      svg_prep_job_fwd(&L.d, &j);
-      j.src_off = p->params[L.kparam].off;
-      align(); L.wf_off = arena; j.dst_off = arena;
-      arena += (int64_t)j.rows * j.ntaps * j.inner;
-      push(j);
-      if (svg_poly(&L.d)) {                             // border-fix image of the polyphase head, right behind the composite image
-        PrepJob jf;
-        svg_prep_job_polyfix(&L.d, &jf);
-        jf.src_off = p->params[L.kparam].off;
-        jf.dst_off = arena;
-        arena += (int64_t)jf.rows * jf.ntaps * jf.inner;
-        push(jf);
-      }
-    }
-    if (!is_head) {                                       // the input gradient keeps its own forms whichever forward image was prepared
-      if (L.need_dgrad)
-        for (int c = 0; c < svg_dgrad_classes(&L.d); ++c) {
-          PrepJob jd;
-          svg_prep_job_dgrad(&L.d, c, &jd);
-          jd.src_off = p->params[L.kparam].off;
-          align(); L.wd_off[c] = arena; jd.dst_off = arena;
-          arena += (int64_t)jd.rows * jd.ntaps * jd.inner;
-          push(jd);
-        }
-      polyd_jobs(L);
+    if (!is_head) {
+      // per-class polyphase forward (conv_geom.h: svg_polyc) where the class problems plan on the tile kernel, else the direct form; the input / weight
+      // gradients keep their own forms whichever forward image was prepared
+      L.polyc = svg_polyc(&L.d) && svk_polyc_fwd_plannable(&L.d);
+      const int64_t src = p->params[L.kparam].off;
+      WImage w;
+      svg_wimage_fwd(&L.d, L.polyc, false, &w);
+      L.wf_off = ar.place(w, src);
+      if (const WImagePart* fix = w.find(SV_WP_POLY_FIX)) L.wfix_off = L.wf_off + fix->off;
+      if (!L.need_dgrad) return;
+      svg_wimage_dgrad(&L.d, &w);
+      const int64_t base = ar.place(w, src);
+      for (int c = 0; c < svg_dgrad_classes(&L.d); ++c) L.wd_off[c] = base + w.off(SV_WP_DGRAD_CLASS, c);
+      L.polyd = w.find(SV_WP_POLYD_MAIN) != nullptr;
     } else {
       // two Keras tensors [F,L] (mean at kparam, sd at kparam+2) -> one [2L][F] forward image
       // and one [F][2L] dgrad image
       const int F = L.d.Cin, L2 = L.d.Cout, Lh = L2 / 2;
-      align(); L.wf_off = arena;
+      ar.align(); L.wf_off = ar.elems;
       for (int h = 0; h < 2; ++h) {
         PrepJob j;
         memset(&j, 0, sizeof(j));
         j.src_off = p->params[L.kparam + 2 * h].off;
         j.ntaps = 1; j.Cin = F; j.Cout = Lh; j.rows = Lh; j.inner = F; j.inner_ld = F; j.inner_off = 0;
         j.transpose = 0; j.srctap[0] = 0;
-        j.dst_off = arena + (int64_t)h * Lh * F;
+        j.dst_off = ar.elems + (int64_t)h * Lh * F;
         j.nblocks = svg_prep_nblocks(&j);
-        push(j);
+        ar.push(j);
       }
-      arena += (int64_t)L2 * F;
-      align(); L.wd_off[0] = arena;
+      ar.elems += (int64_t)L2 * F;
+      ar.align(); L.wd_off[0] = ar.elems;
       for (int h = 0; h < 2; ++h) {
         PrepJob j;
         memset(&j, 0, sizeof(j));
         j.src_off = p->params[L.kparam + 2 * h].off;
         j.ntaps = 1; j.Cin = F; j.Cout = Lh; j.rows = F; j.inner = Lh; j.inner_ld = L2; j.inner_off = h * Lh;
         j.transpose = 1; j.srctap[0] = 0;
-        j.dst_off = arena;
+        j.dst_off = ar.elems;
         j.nblocks = svg_prep_nblocks(&j);
-        push(j);
+        ar.push(j);
       }
-      arena += (int64_t)F * L2;
+      ar.elems += (int64_t)F * L2;
     }
   };
   for (int e = 0; e < 2 && !p->d.global_only; ++e)
     for (int l = 0; l < 4; ++l) do_layer(p->enc[e][l], l == 3);
-  p->dec_block0 = blocks;
+  p->dec_block0 = ar.blocks;
   for (int k = 0; k < p->ndec(); ++k)
     for (int l = 0; l < 5; ++l) do_layer(p->dec[k][l], false);
-  p->arena_elems = arena + 128;
-  p->prep_blocks = blocks;
+  p->arena_elems = ar.elems + 128;
+  p->prep_blocks = ar.blocks;
+  p->jobs = std::move(ar.jobs);
 }
 
 // sizes by id; LGVAE_BUFFERS gives the positions (the order of the statements here gives nothing)
@@ -731,7 +686,7 @@ static int run_fwd_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void* 
     float* const* fixbuf = p->fpair(POLYFIX);
     const sv_conv_desc& d = L[0]->d;
     for (int i = 0; i < n; ++i) {
-      wfix[i] = (const char*)a[i].Wt + (int64_t)32 * 25 * svg_cin_pad(&L[i]->d) * p->esz();
+      wfix[i] = (const char*)p->buf(WARENA) + L[i]->wfix_off * p->esz();
       a[i].fix = fixbuf[i];
     }
     SV_TRY(svk_poly_fix_multi(n, x, wfix, nullptr, fixbuf, d.B, d.H / 2, d.W / 2, d.ldx, d.Cout, st, d.dtype));
@@ -751,7 +706,7 @@ static int run_dgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
   if (!adj && !f32_atomic && ncls == 4) {              // classes that share one dY window (e2): one problem per network
     bool ok = true;
     for (int i = 0; i < n && ok; ++i) {
-      ok = svg_dgrad_merged_args(&L[i]->d, L[i]->wd_off, &a[i]);
+      ok = svg_dgrad_merged_args(&L[i]->d, &a[i]);
       a[i].A = dy[i]; a[i].Wt = (char*)p->buf(WARENA) + L[i]->wd_off[0] * p->esz(); a[i].out = dx[i]; a[i].mask = mask[i];
       fl += conv_flops(L[i]->d);
     }
@@ -1121,12 +1076,12 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
     //  default moved from 256 to 128)
     static const int adj_min = SV_TUNE_INT("SV_RC_ADJ_MIN", 128);
     int frc = SV_E_UNSUPPORTED;
-    if (Ls[0]->wdp_off >= 0 && (nd == 1 || Ls[1]->wdp_off >= 0)) {
+    if (Ls[0]->polyd && (nd == 1 || Ls[1]->polyd)) {
       // fp32: the polyphase form (polyd_dgrad.hip): conv-transpose + resize adjoint + ReLU gate as one stride-2 conv over dY, edge terms through a workspace
       const void* wp[2];
       double fl = 0, by = 0;
       for (int k = 0; k < nd; ++k) {
-        wp[k] = (const char*)p->buf(WARENA) + Ls[k]->wdp_off * p->esz();
+        wp[k] = (const char*)p->buf(WARENA) + Ls[k]->wd_off[0] * p->esz();
         fl += conv_flops(Ls[k]->d); by += conv_bytes(Ls[k]->d, 1, p->esz());
       }
       Scope sc(p, st, Ls[0]->sc_dgrad, fl, by);

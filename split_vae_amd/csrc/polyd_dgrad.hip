@@ -191,19 +191,20 @@ static int launch_edge(const PolydEdgeMulti& m, int n, int B, int h, int w, int 
 }  // namespace
 
 // n <= 2 twin layers: edge + corner terms into edgews[i] (svg_polyd_ws_bytes), then the main stride-2 conv whose epilogue adds them and applies the ReLU
-// gate of the low-res activation mask_lo[i] (may be null).  w_polyd[i]: the main / edge / corner images (svg_prep_job_polyd 0, 1, 2 back to back).
-int svk_polyd_dgrad_multi(const sv_conv_desc* d, int n, const void* const* dy, const void* const* w_polyd, const void* const* mask_lo, void* const* dx_lo,
+// gate of the low-res activation mask_lo[i] (may be null).  w_dgrad[i]: the layer's input-gradient image (svg_wimage_dgrad), whose main / edge / corner parts are read.
+int svk_polyd_dgrad_multi(const sv_conv_desc* d, int n, const void* const* dy, const void* const* w_dgrad, const void* const* mask_lo, void* const* dx_lo,
                           void* const* edgews, hipStream_t st) {
   if (!svg_polyd(d) || n < 1 || n > 2) return SV_E_UNSUPPORTED;
   const size_t esz = d->dtype == SV_BF16 ? 2 : 4;
   const int h = d->H / 2, w = d->W / 2, cin = svg_cin_pad(d), gdy = svg_gdy(d), cop = svg_polyd_cop(d), K = d->KH;
-  const int64_t o1 = svg_polyd_elems(d, 0), o2 = o1 + svg_polyd_elems(d, 1);
+  WImage img;
+  svg_wimage_dgrad(d, &img);
   PolydEdgeMulti m;
   TapGemmArgs a[2];
   for (int i = 0; i < 2; ++i) {
     const int k = i < n ? i : 0;
     m.dy[i] = dy[k];
-    m.wedge[i] = (const char*)w_polyd[k] + o1 * esz; m.wcorner[i] = (const char*)w_polyd[k] + o2 * esz;
+    m.wedge[i] = (const char*)w_dgrad[k] + img.off(SV_WP_POLYD_EDGE) * esz; m.wcorner[i] = (const char*)w_dgrad[k] + img.off(SV_WP_POLYD_CORNER) * esz;
     m.erow[i] = (float*)edgews[k]; m.ecol[i] = m.erow[i] + (int64_t)d->B * 2 * w * cin;
   }
   int rc = SV_E_UNSUPPORTED;
@@ -212,7 +213,7 @@ int svk_polyd_dgrad_multi(const sv_conv_desc* d, int n, const void* const* dy, c
   if (rc) return rc;
   for (int i = 0; i < n; ++i) {
     svg_polyd_args(d, &a[i]);
-    a[i].A = dy[i]; a[i].Wt = w_polyd[i]; a[i].out = dx_lo[i]; a[i].mask = mask_lo ? mask_lo[i] : nullptr;
+    a[i].A = dy[i]; a[i].Wt = (const char*)w_dgrad[i] + img.off(SV_WP_POLYD_MAIN) * esz; a[i].out = dx_lo[i]; a[i].mask = mask_lo ? mask_lo[i] : nullptr;
     a[i].fix = m.erow[i]; a[i].fix2 = m.ecol[i];
   }
   return svk_conv_dispatch_multi(a, n, d->dtype, svg_pick_cfg(d->Cin), st);

@@ -612,31 +612,17 @@ extern "C" int sv_tape_finalize(sv_tape* t) {
     }
   }
   // conv weight images + scratch
-  int64_t arena = 0;
-  int blocks = 0;
-  auto push = [&](PrepJob j) { j.first_block = blocks; blocks += j.nblocks; t->jobs.push_back(j); };
+  PrepArena ar;
   for (size_t i = 0; i < t->nodes.size(); ++i) {
     const sv_tape_node& n = t->nodes[i];
     sv_tape::Extra& e = t->ex[i];
-    if (n.kind == SV_TAPE_CONV) {
-      PrepJob j;
-      svg_prep_job_fwd(&e.cd, &j);
-      j.src_off = n.w_off;
-      arena = (arena + 127) / 128 * 128;
-      e.wf_off = arena; j.dst_off = arena;
-      arena += (int64_t)j.rows * j.ntaps * j.inner;
-      push(j);
+    if (n.kind == SV_TAPE_CONV) {       // the images sv_conv2d_nhwc_fwd / _dgrad read (the same layout table: conv_geom.h)
+      WImage w;
+      svg_wimage_fwd_api(&e.cd, &w);
+      e.wf_off = ar.place(w, n.w_off);
       if (gr(n.x)) {
-        arena = (arena + 127) / 128 * 128;
-        e.wd_off = arena;
-        for (int c = 0; c < svg_dgrad_classes(&e.cd); ++c) {
-          PrepJob jd;
-          svg_prep_job_dgrad(&e.cd, c, &jd);
-          jd.src_off = n.w_off;
-          jd.dst_off = arena;
-          arena += (int64_t)jd.rows * jd.ntaps * jd.inner;
-          push(jd);
-        }
+        svg_wimage_dgrad(&e.cd, &w);
+        e.wd_off = ar.place(w, n.w_off);
       }
     }
     auto scratch = [&](int64_t floats) { const int64_t o = t->scratch_floats; t->scratch_floats += (floats + 63) / 64 * 64; return o; };
@@ -661,8 +647,9 @@ extern "C" int sv_tape_finalize(sv_tape* t) {
     }
     if (n.kind == SV_TAPE_UPSAMPLE && gr(n.x) && t->tens[t->root(n.x)].writers > 1) e.scratch = scratch(t->tens[n.x].rows * t->tens[n.x].ld);
   }
-  t->arena_elems = arena + 128;
-  t->prep_blocks = blocks;
+  t->arena_elems = ar.elems + 128;
+  t->prep_blocks = ar.blocks;
+  t->jobs = std::move(ar.jobs);
   const int64_t es = t->dtype == SV_BF16 ? 2 : 4;
   auto al = [](int64_t b) { return (b + 255) / 256 * 256; };
   int64_t o = 0;

@@ -98,6 +98,38 @@ def test_workspace_layout_is_pinned(lib_built, kind, index):
     assert sum((b + 255) // 256 * 256 for _, b in present) == got["workspace_bytes"]
 
 
+def test_weight_image_sizes_are_pinned(lib_built):
+    """sv_conv2d_wprep_elems (forward and input-gradient image) and the four conv workspace-size queries against tests/golden/wprep_elems.json
+    (recorded by tests/golden/make_golden_wprep_elems.py from the commit before the weight-image layout table), entry by entry: every accepted
+    descriptor of conv_domain_grid(), every case of tests/test_gpu_conv_api.py, the plan's nine layers at two shapes and both dtypes.  Host only."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("make_golden_wprep_elems", os.path.join(ROOT, "tests", "golden", "make_golden_wprep_elems.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    from split_vae_amd import _lib
+    lib = _lib.load()
+    with open(os.path.join(ROOT, "tests", "golden", "wprep_elems.json")) as f:
+        doc = json.load(f)
+    assert re.fullmatch(r"[0-9a-f]{40}", doc["recorded_from_commit"])
+    # the grid: the same descriptors are accepted, and each answers what it answered
+    want = gen.decode_grid(doc["grid"])
+    descs = list(gen.grid_descs())
+    assert len(want) == len(descs) and sum(w[0] != -1 for w in want) > 1000
+    for i, d in enumerate(descs):
+        got = gen.queries(lib, d)
+        assert got == want[i], (i, d, got, want[i])
+    # the named descriptors: the file's lists are the generator's lists, and every entry matches
+    for key, descs in (("cases", gen.case_descs()), ("layers", gen.layer_descs())):
+        descs = list(descs)
+        assert [(e["name"], e["desc"]) for e in doc[key]] == [(n, d) for n, d in descs], key
+        for e in doc[key]:
+            assert gen.queries(lib, e["desc"]) == e["sizes"], (key, e["name"])
+    assert len(doc["cases"]) >= 50 and len(doc["layers"]) == 36
+    # the groups reach the forms the grid does not: polyphase images (forward workspace > 0) and the polyphase input gradient
+    assert any(e["sizes"][2] > 0 for e in doc["cases"]) and any(e["sizes"][4] > 0 for e in doc["layers"])
+
+
 @pytest.mark.parametrize("gl,ll,B", [(128, 128, 512), (64, 64, 64), (256, 256, 96), (128, 128, 70), (256, 128, 64)])
 def test_latent_slab_workspace_covers_every_split(lib_built, gl, ll, B):
     """the K-slice slabs of the latent block (lat_ws_x / lat_ws_xh) are sized from the four launches' own (split, N) pairs; a slab
@@ -343,18 +375,24 @@ def _conv_domain_rule(B, H, W, Cin, Cout, KH, KW, s, dtype, ldx, ldy, y_f32, ups
     return 0
 
 
-def test_conv_accepted_domain_matches_the_header(lib_built):
-    """host-only queries (no device work): a grid of descriptors through sv_conv2d_wprep_elems / the workspace-size queries, which answer
-    -1 exactly for the descriptors the header's rule refuses, against a Python statement of that rule"""
+def conv_domain_grid():
+    """the descriptors of test_conv_accepted_domain_matches_the_header, in a fixed order (tests/golden/make_golden_wprep_elems.py walks them too)"""
     import itertools
-    from split_vae_amd import _lib
-    lib = _lib.load()
-    n = 0
     grid = itertools.product((1, 3), ((16, 16), (16, 32), (12, 20), (24, 12), (15, 16), (1, 1)), (1, 3, 5, 12, 17, 30, 60), (1, 6, 10, 48),
                              ((3, 3), (3, 5), (6, 6), (9, 10)), (1, 2, 3, 4), (0, 1), (0, 8, 12), (0, 1), (0, 1))
     for B, (H, W), Cin, Cout, (KH, KW), s, dtype, ldx_over, y_f32, ups in grid:
         ldx = (Cin + 7) // 8 * 8 + ldx_over
         ldy = Cout if y_f32 else (Cout + 7) // 8 * 8
+        yield B, H, W, Cin, Cout, KH, KW, s, dtype, ldx, ldy, y_f32, ups
+
+
+def test_conv_accepted_domain_matches_the_header(lib_built):
+    """host-only queries (no device work): a grid of descriptors through sv_conv2d_wprep_elems / the workspace-size queries, which answer
+    -1 exactly for the descriptors the header's rule refuses, against a Python statement of that rule"""
+    from split_vae_amd import _lib
+    lib = _lib.load()
+    n = 0
+    for B, H, W, Cin, Cout, KH, KW, s, dtype, ldx, ldy, y_f32, ups in conv_domain_grid():
         d = _lib.ConvDesc(B, H, W, Cin, Cout, KH, KW, s, 0, dtype, ldx, ldy, y_f32, ups)
         ok = _conv_domain_rule(B, H, W, Cin, Cout, KH, KW, s, dtype, ldx, ldy, y_f32, ups) == 0
         got = [lib.sv_conv2d_wprep_elems(C.byref(d), 0), lib.sv_conv2d_wprep_elems(C.byref(d), 1), lib.sv_conv2d_fwd_workspace_bytes(C.byref(d)),
