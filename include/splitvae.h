@@ -776,6 +776,54 @@ int sv_knn_classify(const float* q, int32_t ldq, const float* r, int32_t ldr, co
                     float* nn_dist /* [Nq,k] or NULL */, int32_t* pred /* [Nq] */, const uint8_t* q_class /* or NULL */,
                     int64_t* acc /* [2]: hits, count; ADDED to; or NULL */, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- aggregate-posterior information report (csrc/latent_info.hip)
+ * No reference counterpart.  Hoffman & Johnson's decomposition ("ELBO surgery") of the average KL term into the index-code mutual
+ * information and the marginal KL, per latent block, plus the mutual information of the two blocks under the aggregate posterior.
+ * Needs no labels.  A block of width L has posterior means mu_j and standard deviations sig_j for the images j = 0 .. N-1; the two
+ * blocks are concatenated: columns 0 .. Lg-1 are z_g, columns Lg .. Lg+Ll-1 are z_l (Ll = 0: one block).  fp32 inputs, ALL FINITE,
+ * sig > 0.
+ *   sample       z_i = mu_i + sig_i * eps_i (fp32, that expression).  eps [N, Lg+Ll] (row pitch lde) pins it; NULL: the library's
+ *                Philox4x32-10 with a key constant of its own (seed ^ 0x1a7e27140f0) and counter (dimension j within its block,
+ *                global image index sample_offset + b, 'li' tag | 0 global / 1 local, 0) and the Box-Muller of sv_iw_advance: a
+ *                pure function of (seed, image, block, dimension), whatever batch the image sits in;
+ *   row constant c_j = -sum_d log sig_jd - L/2 log(2 pi), the sum in fp64 over fp32 logf; cst [N,2] fp32 = (c^g_j, c^l_j);
+ *   pair score   e_ij = c_j - 1/2 sum_d ((z_id - mu_jd) * rsig_jd)^2 with rsig = 1 / sig (fp32, correctly rounded), computed in this
+ *                DIRECT form in fp32 -- subtract, multiply, fused multiply-add onto the running sum, d ascending within the block
+ *                (zero-padded to a multiple of 32), then c_j - 0.5 * sum.  Only non-negative terms: the error is relative to the
+ *                score.  (The expanded z^2.a - 2 z.b + c cancels ~1e5 against ~1e5 at sig ~ 1e-2.)  e^gl_ij = e^g_ij + e^l_ij (fp32);
+ *   own term     own_i = c_i - 1/2 sum_d eps_id^2, in closed form from eps (fp64 sums): never taken from the pair loop;
+ *   prior term   prior_i = -L/2 log(2 pi) - 1/2 sum_d z_id^2 (fp64 sums) = log N(z_i; 0, I);
+ *   aggregate    lse_g[i] = logsumexp_j e^g_ij - log Nr, lse_l[i] likewise, lse_gl[i] = logsumexp_j (e^g_ij + e^l_ij) - log Nr;
+ *   reported     per block KL = mean_i (own_i - prior_i), MI = mean_i (own_i - lse_i), marginal KL = mean_i (lse_i - prior_i), so
+ *                KL = MI + marginal KL by construction; overlap I(z_g; z_l) = mean_i (lse_gl[i] - lse_g[i] - lse_l[i]); log N.
+ *                Every MI-type figure saturates at log N: the known upward bias of this estimator.
+ * sv_latent_info_draw: mu, sig [N, Lg+Ll] (row pitches ldm, lds) -> z (ldz), rsig (ldr), cst [N,2] fp32, own [N,2] and prior [N,2]
+ *   fp64 (column 1 is 0 when Ll = 0).  One wave per image.
+ * sv_latent_info_lse: queries z [Nq, Lg+Ll] against the references mu, rsig [Nr, Lg+Ll] and cst [Nr,2] -> lse [3, Nq] fp64: rows
+ *   lse_g, lse_l, lse_gl (rows 1 and 2 are not written when Ll = 0).  Nq and Nr are independent.  The references are cut into chunks
+ *   of sv_latent_info_chunk_rows() rows; a tile kernel leaves one fp32 (max, sum) per (query, chunk, sum) in the workspace
+ *   (sv_latent_info_workspace_bytes; 16-byte aligned; may hold anything on entry) and a merge kernel folds them per query in chunk
+ *   order in fp64.  No atomics: the same inputs give the same bits, wherever a query row sits.
+ * sv_latent_info_finish: own, prior [N,2], lse [3,N] of Nq = Nr = N -> out [8] fp64 = (KL_g, MI_g, marginal KL_g, KL_l, MI_l,
+ *   marginal KL_l, overlap, log N), the means summed in one fixed order by one workgroup (thread t takes the images t, t + 256, ... in
+ *   ascending order, then the 256 partial sums are added in thread order: deterministic); entries 3 .. 6 are 0 when Ll = 0.  One
+ *   read-back per evaluation.
+ * Everything is enqueued on `stream`; no host synchronisation.  Accepted domain: 1 <= Lg <= 512, 0 <= Ll <= 512, N, Nq, Nr >= 1 (Nr
+ * at most 65535 chunks), row pitches >= Lg + Ll, sample_offset >= 0: anything else SV_E_UNSUPPORTED; a null pointer (eps may be
+ * NULL) or a misaligned one (4 bytes; fp64 arrays 8; workspace 16): SV_E_BADARG; workspace_bytes below
+ * sv_latent_info_workspace_bytes: SV_E_WORKSPACE.  All checked before anything is enqueued. */
+int sv_latent_info_chunk_rows(void);
+int sv_latent_info_workspace_bytes(int32_t Nq, int32_t Nr, int64_t* bytes);
+int sv_latent_info_draw(const float* mu, int32_t ldm, const float* sig, int32_t lds, const float* eps /* or NULL */, int32_t lde,
+                        float* z, int32_t ldz, float* rsig, int32_t ldr, float* cst /* [N,2] */, double* own /* [N,2] */,
+                        double* prior /* [N,2] */, int32_t N, int32_t Lg, int32_t Ll, uint64_t seed, int64_t sample_offset,
+                        void* stream);
+int sv_latent_info_lse(const float* z, int32_t ldz, const float* mu, int32_t ldm, const float* rsig, int32_t ldr, const float* cst,
+                       int32_t Nq, int32_t Nr, int32_t Lg, int32_t Ll, double* lse /* [3,Nq] */, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int sv_latent_info_finish(const double* own, const double* prior, const double* lse, int32_t N, int32_t Ll, double* out /* [8] */,
+                          void* stream);
+
 /* ---------------------------------------------------------------- SPLIT-SPAIR: Dense layers, exact fp32 on the matrix cores
  * tf.keras.layers.Dense (spair/spair.py:135-154, :185-202, :246-273, :341-366, :424-467) for ANY fan-in / fan-out, reading the Keras
  * [in, out] kernel as it lies in the variable buffer (dense_f32.hip).  x [M, ldx], y / dy [M, ldy], w [K, N] row-major.

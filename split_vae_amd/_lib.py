@@ -20,6 +20,7 @@ PHASE_BUCKET_EVENTS = 1024  # modifier: record the gradient-bucket events of the
 PHASE_INFER = PHASE_PREP | PHASE_FORWARD
 IW_ACCUMULATE, IW_DRAW = 1, 2      # sv_iw_advance flags (include/splitvae.h)
 KNN_MAX_K, KNN_MAX_L, KNN_MAX_CLASSES = 32, 512, 64      # accepted domain of sv_knn_classify (include/splitvae.h)
+LATENT_INFO_MAX_L = 512            # accepted width of either latent block of sv_latent_info_* (include/splitvae.h)
 
 STATUS = {0: "SV_OK", -1: "SV_E_BADARG", -2: "SV_E_UNSUPPORTED", -3: "SV_E_WORKSPACE", -4: "SV_E_STATE"}
 STATUS_BADARG, STATUS_UNSUPPORTED, STATUS_WORKSPACE, STATUS_STATE = -1, -2, -3, -4
@@ -275,6 +276,11 @@ SYMBOLS = {
     "sv_knn_chunk_rows": (C.c_int, []),
     "sv_knn_workspace_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
     "sv_knn_classify": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sv_latent_info_chunk_rows": (C.c_int, []),
+    "sv_latent_info_workspace_bytes": (C.c_int, [_i32, _i32, C.POINTER(_i64)]),
+    "sv_latent_info_draw": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _u64, _i64, _vp]),
+    "sv_latent_info_lse": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "sv_latent_info_finish": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -4,7 +4,7 @@
     python -m split_vae_amd.main --model gmvae --beta 40 --patch_size 4       (GMVAE baseline, Table 2)
 
 Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout, --mix_per_image,
---resident_data, --iw_samples, --gm_iw_samples, --knn_probe, --knn_refs.
+--resident_data, --iw_samples, --gm_iw_samples, --knn_probe, --knn_refs, --latent_info.
 """
 import argparse
 
@@ -57,6 +57,10 @@ def build_parser():
                          "needs labels; K <= 32")
     ap.add_argument("--knn_refs", type=int, default=20000,
                     help="--knn_probe: the number of reference images, the first N of the training set in file order")
+    ap.add_argument("--latent_info", type=int, default=0,
+                    help="N >= 2: after the report of every evaluation, the aggregate-posterior information report over the first N "
+                         "test images: per latent block the KL term split into index-code mutual information and marginal KL, and the "
+                         "mutual information of z_g and z_l (split_vae_amd/latent_info.py); needs no labels")
     return ap
 
 
@@ -133,6 +137,8 @@ def main(argv=None):
     check_mixture_model_name(args.model, args.gm_iw_samples)
     from .probe import check_flags
     check_flags(args.knn_probe, args.knn_refs, args.no_label)
+    from .latent_info import check_flags as check_latent_info
+    check_latent_info(args.latent_info, args.global_latent_dims, args.local_latent_dims if args.model != 'gmvae' else 0)
     from . import configure_hw_queues
     configure_hw_queues()                            # before the first HIP call (split_vae_amd/__init__.py)
     config = dotdict(vars(args))

@@ -818,6 +818,86 @@ def knn_classify(q, r, r_class, k, n_class, q_class=None, acc=None, want_neighbo
     return (pred, nn_i, nn_d) if want_neighbours else pred
 
 
+# ------------------------------------------------------------------ aggregate-posterior information report (include/splitvae.h)
+def latent_info_chunk_rows():
+    return int(_lib.load().sv_latent_info_chunk_rows())
+
+
+def latent_info_workspace_bytes(Nq, Nr):
+    n = C.c_int64()
+    check(_lib.load().sv_latent_info_workspace_bytes(int(Nq), int(Nr), C.byref(n)), "sv_latent_info_workspace_bytes")
+    return n.value
+
+
+def _same_rows(t, name, N, Lc, device):
+    p, ld = _rows_f32(t, name)
+    if tuple(t.shape) != (N, Lc) or t.device != device:
+        raise ValueError("%s must be [%d,%d] on %s, got %s" % (name, N, Lc, device, tuple(t.shape)))
+    return p, ld
+
+
+def latent_info_draw(mu, sig, Lg, eps=None, seed=0, sample_offset=0, out=None):
+    """sv_latent_info_draw: mu, sig [N, Lg+Ll] fp32 (columns 0 .. Lg-1: z_g, the rest: z_l) -> (z, rsig [N, Lg+Ll] fp32, cst [N,2]
+    fp32, own [N,2], prior [N,2] fp64).  eps [N, Lg+Ll] pins the draw; otherwise image sample_offset + b draws from (seed, image,
+    block).  out: that 5-tuple, to write into (z and rsig may have a row pitch above their width)."""
+    mp, ldm = _rows_f32(mu, "mu")
+    N, Lc = mu.shape
+    dev = mu.device
+    sp, lds = _same_rows(sig, "sig", N, Lc, dev)
+    ep, lde = (None, 0) if eps is None else _same_rows(eps, "eps", N, Lc, dev)
+    if out is None:
+        f32, f64 = torch.float32, torch.float64
+        out = (torch.empty((N, Lc), dtype=f32, device=dev), torch.empty((N, Lc), dtype=f32, device=dev),
+               torch.empty((N, 2), dtype=f32, device=dev), torch.empty((N, 2), dtype=f64, device=dev), torch.empty((N, 2), dtype=f64, device=dev))
+    z, rsig, cst, own, prior = out
+    zp, ldz = _same_rows(z, "z", N, Lc, dev)
+    rp, ldr = _same_rows(rsig, "rsig", N, Lc, dev)
+    for t, dt, name in ((cst, torch.float32, "cst"), (own, torch.float64, "own"), (prior, torch.float64, "prior")):
+        if t.dtype != dt or tuple(t.shape) != (N, 2) or not t.is_contiguous() or t.device != dev:
+            raise ValueError("%s must be a contiguous [%d,2] %s device tensor" % (name, N, dt))
+    check(_lib.load().sv_latent_info_draw(mp, ldm, sp, lds, ep, lde, zp, ldz, rp, ldr, _p(cst), _p(own), _p(prior), N, int(Lg), Lc - int(Lg),
+                                          int(seed), int(sample_offset), _stream()), "sv_latent_info_draw")
+    return out
+
+
+def latent_info_lse(z, mu, rsig, cst, Lg, lse=None, workspace=None):
+    """sv_latent_info_lse: lse [3, Nq] fp64 = (lse_g, lse_l, lse_gl) of the queries z [Nq, Lg+Ll] under the references mu, rsig
+    [Nr, Lg+Ll], cst [Nr,2] (rows 1 and 2 are not written when Ll = 0).  workspace: a uint8 device tensor of at least
+    latent_info_workspace_bytes(Nq, Nr) bytes with any contents (default: allocated here)."""
+    zp, ldz = _rows_f32(z, "z")
+    Nq, Lc = z.shape
+    Nr = mu.shape[0]
+    dev = z.device
+    mp, ldm = _same_rows(mu, "mu", Nr, Lc, dev)
+    rp, ldr = _same_rows(rsig, "rsig", Nr, Lc, dev)
+    if cst.dtype != torch.float32 or tuple(cst.shape) != (Nr, 2) or not cst.is_contiguous() or cst.device != dev:
+        raise ValueError("cst must be a contiguous [%d,2] fp32 device tensor" % Nr)
+    if lse is None:
+        lse = torch.empty((3, Nq), dtype=torch.float64, device=dev)
+    if lse.dtype != torch.float64 or tuple(lse.shape) != (3, Nq) or not lse.is_contiguous() or lse.device != dev:
+        raise ValueError("lse must be a contiguous [3,%d] fp64 device tensor" % Nq)
+    nbytes = latent_info_workspace_bytes(Nq, Nr)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous():
+        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    check(_lib.load().sv_latent_info_lse(zp, ldz, mp, ldm, rp, ldr, _p(cst), Nq, Nr, int(Lg), Lc - int(Lg), _p(lse), _p(ws), ws.numel(),
+                                         _stream()), "sv_latent_info_lse")
+    return lse
+
+
+def latent_info_finish(own, prior, lse, Ll, out=None):
+    """sv_latent_info_finish: out [8] fp64 = (KL_g, MI_g, marginal KL_g, KL_l, MI_l, marginal KL_l, overlap, log N)."""
+    N = own.shape[0]
+    f64 = torch.float64
+    if out is None:
+        out = torch.empty((8,), dtype=f64, device=own.device)
+    if not all(t.dtype == f64 and t.is_contiguous() and t.is_cuda for t in (own, prior, lse, out)) or tuple(own.shape) != (N, 2) or \
+            tuple(prior.shape) != (N, 2) or tuple(lse.shape) != (3, N) or out.numel() < 8:
+        raise ValueError("own, prior [N,2], lse [3,N] and out [8] must be contiguous fp64 device tensors")
+    check(_lib.load().sv_latent_info_finish(_p(own), _p(prior), _p(lse), N, int(Ll), _p(out), _stream()), "sv_latent_info_finish")
+    return out
+
+
 # ------------------------------------------------------------------ A9 SPLIT-GMVAE glue (vae/model.py:48-79,:116-135)
 ACT ={None: _lib.SV_ACT_NONE, "relu": _lib.SV_ACT_RELU, "elu": _lib.SV_ACT_ELU}
 

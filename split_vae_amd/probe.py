@@ -9,8 +9,7 @@ k it has no parameters.  lgvae and lggmvae report both latents, gmvae z_g only.
 import torch
 
 from . import ops
-from ._lib import KNN_MAX_K, PHASE_FWD_ENCODERS, PHASE_PREP
-from .model import LGVae
+from ._lib import KNN_MAX_K
 
 REPORT = 'Test k-NN probe (k={}, {} refs): z_g acc {:.4f}'
 REPORT_L = ', z_l acc {:.4f}'
@@ -31,24 +30,9 @@ def check_flags(knn_probe, knn_refs, no_label):
 
 def _means(model, images):
     """(z_mean_x, z_mean_x_hat or None) of one batch, as views of buffers the next batch overwrites."""
-    from .gm import LGGMVae
-    from .gmvae import GMVae, _images6
-    B = images.shape[0]
-    if type(model) is LGVae:
-        from .trainer import _check_images
-        _check_images(model, images)
-        plan = model.plan(B)
-        plan.step(PHASE_PREP | PHASE_FWD_ENCODERS, params=model.flat, images6=images, seed=model.seed)
-        return (plan.buffer("z_mean_x", torch.float32, (B, model.global_latent_dims)),
-                plan.buffer("z_mean_xh", torch.float32, (B, model.local_latent_dims)))
-    if not isinstance(model, (LGGMVae, GMVae)):
-        raise TypeError("the k-NN probe runs LGVae, LGGMVae and GMVae models, got %s" % type(model).__name__)
-    calls = model._calls
-    try:
-        out = model(_images6(images) if isinstance(model, GMVae) else images, copy=False)
-    finally:
-        model._calls = calls                       # a probe between training steps does not move the training noise
-    return out[3], (out[8] if isinstance(model, LGGMVae) else None)
+    from .latent_info import batch_posterior
+    mean_g, _, mean_l, _ = batch_posterior(model, images)
+    return mean_g, mean_l
 
 
 def latent_means(model, batches):

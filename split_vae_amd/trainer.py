@@ -214,6 +214,7 @@ def train_local_global_autoencoder(model, optimizer, dataset, train_dataset, tes
                 from . import iw
                 print(iw.report_line(config.iw_samples, iw.evaluate(model, test_dataset, config.iw_samples)))
             _knn_probe_report(model, test_dataset, config, step)
+            _latent_info_report(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             # vae/trainer.py:405-414 resets x_recon / x_kl / total_kl but never the x_hat_* means
             metrics.reset_states(["x_recon_loss", "x_kl_loss", "total_kl_loss"])
@@ -237,6 +238,15 @@ def _knn_probe_report(model, test_dataset, config, step):
         config.knn_history = []
     config.knn_history.append(dict(step=step, knn_acc_g=res["acc_g"], knn_acc_l=res["acc_l"]))
     return res
+
+
+def _latent_info_report(model, test_dataset, config, step):
+    """--latent_info N: the aggregate-posterior information report (latent_info.py) behind an evaluation's report; the figures are
+    kept in config.latent_info_history: one dict per evaluation."""
+    if int(config.get("latent_info") or 0) <= 0:
+        return None
+    from . import latent_info
+    return latent_info.report(model, test_dataset, config, step)
 
 
 def _gm_iw_report(model, test_dataset, config, step):
@@ -325,6 +335,7 @@ def _train_lggmvae(model, optimizer, train_dataset, test_dataset, config):
                 print('            Classifier cluster acc: {:.4f}'.format(cluster.result()))
             _gm_iw_report(model, test_dataset, config, step)
             _knn_probe_report(model, test_dataset, config, step)
+            _latent_info_report(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             acc, n_acc = None, 0
             start = time.time()
@@ -382,6 +393,7 @@ def _train_gmvae(model, optimizer, train_dataset, test_dataset, config):
             print('            Y KL train loss: {:.4f}, Y KL test loss: {:.4f}'.format(tr[2], te[2]))
             _gm_iw_report(model, test_dataset, config, step)
             _knn_probe_report(model, test_dataset, config, step)
+            _latent_info_report(model, test_dataset, config, step)
             acc, n_acc = None, 0
             start = time.time()
         if step >= config.training_steps:
