@@ -30,6 +30,9 @@
 #ifndef SV_TC_PPS64
 #define SV_TC_PPS64 8     // ... of the 64-column kernel
 #endif
+#ifndef SV_TC_EPI_BATCH
+#define SV_TC_EPI_BATCH 8 // pieces per batch of the fp32 fast store path (build-time A/B knob; a power of two)
+#endif
 // with row-window reuse (YR = KH) the 16-column kernel steps one whole filter column (KH taps x 4 pieces), the wider
 // ones two taps (their weight tiles are BN x PPS x 16 B x 2 buffers of LDS)
 static __host__ __device__ constexpr int tile_pps(int BN, int YR = 0) {
@@ -348,6 +351,66 @@ __global__ __launch_bounds__(64 * NW, tile_min_waves(BN, NW, YR, WR)) void tile_
   }
   __syncthreads();
   if (SV_DBG(g.dbg) & 4) return;
+  // FAST STORE PATH (fp32 instantiations only -- code compiled into the bf16 kernels has twice cost the head's fused-loss forward 20+ us): a FULL column tile
+  // that is not x-packed and lies inside the batch and the image.  Its rows are BN * 4 bytes, so the pieces are 16 B, PPRF = BN / 4 of them per row, a power of
+  // two that divides NT: a thread's piece column -- with it its channel offset and, under cls_n, its parity class -- is the same in every pass and only the tile
+  // row advances, by RPI.  The general loop at the end of the kernel (kept for the partial column tile, the 8-byte pieces, the x-packed forms and the tile that
+  // reaches past the batch) handles one piece per iteration: about seven kernarg fields reloaded with a wait each, two emulated divisions, and ONE mask load in
+  // flight per lane behind a vmcnt(0).  Here the fields are locals, the one division is done once, and the pieces go in batches of EB: all mask loads, then all
+  // LDS reads, then the selects and stores behind counted vmcnt waits.  Same predicate (mask > 0), same values, same addresses: bitwise the general loop's output.
+  // Measured (profiles/tile_epilogue_bench_ab.txt): fp32 step at 2 x 512 images 9.14 -> 8.95 ms.  Batches of 4 or 8: equal.  The first batch's mask loads issued
+  // AHEAD of the transpose (their latency under it): equal at batches of 4 with 16-20 more VGPRs in the two big tiles, slower at 8 (two kernels lose a wave).
+  if constexpr (sizeof(T) == 4) {
+    constexpr int PPRF = BN / 4, RPI = NT / PPRF, TRIPS = BM / RPI;   // pieces per row, tile rows per pass, pieces per thread
+    constexpr int EB = TRIPS < SV_TC_EPI_BATCH ? TRIPS : SV_TC_EPI_BATCH;
+    constexpr int SROW = BN * 4 + 16;                   // = srow of a full fp32 column tile
+    static_assert(NT % PPRF == 0 && BM % RPI == 0 && TRIPS % EB == 0, "fast store path: the pieces of a row must divide the workgroup");
+    // (rowb = BN * 4: psz == 16.)  The out-of-range predicate of a piece (b < B, oy < OY, ox < OX) is taken for the WHOLE tile, once and the same in every lane:
+    // the tile that reaches past the batch keeps the general loop and its per-piece predicate, and the batches are free of branches (with a predicate per piece
+    // hipcc put every load into a block of its own, folded the compares into it and waited with vmcnt(0) behind each load)
+    if (ncols == BN && !g.d2s && b0 + NB <= g.B && ty0 + TH <= g.OY && tx0 + TW <= g.OX) {
+      const int fr0 = tid / PPRF, fcb = (tid & (PPRF - 1)) * 16, elTW = g.lTW, elTH = g.lTH;
+      const char* emask = (const char*)g.mask;
+      char* eout = (char*)g.out;
+      const int n = n0 + (fcb >> 2), eOS = g.OS, eldo = g.ldo;
+      int ech = n, eyo = g.ooy, exo = g.oox;
+      if (g.cls_n) {                                    // merged parity classes: this piece's class picks the sub-pixel
+        const int cls = n / g.cls_n;
+        ech = n - cls * g.cls_n; eyo = cls >> 1; exo = cls & 1;
+      }
+      // the general loop's ((b * OHF + oy * OS + yo) * OWF + ox * OS + xo) * ldo + ch, in bytes, split into the tile's origin and the strides of (bl, ty, tx)
+      const int64_t pix0 = ((int64_t)b0 * g.OHF + ty0 * eOS + eyo) * g.OWF + tx0 * eOS + exo;
+      const int64_t ebase = (pix0 * eldo + ech) * 4, esx = (int64_t)eOS * eldo * 4, esy = esx * g.OWF, esb = (int64_t)g.OHF * g.OWF * eldo * 4;
+      const char* sp = sC + fr0 * SROW + fcb;
+#pragma unroll
+      for (int it0 = 0; it0 < TRIPS; it0 += EB) {
+        uint4 mv[EB], v[EB];
+        int64_t ob[EB];
+#pragma unroll
+        for (int u = 0; u < EB; ++u) {
+          const int r = fr0 + (it0 + u) * RPI;
+          const int tx = r & ((1 << elTW) - 1), ty = (r >> elTW) & ((1 << elTH) - 1), bl = r >> (elTW + elTH);
+          ob[u] = ebase + bl * esb + ty * esy + tx * esx;
+        }
+        if (emask) {
+#pragma unroll
+          for (int u = 0; u < EB; ++u) mv[u] = *(const uint4*)(emask + ob[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < EB; ++u) v[u] = *(const uint4*)(sp + (it0 + u) * (RPI * SROW));
+#pragma unroll
+        for (int u = 0; u < EB; ++u) {
+          if (emask) {                                  // mask tensor has the output's type and indexing
+            const float4 m = __builtin_bit_cast(float4, mv[u]);
+            v[u].x = m.x > 0.f ? v[u].x : 0u; v[u].y = m.y > 0.f ? v[u].y : 0u;
+            v[u].z = m.z > 0.f ? v[u].z : 0u; v[u].w = m.w > 0.f ? v[u].w : 0u;
+          }
+          *(uint4*)(eout + ob[u]) = v[u];
+        }
+      }
+      return;
+    }
+  }
   const int psz = (rowb & 15) ? 8 : 16;                 // piece size; rowb is a multiple of 8
   const int ppr_o = rowb / psz;
   if (g.d2s_y) {
