@@ -86,6 +86,26 @@ template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return (bf16_t)v; }
 
+// ---- the two LDS primitives of the DMA-fed kernels (weight gradients, row-ring conv, latent GEMMs), defined here once
+// 64 lanes x 16 B, global -> LDS (lane l lands at lds + 16 l).  base: the wave-uniform tensor pointer (an SGPR pair); off: this lane's byte offset from it;
+// lds: the wave-uniform LDS address of lane 0's 16 bytes (it goes through m0).  Inline assembly and not __builtin_amdgcn_global_load_lds (tile_stage.hip.h:
+// stage_dma16 is that form): the compiler orders every later read of an LDS object a DMA builtin may have written behind s_waitcnt vmcnt(0), which parks a
+// producer wave on its NEWEST transfer every step; here the only waits are the counted s_waitcnt vmcnt(N) the kernels place themselves.
+// m0 is on the clobber list because the statement writes it.  clang answers every use with "inline asm clobber list contains reserved registers: m0" (it does
+// not save and restore a reserved register around the statement; the code generator writes m0 right before each instruction of its own that reads it, which
+// every kernel using this has relied on since it was written): hundreds of lines per build that hid real warnings, silenced for this one statement.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ void lds_dma16(const void* base, uint32_t off, const char* lds) {
+  const uint32_t l = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(l) : "memory", "m0");
+}
+#pragma clang diagnostic pop
+// transposed 8-byte LDS read: four bf16 of one column of a 16 x 16 block stored row-major (ds_read_b64_tr_b16), the MFMA operand layout
+__device__ __forceinline__ short4_t lds_tr16(const char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(p));
+}
+
 // GEMM row m -> (image, oy, ox) of an OY x OX iteration grid: shifts for power-of-two grids (every SPLIT-VAE layer),
 // two integer divisions otherwise (wave-uniform choice)
 __device__ __forceinline__ void sv_decode_row(int m, int lOY, int lOX, int OY, int OX, int& b, int& oy, int& ox) {

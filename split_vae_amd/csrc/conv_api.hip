@@ -963,7 +963,7 @@ extern "C" int sv_conv2d_nhwc_wgrad_poly(const sv_conv_desc* d, const void* x_lo
   svg_poly_wgrad_args(d, &a);
   sv_trace_note(nullptr);
   a.A = x_lo; a.dY = dy; a.dW = pw; a.dbias = pw + 25 * Cin * 32; a.ws = (float*)workspace; a.ws_bytes = SV_WGRAD_WS_BYTES;
-  rc = svk_wgrad_tile(a, (hipStream_t)stream);
+  rc = svk_wgrad_bf16_forms_multi(&a, 1, (hipStream_t)stream);        // wgrad_p5 or wgrad_tile
   if (rc) return rc;
   rc = svk_poly_wgrad_finish(1, &x_lo, &dy, &pw, &dw, &dbias, d->B, d->H / 2, d->W / 2, d->ldx, Cin, d->Cout, SV_POLY_WGRAD_NWG,
                              (hipStream_t)stream);

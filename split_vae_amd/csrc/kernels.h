@@ -137,8 +137,8 @@ struct WgradArgs {
   float* ws;          // optional partial-sum workspace for the two-stage (deterministic) flush of the tile kernel
   int64_t ws_bytes;
   hipEvent_t ev_mid[2];   // profiling: when set, both are recorded after the main kernel, before the slab reduce
-  struct WgradReduceDesc* defer; int* n_defer;   // fp32 tile kernel, slab path (polyc_wgrad.hip): do NOT launch the reduce, append its descriptor here
-                                                 // (svk_wgrad_reduce_all later; the slab workspace must stay untouched until then)
+  struct WgradReduceDesc* defer; int* n_defer;   // slab launches (wgrad_host.h: wgrad_finish; set by polyc_wgrad.hip): do NOT launch the reduce, append its descriptor
+                                                 // here (svk_wgrad_reduce_all later; the slab workspace must stay untouched until then)
   int8_t dy[SV_MAX_TAPS];
   int8_t dx[SV_MAX_TAPS];
 };
@@ -191,30 +191,38 @@ struct WgradReduceDesc {
 struct WgradReduceAll { WgradReduceDesc d[SV_WGRAD_DEFER_MAX]; int first[SV_WGRAD_DEFER_MAX + 1]; int n; };   // first: block ranges of the flat grid
 int svk_wgrad_reduce_all(const WgradReduceDesc* d, int n, hipStream_t st);   // every pending reduce in ONE launch (blockIdx.z = descriptor)
 #define SV_WGRAD_MAX_MULTI 2
-// rolling-window form for the 6x6 conv over an upsampled 64-channel input (d4; wgrad_roll.hip): needs the slab workspace
+// The bf16 forms.  Each strip kernel has a plan (wgrad_host.h: WgradStripPlan): _supported = the plan succeeds, nothing launched; _multi launches
+// from the same plan (SV_E_UNSUPPORTED where it does not succeed).  All need the slab workspace (wgrad_host.h: WgradSlabs).
+// rolling-window form for the 6x6 conv over an upsampled 64-channel input (d4; wgrad_roll.hip)
 bool svk_wgrad_roll_supported(const WgradArgs* w, int n);
 int svk_wgrad_roll_multi(const WgradArgs* w, int n, hipStream_t st);
-// rolling-window form of the polyphase main term of the head's weight gradient (d5; wgrad_p5.hip): needs the slab workspace
+// rolling-window form of the polyphase main term of the head's weight gradient (d5; wgrad_p5.hip)
 bool svk_wgrad_p5_supported(const WgradArgs* w, int n);
 int svk_wgrad_p5_multi(const WgradArgs* w, int n, hipStream_t st);
-// e1's weight gradient, one pipeline per wave (wgrad_e1.hip): needs the slab workspace
+// e1's weight gradient, one pipeline per wave (wgrad_e1.hip)
 bool svk_wgrad_e1_supported(const WgradArgs* w, int n);
 int svk_wgrad_e1_multi(const WgradArgs* w, int n, hipStream_t st);
-// e2's weight gradient, rolling window over the space-to-depth input (wgrad_e2.hip): needs the slab workspace
+// e2's weight gradient, rolling window over the space-to-depth input (wgrad_e2.hip)
 bool svk_wgrad_e2_supported(const WgradArgs* w, int n);
 int svk_wgrad_e2_multi(const WgradArgs* w, int n, hipStream_t st);
 struct WgradTileMulti { WgradTileArgs a[SV_WGRAD_MAX_MULTI]; };     // blockIdx.z selects the problem
 struct WgradReduceMulti { const float* slab[SV_WGRAD_MAX_MULTI]; float* dW[SV_WGRAD_MAX_MULTI]; const float* bslab[SV_WGRAD_MAX_MULTI]; float* dbias[SV_WGRAD_MAX_MULTI]; };
-// fp32 (the reference's precision): LDS tiles + v_mfma_f32_16x16x4_f32 + the same slabs (wgrad_tile_f32.hip); SV_E_UNSUPPORTED -> im2col kernel
+// fp32 (the reference's precision): LDS tiles + v_mfma_f32_16x16x4_f32 + the same slabs (wgrad_tile_f32.hip); SV_E_UNSUPPORTED (nothing launched) -> im2col kernel
 int svk_wgrad_tile_f32_multi(const WgradArgs* w, int n, hipStream_t st);
 // the four parity classes of n <= 2 per-class polyphase layers in one launch (cls[c * n + i]); appends the 4 n slab-reduce descriptors
 int svk_wgrad_polyc_f32_multi(const WgradArgs* cls, int n, int mask, WgradReduceDesc* rd, int* nrd, hipStream_t st);
-int svk_wgrad_tile(const WgradArgs& w, hipStream_t st);   // SV_E_UNSUPPORTED -> use svk_wgrad
-int svk_wgrad_tile_multi(const WgradArgs* w, int n, hipStream_t st);   // n twin layers, one launch (own ws each)
+// the bf16 tile kernel alone (wgrad_tile.hip): n twin layers, one launch (own ws each); called through the chain below, which checks its preconditions
+int svk_wgrad_tile_multi(const WgradArgs* w, int n, hipStream_t st);
+// ---- wgrad_dispatch.hip (no kernels)
+// the bf16 form chain: the first of wgrad_roll, wgrad_p5, wgrad_e1, wgrad_e2, wgrad_tile that takes the n twin layers; SV_E_UNSUPPORTED (nothing launched)
+// when none does.  Called directly for the polyphase main term (svg_poly_wgrad_args: wgrad_p5 or wgrad_tile), which has no im2col form
+int svk_wgrad_bf16_forms_multi(const WgradArgs* w, int n, hipStream_t st);
+// the chain (bf16) / svk_wgrad_tile_f32_multi (fp32), the im2col kernel where they refuse; SV_E_UNSUPPORTED: a view or fusion only the LDS-tile forms have
 int svk_wgrad_dispatch_multi(const WgradArgs* w, int n, int dtype, int cfg, hipStream_t st);
-// tile kernel when the layer has an instantiation (bf16), im2col kernel otherwise
-int svk_wgrad_dispatch(const WgradArgs& w, int dtype, int cfg, hipStream_t st);
-#define SV_WGRAD_WS_BYTES (512LL * 36 * 4 * 256 * 4 + 512LL * 128 * 4)   // 512 workgroups x 36 fragments x 4 waves x 256 floats + their bias partials
+int svk_wgrad_dispatch(const WgradArgs& w, int dtype, int cfg, hipStream_t st);   // = svk_wgrad_dispatch_multi(&w, 1, ...)
+// bytes of a layer's partial-sum workspace.  How a launch carves it is defined in ONE place, wgrad_host.h's WgradSlabs; this is WgradSlabs(512, 1, 36 * 4 * 256)
+// .bytes(): 512 workgroup rows x 36 fragments x 4 waves x 256 floats + their bias partials (a launcher whose carve does not fit refuses, or flushes with atomics)
+#define SV_WGRAD_WS_BYTES (512LL * (36 * 4 * 256 + 128) * 4)
 
 // ---- the latent block's GEMMs (latent_gemm.hip): out [M, N] = A [M, K] . W^T, A and the prepared image W [N, K] K-contiguous
 struct NtGemmProb {

@@ -140,12 +140,8 @@ __global__ __launch_bounds__(256) void nt_gemm_kernel(const NtGemmMulti mg) {
 // The same tile with a RING of NS phase slots (big-K slices: several phases per workgroup, one workgroup per CU, so nothing else hides a
 // phase's transfer time): phase ph + NS - 1 is issued right after the barrier that retires phase ph - 1, i.e. NS - 1 phases are in flight
 // beside the MFMAs of phase ph.  The transfers are inline assembly with counted waits (the compiler would order every LDS read behind a
-// DMA builtin's vmcnt(0): wgrad_roll.hip); every wave issues the same PER instructions per phase, so "all but the youngest PER * n"
+// DMA builtin's vmcnt(0): common.hip.h, lds_dma16); every wave issues the same PER instructions per phase, so "all but the youngest PER * n"
 // is exactly "phase ph has landed".  K-slice slabs only (bias / activation belong to the consumer).
-__device__ __forceinline__ void nt_dma16(const void* base, uint32_t off, const char* lds) {     // base: wave-uniform; off: this lane's byte offset
-  const uint32_t l = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(l) : "memory", "m0");
-}
 
 template <typename T, int BM, int NS>
 __global__ __launch_bounds__(256) void nt_gemm_ring_kernel(const NtGemmMulti mg) {
@@ -186,9 +182,9 @@ __global__ __launch_bounds__(256) void nt_gemm_ring_kernel(const NtGemmMulti mg)
     char* sW = sA + BM * RB;
     const uint32_t kb = (uint32_t)ph * RB;
 #pragma unroll
-    for (int i = 0; i < BM / 16; ++i) nt_dma16(g.A, offA[i] + kb, sA + (wave + 4 * i) * (4 * RB));
+    for (int i = 0; i < BM / 16; ++i) lds_dma16(g.A, offA[i] + kb, sA + (wave + 4 * i) * (4 * RB));
 #pragma unroll
-    for (int i = 0; i < BN / 16; ++i) nt_dma16(g.W, offW[i] + kb, sW + (wave + 4 * i) * (4 * RB));
+    for (int i = 0; i < BN / 16; ++i) lds_dma16(g.W, offW[i] + kb, sW + (wave + 4 * i) * (4 * RB));
   };
 #pragma unroll
   for (int i = 0; i < NS - 1; ++i)
@@ -358,10 +354,6 @@ int svk_nt_slab_reduce(const NtGemmProb* p, float* const* out, int n, hipStream_
 // no atomics; the workgroups of the first Kw tile also produce dbias (an all-ones MFMA tap on the dY fragments).
 namespace {
 
-__device__ __forceinline__ short4_t tn_tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(p));
-}
-
 __global__ __launch_bounds__(256) void tn_wgrad_kernel(const TnWgradMulti mg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const TnWgradProb& g = mg.p[blockIdx.z];
@@ -411,14 +403,14 @@ __global__ __launch_bounds__(256) void tn_wgrad_kernel(const TnWgradMulti mg) {
       for (int i = 0; i < 4; ++i) {
         const int col = wm + i * 16 + 4 * lp;
         const char* p = sA + mrow * 256 + ((((col >> 3) ^ sw)) << 4) + (col & 7) * 2;
-        const short4_t lo = tn_tr16(p), hi = tn_tr16(p + 16 * 256);
+        const short4_t lo = lds_tr16(p), hi = lds_tr16(p + 16 * 256);
         af[i] = (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int col = wn + j * 16 + 4 * lp;
         const char* p = sB + mrow * 256 + ((((col >> 3) ^ sw)) << 4) + (col & 7) * 2;
-        const short4_t lo = tn_tr16(p), hi = tn_tr16(p + 16 * 256);
+        const short4_t lo = lds_tr16(p), hi = lds_tr16(p + 16 * 256);
         bf[j] = (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       }
 #pragma unroll
@@ -487,9 +479,9 @@ __global__ __launch_bounds__(256) void tn_wgrad_f32_kernel(const TnWgradMulti mg
   auto issue = [&](int ph, int slot) {
     char* sX = smem + slot * SLOTB;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) nt_dma16(g.X, offX[i] + (uint32_t)ph * phX, sX + (wave + 4 * i) * 1024);
+    for (int i = 0; i < 4; ++i) lds_dma16(g.X, offX[i] + (uint32_t)ph * phX, sX + (wave + 4 * i) * 1024);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) nt_dma16(g.dY, offY[i] + (uint32_t)ph * phY, sX + OPB + (wave + 4 * i) * 1024);
+    for (int i = 0; i < 4; ++i) lds_dma16(g.dY, offY[i] + (uint32_t)ph * phY, sX + OPB + (wave + 4 * i) * 1024);
   };
   const int nph = g.M / PR;                          // (M is a multiple of 32: svk_tn_wgrad_supported)
   issue(0, 0);

@@ -821,7 +821,7 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
     }
     Scope sc(p, st, nm, fl, by);
     { double is = 0; for (int i = 0; i < n; ++i) is += poly_issued(L[i]->d, 100, false); sc.issued(is); }
-    SV_TRY(svk_wgrad_tile_multi(a, n, st));
+    SV_TRY(svk_wgrad_bf16_forms_multi(a, n, st));        // wgrad_p5 or wgrad_tile
     const sv_conv_desc& d = L[0]->d;
     return svk_poly_wgrad_finish(n, x, dy, pw, dwv, dbv, d.B, d.H / 2, d.W / 2, d.ldx, Cin, d.Cout, SV_POLY_WGRAD_NWG, st);
   }

@@ -19,10 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ short4_t tr16p(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(p));
-}
-
 struct PolyWgradMulti { const bf16_t* x[2]; const bf16_t* dy[2]; float* slab[2]; };
 
 // blocks: (line, class pair): 0 top (0,1) | 1 bottom (2,3) | 2 bottom (4,-) | 3 left (5,6) | 4 right (7,8) | 5 right (9,-)
@@ -101,14 +97,14 @@ __global__ __launch_bounds__(384) void poly_wgrad_frame_kernel(const PolyWgradMu
     const char* lineb = sLine + bl * LW * PSL;
     const char* dyblk = sDy + wave * L * 32;
     for (int kc = 0; kc < npos / 32; ++kc) {
-      const short4_t blo = tr16p(dyblk + (kc * 32 + r) * 32 + 8 * lp), bhi = tr16p(dyblk + (kc * 32 + 16 + r) * 32 + 8 * lp);
+      const short4_t blo = lds_tr16(dyblk + (kc * 32 + r) * 32 + 8 * lp), bhi = lds_tr16(dyblk + (kc * 32 + 16 + r) * 32 + 8 * lp);
       const short8_t bfr = (short8_t){blo[0], blo[1], blo[2], blo[3], bhi[0], bhi[1], bhi[2], bhi[3]};
 #pragma unroll
       for (int t = 0; t < 6; ++t)
 #pragma unroll
         for (int i = 0; i < CIF; ++i) {
-          const short4_t alo = tr16p(lineb + (kc * 32 + r + t) * PSL + 8 * lp + i * 32);
-          const short4_t ahi = tr16p(lineb + (kc * 32 + 16 + r + t) * PSL + 8 * lp + i * 32);
+          const short4_t alo = lds_tr16(lineb + (kc * 32 + r + t) * PSL + 8 * lp + i * 32);
+          const short4_t ahi = lds_tr16(lineb + (kc * 32 + 16 + r + t) * PSL + 8 * lp + i * 32);
           const short8_t af = (short8_t){alo[0], alo[1], alo[2], alo[3], ahi[0], ahi[1], ahi[2], ahi[3]};
           acc[t][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, bfr), acc[t][i], 0, 0, 0);
         }

@@ -324,16 +324,8 @@ __device__ __forceinline__ void stage_rows_dma(const RowConvArgs& g, int b, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- MB (RowCfg::MB)
-// 64 lanes x 16 B, global -> LDS (lane l lands at lds + 16 l), as inline assembly: behind the DMA builtin the compiler orders every later
-// LDS read of an object the DMA may alias behind s_waitcnt vmcnt(0) -- the whole ring here -- which would park the wave on its newest
-// transfer at the first fragment read (wgrad_roll.hip has the same helper).  The only waits are the counted ones at the end of a step.
-__device__ __forceinline__ void rc_dma16(const void* base, uint32_t off, const char* lds) {    // base: wave-uniform; off: this lane's byte offset
-  const uint32_t l = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(l) : "memory", "m0");
-}
-__device__ __forceinline__ short4_t rc_tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(p));
-}
+// The rows arrive by lds_dma16 (common.hip.h: inline assembly, so the whole ring is not ordered behind vmcnt(0) at the first fragment read);
+// the only waits are the counted ones at the end of a step.
 
 // The problem's geometry BY VALUE, read once per unit: a RowConvArgs reference is a pointer into the kernel-argument segment, and every
 // use inside the step loop became a scalar load + wait (with one wave per SIMD nothing hides them: ~2 000 cycles per step)
@@ -346,7 +338,7 @@ __device__ __forceinline__ void mb_dma_half(const MbGeom& g, int b, int r, int h
   static_assert(PPI * 2 == C::WIDTH / 2, "two instructions per raw row");
   const bf16_t* rowp = g.A + (((int64_t)b * g.LH + r) * g.LW + hf * PPI) * g.lda;    // wave-uniform
   const uint32_t off = (uint32_t)(((lane / (64 / PPI)) * g.lda + (lane % (64 / PPI)) * 8) * 2);
-  rc_dma16(rowp, off, sRaw + (r % C::NRAW) * C::RAWB + hf * 1024);
+  lds_dma16(rowp, off, sRaw + (r % C::NRAW) * C::RAWB + hf * 1024);
 }
 // rows [r0, r1] (clamped to the image by the caller), two instructions each, dealt round-robin to the waves
 template <typename C>
@@ -402,8 +394,8 @@ __device__ __forceinline__ void mb_blend_rows(const MbGeom& g, int bb0, int Ya, 
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
       const int rlo = min(max(bb0 + k, 0), LH - 1), rhi = min(max(bb0 + k + 1, 0), LH - 1);
-      a_lo[k] = rc_tr16(sRaw + (rlo % C::NRAW) * C::RAWB + ml.rd + f * 32);
-      a_hi[k] = rc_tr16(sRaw + (rhi % C::NRAW) * C::RAWB + ml.rd + f * 32);
+      a_lo[k] = lds_tr16(sRaw + (rlo % C::NRAW) * C::RAWB + ml.rd + f * 32);
+      a_hi[k] = lds_tr16(sRaw + (rhi % C::NRAW) * C::RAWB + ml.rd + f * 32);
     }
     f32x4 dd[NB][2][C::NSG];
 #pragma unroll

@@ -10,10 +10,6 @@
 #include "common.hip.h"
 #include "kernels.h"
 
-__device__ __forceinline__ short4_t lds_tr16_b64(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(p));
-}
-
 template <typename T, int WR, int WC, int CF>
 __global__ __launch_bounds__(256) void wgrad_kernel(const WgradMulti mg) {
   // several independent problems per launch (tap_gemm.hip has the same scheme): blockIdx.z = (problem, m-split)
@@ -139,13 +135,13 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradMulti mg) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const char* p = cA + mrow * SA + (wr * 64 + i * 16 + 4 * lp) * 2;
-          const short4_t lo = lds_tr16_b64(p), hi = lds_tr16_b64(p + 16 * SA);
+          const short4_t lo = lds_tr16(p), hi = lds_tr16(p + 16 * SA);
           af[i] = (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         }
 #pragma unroll
         for (int j = 0; j < CF; ++j) {
           const char* p = cB + mrow * SB + ((wc * CF + j) * 16 + 4 * lp) * 2;
-          const short4_t lo = lds_tr16_b64(p), hi = lds_tr16_b64(p + 16 * SB);
+          const short4_t lo = lds_tr16(p), hi = lds_tr16(p + 16 * SB);
           bfr[j] = (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         }
 #pragma unroll

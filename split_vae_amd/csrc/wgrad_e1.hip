@@ -23,6 +23,7 @@
 #include <string.h>
 #include "common.hip.h"
 #include "kernels.h"
+#include "wgrad_host.h"
 
 namespace {
 
@@ -34,14 +35,6 @@ struct E1Args {
   int B, ntasks;          // ntasks = 2 B (image, strip)
 };
 struct E1Multi { E1Args a[SV_WGRAD_MAX_MULTI]; };
-
-__device__ __forceinline__ void dma16(const void* base, uint32_t off, const char* lds) {     // see wgrad_roll.hip
-  const uint32_t l = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(l) : "memory", "m0");
-}
-__device__ __forceinline__ short4_t tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(p));
-}
 
 constexpr int IH = 64, IW = 64, OH = 32, OW = 32;
 constexpr int ROWB = 608;                     // an input row of the strip: 36 pixels x 16 B (+ 32)
@@ -97,12 +90,12 @@ __global__ __launch_bounds__(512, 1) void wgrad_e1_kernel(const E1Multi mg) {
       const bf16_t* rowb = g.A + ((int64_t)b * IH + (in ? r : 0)) * IW * 8;
       char* dst = in ? slot + k * ROWB : my + NSL * SLOT;        // rows outside the image: the transfer goes to the dump row ...
       if (!in && lane < 36) *(uint4*)(slot + k * ROWB + lane * 16) = make_uint4(0, 0, 0, 0);     // ... and the slot gets zeros
-      if (lane_on) dma16(rowb, (uint32_t)col * 16u, dst);       // ONE instruction per row whatever the mask (never empty): produce_wait counts them
+      if (lane_on) lds_dma16(rowb, (uint32_t)col * 16u, dst);       // ONE instruction per row whatever the mask (never empty): produce_wait counts them
     }
     const int y = 2 * max(ps, 0);
     const bf16_t* src = g.dY + (((int64_t)b * OH + y) * OW + x0) * 32;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) dma16(src + (int64_t)h * OW * 32, (uint32_t)((lane >> 2) * 32 + (lane & 3) * 8) * 2u, slot + IN_SLOT + h * 1024);
+    for (int h = 0; h < 2; ++h) lds_dma16(src + (int64_t)h * OW * 32, (uint32_t)((lane >> 2) * 32 + (lane & 3) * 8) * 2u, slot + IN_SLOT + h * 1024);
     if (pk < ntask_w - 1 || ps < HS - 1) { if (++ps == HS) { ps = -1; ++pk; } }
   };
 
@@ -121,15 +114,15 @@ __global__ __launch_bounds__(512, 1) void wgrad_e1_kernel(const E1Multi mg) {
         for (int py = 0; py < 2; ++py) {
           win[0][tx][py] = win[2][tx][py];
           win[1][tx][py] = win[3][tx][py];
-          win[2][tx][py] = tr16(slot + (0 * 2 + py) * ROWB + (pxl + tx) * 32 + lp * 8);
-          win[3][tx][py] = tr16(slot + (1 * 2 + py) * ROWB + (pxl + tx) * 32 + lp * 8);
+          win[2][tx][py] = lds_tr16(slot + (0 * 2 + py) * ROWB + (pxl + tx) * 32 + lp * 8);
+          win[3][tx][py] = lds_tr16(slot + (1 * 2 + py) * ROWB + (pxl + tx) * 32 + lp * 8);
         }
       if (ms >= 0) {
         const char* sd = slot + IN_SLOT + pxl * 64 + lp * 8;
         short8_t bfr[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const short4_t lo = tr16(sd + j * 32), hi = tr16(sd + 1024 + j * 32);
+          const short4_t lo = lds_tr16(sd + j * 32), hi = lds_tr16(sd + 1024 + j * 32);
           bfr[j] = (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         }
 #pragma unroll
@@ -191,54 +184,48 @@ __global__ __launch_bounds__(512, 1) void wgrad_e1_kernel(const E1Multi mg) {
   }
 }
 
-int e1_wgs(int n, int ntasks) {               // workgroups per problem: 8 waves each, one per CU over the launch
-  int X = 256 / n;
-  const int cap = (ntasks + 7) / 8;
-  if (X > cap) X = cap;
-  return X < 1 ? 1 : X;
-}
-
-}  // namespace
-
-bool svk_wgrad_e1_supported(const WgradArgs* wv, int n) {
+bool e1_plan(const WgradArgs* wv, int n, WgradStripPlan* p) {
   const bool off = sv_knob_no_wgrad_e1();
   if (off || n < 1 || n > SV_WGRAD_MAX_MULTI) return false;
   const WgradArgs& w = wv[0];
   if (w.ups || w.S != 2 || w.SX != 2 || w.ntaps != 36 || w.Cin_pad != 8 || w.lda != 8 || w.ldy != 32 || w.ycols != 32 || w.N != 32) return false;
   if (w.fold_kw || w.clampin || w.dy_s2d || w.assign) return false;
   if (w.OY != OH || w.OX != OW || w.IH != IH || w.IW != IW || w.Cin_real > 8) return false;
-  for (int t = 0; t < 36; ++t)
-    if (w.dy[t] != t / 6 - 2 || w.dx[t] != t % 6 - 2) return false;
-  const int B = w.M / (OH * OW);
+  if (!wgrad_taps_are_window(w, 6, 2)) return false;
+  p->B = w.M / (OH * OW);
+  p->units = 2 * p->B;                         // tasks: (image, strip)
   static const int min_tasks = SV_TUNE_INT("SV_WGRAD_E1_MIN", 512);
-  if (n * 2 * B < min_tasks) return false;     // small launches: too few strips for the waves of the chip (the tile kernel cuts 2-D tiles)
-  const int X = e1_wgs(n, 2 * B);
-  const int64_t need = (int64_t)X * 4 * 10 * 256 * 4 + (int64_t)X * 128 * 4;
-  for (int i = 0; i < n; ++i)
-    if (!wv[i].ws || wv[i].ws_bytes < need) return false;
-  return true;
+  if (n * p->units < min_tasks) return false;  // small launches: too few strips for the waves of the chip (the tile kernel cuts 2-D tiles)
+  int X = 256 / n;                             // workgroups per problem: 8 waves each, one per CU over the launch
+  const int cap = (p->units + 7) / 8;
+  if (X > cap) X = cap;
+  p->wgs = X < 1 ? 1 : X;
+  p->slabs = WgradSlabs{p->wgs, 1, 4 * 10 * 256};
+  return p->slabs.fits(wv, n);
 }
 
+}  // namespace
+
+bool svk_wgrad_e1_supported(const WgradArgs* wv, int n) { WgradStripPlan p; return e1_plan(wv, n, &p); }
+
 int svk_wgrad_e1_multi(const WgradArgs* wv, int n, hipStream_t st) {
-  if (!svk_wgrad_e1_supported(wv, n)) return SV_E_UNSUPPORTED;
+  WgradStripPlan p;
+  if (!e1_plan(wv, n, &p)) return SV_E_UNSUPPORTED;
   const WgradArgs& w = wv[0];
-  const int B = w.M / (OH * OW);
-  const int X = e1_wgs(n, 2 * B);
   E1Multi m;
   WgradReduceDesc rd[SV_WGRAD_MAX_MULTI];
   for (int i = 0; i < n; ++i) {
     E1Args& a = m.a[i];
     a.A = (const bf16_t*)wv[i].A; a.dY = (const bf16_t*)wv[i].dY;
     a.slab = wv[i].ws;
-    a.bslab = wv[i].dbias ? wv[i].ws + (int64_t)X * 4 * 10 * 256 : nullptr;
-    a.B = B; a.ntasks = 2 * B;
+    a.bslab = wv[i].dbias ? p.slabs.bias_part(wv[i].ws) : nullptr;
+    a.B = p.B; a.ntasks = p.units;
     // the reduce of the tile kernel's pairx form: 18 tap entries (ky, kx / 2), rows 8..15 of a fragment = the odd kx
-    rd[i] = WgradReduceDesc{a.slab, wv[i].dW, a.bslab, wv[i].dbias, X, 1, 1, 8, w.Cin_real, 32, 18, 0, 0, 1, 0, 5, 1, 2};
+    rd[i] = WgradReduceDesc{a.slab, wv[i].dW, a.bslab, wv[i].dbias, p.wgs, 1, 1, 8, w.Cin_real, 32, 18, 0, 0, 1, 0, 5, 1, 2};
   }
   const size_t lds = 8 * WAVE_LDS;
   sv_ensure_dynamic_lds((const void*)wgrad_e1_kernel, lds);
-  hipLaunchKernelGGL(wgrad_e1_kernel, dim3(X, 1, n), dim3(512), lds, st, m);
+  hipLaunchKernelGGL(wgrad_e1_kernel, dim3(p.wgs, 1, n), dim3(512), lds, st, m);
   SV_LAUNCH_CHECK();
-  if (w.ev_mid[0]) { (void)hipEventRecord(w.ev_mid[0], st); (void)hipEventRecord(w.ev_mid[1], st); }
-  return svk_wgrad_reduce_all(rd, n, st);
+  return wgrad_finish(w, rd, n, st);
 }

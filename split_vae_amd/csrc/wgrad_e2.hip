@@ -21,6 +21,7 @@
 #include <string.h>
 #include "common.hip.h"
 #include "kernels.h"
+#include "wgrad_host.h"
 
 namespace {
 
@@ -32,14 +33,6 @@ struct E2Args {
   int B;
 };
 struct E2Multi { E2Args a[SV_WGRAD_MAX_MULTI]; };
-
-__device__ __forceinline__ void dma16(const void* base, uint32_t off, const char* lds) {     // see wgrad_roll.hip
-  const uint32_t l = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(l) : "memory", "m0");
-}
-__device__ __forceinline__ short4_t tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(p));
-}
 
 constexpr int IH = 32, IW = 32, OH = 16, OW = 16, CI = 32, CO = 64;
 constexpr int ROWB = 36 * 64;                 // an input row of the strip: 36 pixels (s2d columns -1 .. 16) x 64 B
@@ -103,13 +96,13 @@ __global__ __launch_bounds__(512, 1) void wgrad_e2_kernel(const E2Multi mg) {
         const bf16_t* rowb = g.A + ((int64_t)pb * IH + (in ? r : 0)) * IW * CI;
         const uint32_t off = (uint32_t)(col * 64 + (u32 & 1) * 32 + (q & 1) * 16);
         if (!in && q < 144) *(uint4*)(slot + k * ROWB + q * 16) = make_uint4(0, 0, 0, 0);
-        if (lane_on) dma16(rowb, off, in ? slot + k * ROWB + seg * 1024 : dump);
+        if (lane_on) lds_dma16(rowb, off, in ? slot + k * ROWB + seg * 1024 : dump);
       } else {
         const int h = (job - 12) >> 1, hf = (job - 12) & 1;
         const int y = 2 * max(ps, 0) + h;
         const int q = hf * 64 + lane, px = q >> 3, pos = (q >> 1) & 3, j = pos ^ ((px >> 1) & 3);       // position -> pixel, source unit
         const bf16_t* src = g.dY + (((int64_t)pb * OH + y) * OW) * CO;
-        dma16(src, (uint32_t)(px * 128 + j * 32 + (q & 1) * 16), slot + IN_SLOT + h * 2048 + hf * 1024);
+        lds_dma16(src, (uint32_t)(px * 128 + j * 32 + (q & 1) * 16), slot + IN_SLOT + h * 2048 + hf * 1024);
       }
     }
     if (pb < b_hi - 1 || ps < HS - 1) { if (++ps == HS) { ps = -1; ++pb; } }
@@ -132,15 +125,15 @@ __global__ __launch_bounds__(512, 1) void wgrad_e2_kernel(const E2Multi mg) {
       for (int tx = 0; tx < 3; ++tx) {
         win[0][tx] = win[2][tx];
         win[1][tx] = win[3][tx];
-        win[2][tx] = tr16(r0 + aoff[tx]);
-        win[3][tx] = tr16(r1 + aoff[tx]);
+        win[2][tx] = lds_tr16(r0 + aoff[tx]);
+        win[3][tx] = lds_tr16(r1 + aoff[tx]);
       }
       if (ms >= 0) {
         const char* sd = slot + IN_SLOT;
         short8_t bfr[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const short4_t lo = tr16(sd + boff[j]), hi = tr16(sd + 2048 + boff[j]);
+          const short4_t lo = lds_tr16(sd + boff[j]), hi = lds_tr16(sd + 2048 + boff[j]);
           bfr[j] = (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         }
 #pragma unroll
@@ -182,51 +175,44 @@ __global__ __launch_bounds__(512, 1) void wgrad_e2_kernel(const E2Multi mg) {
   if (g.bslab && wave < 4 && lane < 16) g.bslab[(int64_t)blockIdx.x * 128 + wave * 16 + lane] = bacc[0];
 }
 
-int e2_wgs(int n, int B) {
-  int X = 256 / n;
-  if (X > B) X = B;
-  return X < 1 ? 1 : X;
-}
-
-}  // namespace
-
-bool svk_wgrad_e2_supported(const WgradArgs* wv, int n) {
+// workgroups per problem: one 8-wave workgroup per CU over the launch, at most one per image
+bool e2_plan(const WgradArgs* wv, int n, WgradStripPlan* p) {
   const bool off = sv_knob_no_wgrad_e2();
   if (off || n < 1 || n > SV_WGRAD_MAX_MULTI) return false;
   const WgradArgs& w = wv[0];
   if (w.ups || w.S != 2 || w.SX != 2 || w.ntaps != 36 || w.Cin_pad != CI || w.Cin_real != CI || w.lda != CI || w.ldy != CO || w.ycols != CO || w.N != CO) return false;
   if (w.fold_kw || w.clampin || w.dy_s2d || w.assign) return false;
   if (w.OY != OH || w.OX != OW || w.IH != IH || w.IW != IW) return false;
-  for (int t = 0; t < 36; ++t)
-    if (w.dy[t] != t / 6 - 2 || w.dx[t] != t % 6 - 2) return false;
-  const int B = w.M / (OH * OW);
+  if (!wgrad_taps_are_window(w, 6, 2)) return false;
+  p->B = p->units = w.M / (OH * OW);
   const int min_images = sv_knob_wgrad_e2_min();
-  if (n * B < min_images) return false;        // small launches: a workgroup per image leaves the chip idle and still writes a full slab each
-  const int X = e2_wgs(n, B);
-  const int64_t need = (int64_t)X * 4 * 72 * 256 * 4 + (int64_t)X * 128 * 4;
-  for (int i = 0; i < n; ++i)
-    if (!wv[i].ws || wv[i].ws_bytes < need) return false;
-  return true;
+  if (n * p->B < min_images) return false;     // small launches: a workgroup per image leaves the chip idle and still writes a full slab each
+  int X = 256 / n;
+  if (X > p->B) X = p->B;
+  p->wgs = X < 1 ? 1 : X;
+  p->slabs = WgradSlabs{p->wgs, 1, 4 * 72 * 256};
+  return p->slabs.fits(wv, n);
 }
 
+}  // namespace
+
+bool svk_wgrad_e2_supported(const WgradArgs* wv, int n) { WgradStripPlan p; return e2_plan(wv, n, &p); }
+
 int svk_wgrad_e2_multi(const WgradArgs* wv, int n, hipStream_t st) {
-  if (!svk_wgrad_e2_supported(wv, n)) return SV_E_UNSUPPORTED;
-  const WgradArgs& w = wv[0];
-  const int B = w.M / (OH * OW);
-  const int X = e2_wgs(n, B);
+  WgradStripPlan p;
+  if (!e2_plan(wv, n, &p)) return SV_E_UNSUPPORTED;
   E2Multi m;
   WgradReduceDesc rd[SV_WGRAD_MAX_MULTI];
   for (int i = 0; i < n; ++i) {
     E2Args& a = m.a[i];
     a.A = (const bf16_t*)wv[i].A; a.dY = (const bf16_t*)wv[i].dY;
     a.slab = wv[i].ws;
-    a.bslab = wv[i].dbias ? wv[i].ws + (int64_t)X * 4 * 72 * 256 : nullptr;
-    a.B = B;
-    rd[i] = WgradReduceDesc{a.slab, wv[i].dW, a.bslab, wv[i].dbias, X, 1, 1, CI, CI, CO, 36, 0, 0, 0, 0, 9, 2, 4};
+    a.bslab = wv[i].dbias ? p.slabs.bias_part(wv[i].ws) : nullptr;
+    a.B = p.B;
+    rd[i] = WgradReduceDesc{a.slab, wv[i].dW, a.bslab, wv[i].dbias, p.wgs, 1, 1, CI, CI, CO, 36, 0, 0, 0, 0, 9, 2, 4};
   }
   sv_ensure_dynamic_lds((const void*)wgrad_e2_kernel, LDS_BYTES);
-  hipLaunchKernelGGL(wgrad_e2_kernel, dim3(X, 1, n), dim3(512), LDS_BYTES, st, m);
+  hipLaunchKernelGGL(wgrad_e2_kernel, dim3(p.wgs, 1, n), dim3(512), LDS_BYTES, st, m);
   SV_LAUNCH_CHECK();
-  if (w.ev_mid[0]) { (void)hipEventRecord(w.ev_mid[0], st); (void)hipEventRecord(w.ev_mid[1], st); }
-  return svk_wgrad_reduce_all(rd, n, st);
+  return wgrad_finish(wv[0], rd, n, st);
 }

@@ -28,6 +28,7 @@
 #include <type_traits>
 #include "common.hip.h"
 #include "kernels.h"
+#include "wgrad_host.h"
 
 namespace {
 
@@ -39,14 +40,6 @@ struct P5Args {
   int B, h, w, lda, nxs, nstrips, per;      // per: strips per TEAM
 };
 struct P5Multi { P5Args a[SV_WGRAD_MAX_MULTI]; };
-
-__device__ __forceinline__ void p5_dma16(const void* base, uint32_t off, const char* lds) {    // base: wave-uniform; off: this lane's byte offset
-  const uint32_t l = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(l) : "memory", "m0");
-}
-__device__ __forceinline__ short4_t p5_tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(p));
-}
 
 constexpr int TW = 5, PADL = 2, NTAP = TW * TW;       // 5 x 5 taps, offsets -2 .. 2
 constexpr int XSLOT = 2048;                           // one staged input row: 32 pixels x 32 channels (pixel q <-> column clamp(j0 - 2 + q); 20 used)
@@ -100,14 +93,14 @@ __global__ __launch_bounds__(512, 1) void wgrad_p5_kernel(const P5Multi mg) {
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
         const int col = min(max(j0 - PADL + hf * 16 + (lane >> 2), 0), g.w - 1);
-        p5_dma16(rowb, (uint32_t)(col * g.lda + (lane & 3) * 8) * 2u, xs + wt * XSLOT + hf * 1024);
+        lds_dma16(rowb, (uint32_t)(col * g.lda + (lane & 3) * 8) * 2u, xs + wt * XSLOT + hf * 1024);
       }
     } else {
       // dY row i of the chunk of step ps (chunk s = ps - LEAD uses it; lead-in steps fetch rows of chunks that do not exist: clamped, unused)
       const int i = min(max(2 * (ps - LEAD) + (wt - 2), 0), g.h - 1);
       const int py = (lane >> 1) & 1, pxp = lane & 1, p = lane >> 2;
       const bf16_t* src = g.dY + ((int64_t)b * H2 + 2 * i) * W2 * 8;        // wave-uniform: hi-res row 2 i of the image
-      p5_dma16(src, (uint32_t)((py * W2 + 2 * (j0 + p) + pxp) * 8) * 2u, ds + (wt - 2) * DSLOT);
+      lds_dma16(src, (uint32_t)((py * W2 + 2 * (j0 + p) + pxp) * 8) * 2u, ds + (wt - 2) * DSLOT);
     }
     if (++ps == SPS) { ps = 0; ++pq; }
   };
@@ -144,8 +137,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_p5_kernel(const P5Multi mg) {
       const char* rp = sX + (t & (NDMA - 1)) * 2 * XSLOT + x_lane;
 #pragma unroll
       for (int x = 0; x < TW; ++x) {
-        const int2 r0 = __builtin_bit_cast(int2, p5_tr16(rp + (x - PADL) * 64));
-        const int2 r1 = __builtin_bit_cast(int2, p5_tr16(rp + XSLOT + (x - PADL) * 64));
+        const int2 r0 = __builtin_bit_cast(int2, lds_tr16(rp + (x - PADL) * 64));
+        const int2 r1 = __builtin_bit_cast(int2, lds_tr16(rp + XSLOT + (x - PADL) * 64));
         win[x][4 * PH] = r0.x; win[x][4 * PH + 1] = r0.y; win[x][4 * PH + 2] = r1.x; win[x][4 * PH + 3] = r1.y;
         if constexpr (PH == 0) { win[x][12] = r0.x; win[x][13] = r0.y; }
       }
@@ -153,7 +146,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_p5_kernel(const P5Multi mg) {
     const bool mm = ms >= LEAD && mq < q_hi;                                // wave-uniform: this step multiplies (not a lead-in step, not an idle team)
     if (mm) {
       const char* sd = sD + (t & (NDMA - 1)) * 2 * DSLOT + d_lane;
-      const short4_t d0 = p5_tr16(sd), d1 = p5_tr16(sd + DSLOT);
+      const short4_t d0 = lds_tr16(sd), d1 = lds_tr16(sd + DSLOT);
       const short8_t bfr = (short8_t){d0[0], d0[1], d0[2], d0[3], d1[0], d1[1], d1[2], d1[3]};
       // chunk rows (2s, 2s + 1), s = t' - 2 in pair units: tap ty's first row is register row 2 (t - 2) + (ty + 2) + ... of the walk = window row
       // rho = ty + 2 counted from the OLDEST pair (t - 2), whose slot is (PH + 1) % 3
@@ -213,16 +206,7 @@ constexpr int P5_LDS = 2 * (NDMA * 2 * XSLOT + NDMA * 2 * DSLOT) > (4 * NTAP * 2
 
 }  // namespace
 
-static int p5_wgs(int n, int nstrips, int* per) {
-  int X = 256 / n;                                     // one 8-wave workgroup per CU over the launch
-  int p = (nstrips + 2 * X - 1) / (2 * X);             // strips per team
-  if (p < 1) p = 1;
-  X = (nstrips + 2 * p - 1) / (2 * p);                 // no workgroup without work
-  *per = p;
-  return X < 1 ? 1 : X;
-}
-
-bool svk_wgrad_p5_supported(const WgradArgs* wv, int n) {
+static bool p5_plan(const WgradArgs* wv, int n, WgradStripPlan* p) {
   static const bool off = SV_TUNE_FLAG("SV_NO_WGRAD_P5");
   static const int min_images = SV_TUNE_INT("SV_WGRAD_P5_MIN", 128);
   if (off || n < 1 || n > SV_WGRAD_MAX_MULTI) return false;
@@ -230,38 +214,37 @@ bool svk_wgrad_p5_supported(const WgradArgs* wv, int n) {
   if (!w.dy_s2d || !w.clampin || !w.assign || w.ups || w.fold_kw || w.S != 1 || w.SX != 1 || w.ntaps != NTAP) return false;
   if (w.Cin_pad != 32 || w.Cin_real != 32 || w.N != 32 || w.ldy != 32 || w.lda != 32) return false;
   if (w.OY != w.OX || w.OY < 16 || (w.OY & 15) || w.lOY < 0 || ((w.OY / 2 + LEAD) % 3)) return false;      // steps per strip: a multiple of the window's rotation period
-  for (int t = 0; t < NTAP; ++t)
-    if (w.dx[t] != t / TW - PADL || w.dy[t] != t % TW - PADL) return false;
-  const int B = w.M >> (2 * w.lOY);
-  if (B * n < min_images) return false;
-  int per;
-  const int X = p5_wgs(n, B * (w.OX / 16), &per);
-  const int64_t need = (int64_t)X * 4 * NFRr * 256 * 4 + (int64_t)X * 128 * 4;
-  for (int i = 0; i < n; ++i)
-    if (!wv[i].ws || wv[i].ws_bytes < need) return false;
-  return true;
+  if (!wgrad_taps_are_window(w, TW, PADL, true)) return false;      // (svg_poly_wgrad_args lists the taps x-major)
+  p->B = w.M >> (2 * w.lOY);
+  if (p->B * n < min_images) return false;
+  p->units = p->B * (w.OX / 16);                       // 16-pixel column strips
+  int X = 256 / n;                                     // one 8-wave workgroup per CU over the launch
+  p->per = (p->units + 2 * X - 1) / (2 * X);           // strips per team
+  if (p->per < 1) p->per = 1;
+  X = (p->units + 2 * p->per - 1) / (2 * p->per);      // no workgroup without work
+  p->wgs = X < 1 ? 1 : X;
+  p->slabs = WgradSlabs{p->wgs, 1, 4 * NFRr * 256};
+  return p->slabs.fits(wv, n);
 }
 
+bool svk_wgrad_p5_supported(const WgradArgs* wv, int n) { WgradStripPlan p; return p5_plan(wv, n, &p); }
+
 int svk_wgrad_p5_multi(const WgradArgs* wv, int n, hipStream_t st) {
-  if (!svk_wgrad_p5_supported(wv, n)) return SV_E_UNSUPPORTED;
+  WgradStripPlan p;
+  if (!p5_plan(wv, n, &p)) return SV_E_UNSUPPORTED;
   const WgradArgs& w = wv[0];
-  const int B = w.M >> (2 * w.lOY);
-  const int nxs = w.OX / 16, nstrips = B * nxs;
-  int per;
-  const int X = p5_wgs(n, nstrips, &per);
   P5Multi m;
   WgradReduceDesc rd[SV_WGRAD_MAX_MULTI];
   for (int i = 0; i < n; ++i) {
     P5Args& a = m.a[i];
     a.A = (const bf16_t*)wv[i].A; a.dY = (const bf16_t*)wv[i].dY;
     a.slab = wv[i].ws;
-    a.bslab = wv[i].dbias ? wv[i].ws + (int64_t)X * 4 * NFRr * 256 : nullptr;
-    a.B = B; a.h = w.OY; a.w = w.OX; a.lda = w.lda; a.nxs = nxs; a.nstrips = nstrips; a.per = per;
-    rd[i] = WgradReduceDesc{a.slab, wv[i].dW, a.bslab, wv[i].dbias, X, 1, 1, 32, 32, 32, NTAP, 0, 0, 0, 1, TPWr, 2, 2};
+    a.bslab = wv[i].dbias ? p.slabs.bias_part(wv[i].ws) : nullptr;
+    a.B = p.B; a.h = w.OY; a.w = w.OX; a.lda = w.lda; a.nxs = w.OX / 16; a.nstrips = p.units; a.per = p.per;
+    rd[i] = WgradReduceDesc{a.slab, wv[i].dW, a.bslab, wv[i].dbias, p.wgs, 1, 1, 32, 32, 32, NTAP, 0, 0, 0, 1, TPWr, 2, 2};
   }
   sv_ensure_dynamic_lds((const void*)wgrad_p5_kernel, P5_LDS);
-  hipLaunchKernelGGL(wgrad_p5_kernel, dim3(X, 1, n), dim3(512), P5_LDS, st, m);
+  hipLaunchKernelGGL(wgrad_p5_kernel, dim3(p.wgs, 1, n), dim3(512), P5_LDS, st, m);
   SV_LAUNCH_CHECK();
-  if (w.ev_mid[0]) { (void)hipEventRecord(w.ev_mid[0], st); (void)hipEventRecord(w.ev_mid[1], st); }
-  return svk_wgrad_reduce_all(rd, n, st);
+  return wgrad_finish(w, rd, n, st);
 }

@@ -36,6 +36,7 @@
 #include <type_traits>
 #include "common.hip.h"
 #include "kernels.h"
+#include "wgrad_host.h"
 
 namespace {
 
@@ -48,17 +49,7 @@ struct RollArgs {
 };
 struct RollMulti { RollArgs a[SV_WGRAD_MAX_MULTI]; };
 
-// 64 lanes x 16 B, global -> LDS (lane l lands at lds + 16 l), as inline assembly: the compiler orders every later read of an LDS object
-// a DMA builtin may have written behind s_waitcnt vmcnt(0), which would park the two producer waves on their NEWEST transfer every step;
-// here the only waits are the counted ones in produce_wait() (the consumers are other waves, behind the step barrier)
-__device__ __forceinline__ void dma16(const void* base, uint32_t off, const char* lds) {     // base: wave-uniform (SGPR pair); off: this lane's byte offset
-  const uint32_t l = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(l) : "memory", "m0");
-}
-__device__ __forceinline__ short4_t tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(p));
-}
-
+// (the DMAs are lds_dma16 of common.hip.h: the only waits are the counted ones in produce_wait(); the consumers are other waves, behind the step barrier)
 // -DSV_ROLL_STAMP (diagnostic builds): every wave of workgroup 0 records the shader clock at NSTAMP points of steps STAMP_T0 .. +3 and
 // the workgroup overwrites the head of its slab with them (results are then wrong; scripts/r03_roll_stamps.py prints the timeline)
 // -DROLL_ABL=<mask> (diagnostic builds, wrong results): 1 no MFMAs, 2 no blend, 4 no DMA, 8 no window reads, 16 no step barrier, 32 no flush
@@ -123,7 +114,7 @@ __device__ __forceinline__ void roll_loop(const RollArgs& g, const RollLds& L, f
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int col = min(max(jlo + h * 8 + (lane >> 3), 0), LW - 1);
-        dma16(rowb, (uint32_t)(col * g.lda + (lane & 7) * 8) * 2u, dst + h * 1024);
+        lds_dma16(rowb, (uint32_t)(col * g.lda + (lane & 7) * 8) * 2u, dst + h * 1024);
       }
     } else {
       const int y = 2 * max(ps, 0);
@@ -131,7 +122,7 @@ __device__ __forceinline__ void roll_loop(const RollArgs& g, const RollLds& L, f
       const char* dst = L.dy + (u & (NDMA - 1)) * DY_SLOT;
       const uint32_t off = (uint32_t)((lane >> 2) * g.ldy + (lane & 3) * 8) * 2u;
 #pragma unroll
-      for (int h = 0; h < 2; ++h) dma16(src + (int64_t)h * g.OW * g.ldy, off, dst + h * 1024);
+      for (int h = 0; h < 2; ++h) lds_dma16(src + (int64_t)h * g.OW * g.ldy, off, dst + h * 1024);
     }
     if (pq < q_hi - 1 || ps < HS - 1) {
       if (++ps == HS) { ps = -LEAD; ++pq; px0 += 16; if (px0 == g.OW) { px0 = 0; ++pb; } }
@@ -188,8 +179,8 @@ __device__ __forceinline__ void roll_loop(const RollArgs& g, const RollLds& L, f
   int w_slot = 0, w_i = 0, w_x = 0;
   auto blend_load = [&](int u) {
     if (ROLL_ABL & 2) return;
-    ba_lo = tr16(L.raw + ((u - 1) & (NDMA - 1)) * RAW_SLOT + raw_lane);
-    ba_hi = tr16(L.raw + (u & (NDMA - 1)) * RAW_SLOT + raw_lane);
+    ba_lo = lds_tr16(L.raw + ((u - 1) & (NDMA - 1)) * RAW_SLOT + raw_lane);
+    ba_hi = lds_tr16(L.raw + (u & (NDMA - 1)) * RAW_SLOT + raw_lane);
     w_slot = (u & (NSLOT - 1)) * IN_SLOT; w_i = ws + 1; w_x = wx0 - PAD;
     if (++ws == HS) { ws = -LEAD; wx0 += 16; if (wx0 == g.OW) wx0 = 0; }
   };
@@ -272,8 +263,8 @@ __device__ __forceinline__ void roll_loop(const RollArgs& g, const RollLds& L, f
           for (int e = 0; e + 4 < 2 * (KS + 1); ++e) win[kx][e] = win[kx][e + 4];
         }
         if (!(ROLL_ABL & 8)) {
-          win_set(kx, std::integral_constant<int, P(KS - 1)>{}, tr16(rp + kx * PS));
-          win_set(kx, std::integral_constant<int, P(KS)>{}, tr16(rp + (PW + kx) * PS));
+          win_set(kx, std::integral_constant<int, P(KS - 1)>{}, lds_tr16(rp + kx * PS));
+          win_set(kx, std::integral_constant<int, P(KS)>{}, lds_tr16(rp + (PW + kx) * PS));
         }
       }
     }
@@ -316,7 +307,7 @@ __device__ __forceinline__ void roll_loop(const RollArgs& g, const RollLds& L, f
     if (ms >= 0) {                                                // the next step multiplies: its dY fragments (chunk t, published long ago)
       const char* sd = L.dy + (t & (NDMA - 1)) * DY_SLOT + dy_lane;
 #pragma unroll
-      for (int j = 0; j < COF; ++j) { nb[j][0] = tr16(sd + j * 32); nb[j][1] = tr16(sd + 1024 + j * 32); }
+      for (int j = 0; j < COF; ++j) { nb[j][0] = lds_tr16(sd + j * 32); nb[j][1] = lds_tr16(sd + 1024 + j * 32); }
     }
     ROLL_STAMP(5);
     if (t & 1) {                                                  // one barrier per two steps
@@ -401,49 +392,41 @@ __global__ __launch_bounds__(512, 1) void wgrad_roll_kernel(const RollMulti mg) 
 // workgroups wrote and re-read 75 MB for 19 steps of work each)
 // (round 4: with two strips or fewer per workgroup, half as many workgroups -- 64 images per network: two strips each, step 0.607 -> 0.600 ms; 128: four
 //  each, 0.766 -> 0.754; a forced minimum of strips per workgroup instead had no effect: profiles/r04_b64_sweep4.txt)
-static int roll_wgs(int n, int nstrips) {
-  int X = 256 / n;
-  if (nstrips <= 2 * X) X /= 2;
-  if (X > nstrips) X = nstrips;
-  return X < 1 ? 1 : X;
-}
-
-bool svk_wgrad_roll_supported(const WgradArgs* wv, int n) {
+static bool roll_plan(const WgradArgs* wv, int n, WgradStripPlan* p) {
   const bool off = sv_knob_no_wgrad_roll();
   if (off || n < 1 || n > SV_WGRAD_MAX_MULTI) return false;
   const WgradArgs& w = wv[0];
   if (!w.ups || w.S != 1 || w.SX != 1 || w.ntaps != NT || w.Cin_pad != 64 || w.Cin_real != 64 || w.ldy != 32 || w.ycols != 32 || w.N != 32) return false;
   if (w.fold_kw || w.clampin || w.dy_s2d || w.assign) return false;
   if (w.lOY < 1 || w.lOX < 4 || w.IH != w.OY || w.IW != w.OX) return false;
-  for (int t = 0; t < NT; ++t)
-    if (w.dy[t] != t / KS - PAD || w.dx[t] != t % KS - PAD) return false;
-  const int B = w.M >> (w.lOY + w.lOX);
-  const int nstrips = B * (w.OX / 16);
-  const int X = roll_wgs(n, nstrips);
-  const int64_t need = (int64_t)X * 4 * 72 * 256 * 4 + (int64_t)X * 128 * 4;
-  for (int i = 0; i < n; ++i)
-    if (!wv[i].ws || wv[i].ws_bytes < need) return false;
-  return true;
+  if (!wgrad_taps_are_window(w, KS, PAD)) return false;
+  p->B = w.M >> (w.lOY + w.lOX);
+  p->units = p->B * (w.OX / 16);               // 16-pixel column strips
+  int X = 256 / n;
+  if (p->units <= 2 * X) X /= 2;
+  if (X > p->units) X = p->units;
+  p->wgs = X < 1 ? 1 : X;
+  p->slabs = WgradSlabs{p->wgs, 1, 4 * 72 * 256};
+  return p->slabs.fits(wv, n);
 }
 
+bool svk_wgrad_roll_supported(const WgradArgs* wv, int n) { WgradStripPlan p; return roll_plan(wv, n, &p); }
+
 int svk_wgrad_roll_multi(const WgradArgs* wv, int n, hipStream_t st) {
-  if (!svk_wgrad_roll_supported(wv, n)) return SV_E_UNSUPPORTED;
+  WgradStripPlan p;
+  if (!roll_plan(wv, n, &p)) return SV_E_UNSUPPORTED;
   const WgradArgs& w = wv[0];
-  const int B = w.M >> (w.lOY + w.lOX);
   RollMulti m;
-  const int nxs = w.OX / 16, nstrips = B * nxs;
-  const int X = roll_wgs(n, nstrips);
   WgradReduceDesc rd[SV_WGRAD_MAX_MULTI];
   for (int i = 0; i < n; ++i) {
     RollArgs& a = m.a[i];
     a.A = (const bf16_t*)wv[i].A; a.dY = (const bf16_t*)wv[i].dY;
     a.slab = wv[i].ws;
-    a.bslab = wv[i].dbias ? wv[i].ws + (int64_t)X * 4 * 72 * 256 : nullptr;
-    a.B = B; a.OH = w.OY; a.OW = w.OX; a.lda = w.lda; a.ldy = w.ldy; a.nxs = nxs; a.nstrips = nstrips;
-    rd[i] = WgradReduceDesc{a.slab, wv[i].dW, a.bslab, wv[i].dbias, X, 1, 1, 64, 64, 32, NT, 0, 0, 0, 0, 9, 4, 2};
+    a.bslab = wv[i].dbias ? p.slabs.bias_part(wv[i].ws) : nullptr;
+    a.B = p.B; a.OH = w.OY; a.OW = w.OX; a.lda = w.lda; a.ldy = w.ldy; a.nxs = w.OX / 16; a.nstrips = p.units;
+    rd[i] = WgradReduceDesc{a.slab, wv[i].dW, a.bslab, wv[i].dbias, p.wgs, 1, 1, 64, 64, 32, NT, 0, 0, 0, 0, 9, 4, 2};
   }
-  hipLaunchKernelGGL(wgrad_roll_kernel, dim3(X, 1, n), dim3(512), 0, st, m);
+  hipLaunchKernelGGL(wgrad_roll_kernel, dim3(p.wgs, 1, n), dim3(512), 0, st, m);
   SV_LAUNCH_CHECK();
-  if (w.ev_mid[0]) { (void)hipEventRecord(w.ev_mid[0], st); (void)hipEventRecord(w.ev_mid[1], st); }
-  return svk_wgrad_reduce_all(rd, n, st);
+  return wgrad_finish(w, rd, n, st);
 }

@@ -19,15 +19,11 @@
 #include "common.hip.h"
 #include "kernels.h"
 #include "tile_stage.hip.h"
-#include "conv_geom.h"
+#include "wgrad_host.h"
 
 #ifndef SV_WT_PF
 #define SV_WT_PF 3      // LDS prefetch depth (fragments) of the transposed A-operand reads (re-measured round 2: 3 beats 4 by 0.5 % of the step, 1-2 and 6-8 lose)
 #endif
-
-__device__ __forceinline__ short4_t tr16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(p));
-}
 
 // TPW taps per wave (4 waves: tap group = 4*TPW taps), CIF ci-fragments (16 channels) per
 // workgroup slice, COF co-fragments (all of Cout_pad16), KC = 32-pixel K chunks per tile.
@@ -150,7 +146,7 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? OCC : 1) void wgrad_tile_kernel
       short8_t bfr[COF];
 #pragma unroll
       for (int j = 0; j < COF; ++j) {
-        const short4_t lo = tr16(sDy + dy_lane + dy_chunk(kc, 0) + j * 32), hi = tr16(sDy + dy_lane + dy_chunk(kc, 1) + j * 32);
+        const short4_t lo = lds_tr16(sDy + dy_lane + dy_chunk(kc, 0) + j * 32), hi = lds_tr16(sDy + dy_lane + dy_chunk(kc, 1) + j * 32);
         bfr[j] = (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       }
       if (BIASM && do_bias) {
@@ -166,16 +162,16 @@ __global__ __launch_bounds__(256 * NG, NG == 1 ? OCC : 1) void wgrad_tile_kernel
       const int ic0 = in_chunk(kc, 0), ic1 = in_chunk(kc, 1);
 #pragma unroll
       for (int u = 0; u < PF; ++u) {
-        alo[u] = tr16(sIn + in_lane + ic0 + tapoff[u / CIF] + (u % CIF) * 32);
-        ahi[u] = tr16(sIn + in_lane + ic1 + tapoff[u / CIF] + (u % CIF) * 32);
+        alo[u] = lds_tr16(sIn + in_lane + ic0 + tapoff[u / CIF] + (u % CIF) * 32);
+        ahi[u] = lds_tr16(sIn + in_lane + ic1 + tapoff[u / CIF] + (u % CIF) * 32);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const short4_t lo = alo[u % PF], hi = ahi[u % PF];
         const short8_t af = (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         if (u + PF < U) {
-          alo[u % PF] = tr16(sIn + in_lane + ic0 + tapoff[(u + PF) / CIF] + ((u + PF) % CIF) * 32);
-          ahi[u % PF] = tr16(sIn + in_lane + ic1 + tapoff[(u + PF) / CIF] + ((u + PF) % CIF) * 32);
+          alo[u % PF] = lds_tr16(sIn + in_lane + ic0 + tapoff[(u + PF) / CIF] + ((u + PF) % CIF) * 32);
+          ahi[u % PF] = lds_tr16(sIn + in_lane + ic1 + tapoff[(u + PF) / CIF] + ((u + PF) % CIF) * 32);
         }
         __builtin_amdgcn_sched_barrier(0);   // keep the prefetch PF fragments ahead of its MFMAs (hipcc sinks it otherwise)
 #pragma unroll
@@ -290,10 +286,6 @@ bias_part:
 //     offsets (relative to the tile's first image) are the same for every tile and computed once (<= 8 registers);
 //   * the LDS layout is the one above (pixel records of PS / YS bytes, padded for the transposed reads): a transfer writes 64 consecutive 16-B
 //     slots, lanes on padding slots or on pixels outside the image are masked off (the ring is zeroed once: those slots stay zero).
-__device__ __forceinline__ void wt_dma16(const void* base, uint32_t off, const char* lds) {    // base: wave-uniform; off: this lane's byte offset
-  const uint32_t l = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(l) : "memory", "m0");
-}
 __device__ __forceinline__ void wt_wait_vm(int n) {      // s_waitcnt vmcnt(n), n wave-uniform (the count is an immediate)
   switch (n) {
 #define SV_WT_VM(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
@@ -381,7 +373,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_tile_pipe_kernel(const WgradTile
         const bool isin = k < nin;
         const char* dst = isin ? buf + k * 1024 : buf + g.in_bytes + (k - nin) * 1024;
         const void* base = isin ? (const void*)ab : (const void*)yb;
-        if (soff[i] != 0xFFFFFFFFu) wt_dma16(base, soff[i], dst);
+        if (soff[i] != 0xFFFFFFFFu) lds_dma16(base, soff[i], dst);
       }
     }
   };
@@ -427,7 +419,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_tile_pipe_kernel(const WgradTile
       short8_t bfr[COF];
 #pragma unroll
       for (int j = 0; j < COF; ++j) {
-        const short4_t lo = tr16(sDy + dy_lane + dy_chunk(kc, 0) + j * 32), hi = tr16(sDy + dy_lane + dy_chunk(kc, 1) + j * 32);
+        const short4_t lo = lds_tr16(sDy + dy_lane + dy_chunk(kc, 0) + j * 32), hi = lds_tr16(sDy + dy_lane + dy_chunk(kc, 1) + j * 32);
         bfr[j] = (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       }
       constexpr int U = TPW * CIF, PF = U < SV_WT_PF ? U : SV_WT_PF;
@@ -435,16 +427,16 @@ __global__ __launch_bounds__(512, 1) void wgrad_tile_pipe_kernel(const WgradTile
       const int ic0 = in_chunk(kc, 0), ic1 = in_chunk(kc, 1);
 #pragma unroll
       for (int u = 0; u < PF; ++u) {
-        alo[u] = tr16(sIn + in_lane + ic0 + tapoff[u / CIF] + (u % CIF) * 32);
-        ahi[u] = tr16(sIn + in_lane + ic1 + tapoff[u / CIF] + (u % CIF) * 32);
+        alo[u] = lds_tr16(sIn + in_lane + ic0 + tapoff[u / CIF] + (u % CIF) * 32);
+        ahi[u] = lds_tr16(sIn + in_lane + ic1 + tapoff[u / CIF] + (u % CIF) * 32);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const short4_t lo = alo[u % PF], hi = ahi[u % PF];
         const short8_t af = (short8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         if (u + PF < U) {
-          alo[u % PF] = tr16(sIn + in_lane + ic0 + tapoff[(u + PF) / CIF] + ((u + PF) % CIF) * 32);
-          ahi[u % PF] = tr16(sIn + in_lane + ic1 + tapoff[(u + PF) / CIF] + ((u + PF) % CIF) * 32);
+          alo[u % PF] = lds_tr16(sIn + in_lane + ic0 + tapoff[(u + PF) / CIF] + ((u + PF) % CIF) * 32);
+          ahi[u % PF] = lds_tr16(sIn + in_lane + ic1 + tapoff[(u + PF) / CIF] + ((u + PF) % CIF) * 32);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -713,17 +705,16 @@ static int launch_wt_ng(const WgradTileArgs* a, int n, int groups, hipStream_t s
   }
   dim3 grid(msplit, groups, n), block(256 * NG);
   constexpr int PER = 4 * TPW * CIF * COF * 256;
-  const int64_t need = (int64_t)msplit * groups * PER * 4 + (int64_t)msplit * 128 * 4;      // + one (<= 128-column) bias partial per workgroup row
+  const WgradSlabs slabs{msplit, groups, PER};
   static const bool no_slab = SV_TUNE_FLAG("SV_WT_ATOMICS");
   WgradTileMulti m;
   WgradReduceMulti r;
-  bool slab = !no_slab;
-  for (int i = 0; i < n; ++i) slab = slab && a[i].ws && a[i].ws_bytes >= need;
+  const bool slab = !no_slab && slabs.fits(a, n);
   for (int i = 0; i < n; ++i) {
     m.a[i] = a[i];
     m.a[i].dbg = dbg;
     m.a[i].slab = slab ? a[i].ws : nullptr;
-    m.a[i].bslab = (slab && a[i].dbias && a[i].ldy <= 128) ? a[i].ws + (int64_t)msplit * groups * PER : nullptr;
+    m.a[i].bslab = (slab && a[i].dbias && a[i].ldy <= 128) ? slabs.bias_part(a[i].ws) : nullptr;      // (a bias partial holds <= 128 columns)
     r.slab[i] = m.a[i].slab; r.dW[i] = a[i].dW; r.bslab[i] = m.a[i].bslab; r.dbias[i] = a[i].dbias;
   }
   bool piped = false;
@@ -748,7 +739,7 @@ static int launch_wt_ng(const WgradTileArgs* a, int n, int groups, hipStream_t s
   }
   if (!piped) hipLaunchKernelGGL((wgrad_tile_kernel<TPW, CIF, COF, KC, NG, OCC>), grid, block, lds, st, m);
   SV_LAUNCH_CHECK();
-  if (ev_mid && ev_mid[0]) { (void)hipEventRecord(ev_mid[0], st); (void)hipEventRecord(ev_mid[1], st); }
+  wgrad_record_mid(ev_mid, st);
   if (slab && !(dbg & 1)) {
     hipLaunchKernelGGL((wgrad_reduce_kernel<TPW, CIF, COF>), dim3(PER / 128, groups, n), dim3(256), 0, st, r, msplit, groups,
                        a[0].ncg, a[0].CW, a[0].Cin_real, a[0].N, a[0].ntaps, a[0].fold_kw, a[0].fold_c, a[0].pairx, a[0].assign);
@@ -772,18 +763,12 @@ static int launch_wt(const WgradTileArgs* a, int n, int groups, hipStream_t st, 
   return launch_wt_ng<TPW, CIF, COF, KC, 1>(a, n, groups, st, ev_mid);
 }
 
-// Returns SV_E_UNSUPPORTED when the layer shape has no tile instantiation (caller falls back to
-// the im2col wgrad).  Shapes: the seven conv layers of the SPLIT-VAE encoder/decoder.
+// The tile kernel alone, the last form of the bf16 chain of wgrad_dispatch.hip (which has checked 1 <= n <= SV_WGRAD_MAX_MULTI, power-of-two
+// grids and stride <= 2).  Returns SV_E_UNSUPPORTED, nothing launched, when the layer shape has no tile
+// instantiation (the dispatcher falls back to the im2col wgrad).  Shapes: the seven conv layers of the SPLIT-VAE encoder/decoder.
 int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
-  if (n < 1 || n > SV_WGRAD_MAX_MULTI) return SV_E_BADARG;
   const WgradArgs& w = wv[0];                       // the n problems share one geometry, pointers differ
-  const bool force_old = sv_tune_force_im2col();
   static const char* skip = SV_TUNE_STR("SV_WGRAD_IM2COL_IDS", nullptr);    // e.g. "23": these layer ids use the im2col kernel (A/B)
-  if (force_old || w.lOY < 0 || w.lOX < 0 || w.S > 2) return SV_E_UNSUPPORTED;   // power-of-two grids, stride <= 2
-  if (svk_wgrad_roll_supported(wv, n)) { sv_trace_note("wgrad_roll"); return svk_wgrad_roll_multi(wv, n, st); }
-  if (svk_wgrad_p5_supported(wv, n)) { sv_trace_note("wgrad_p5"); return svk_wgrad_p5_multi(wv, n, st); }
-  if (svk_wgrad_e1_supported(wv, n)) { sv_trace_note("wgrad_e1"); return svk_wgrad_e1_multi(wv, n, st); }
-  if (svk_wgrad_e2_supported(wv, n)) { sv_trace_note("wgrad_e2"); return svk_wgrad_e2_multi(wv, n, st); }
   const int OY = 1 << w.lOY, OX = 1 << w.lOX;
   if (OY * OX < 16 || w.ycols != w.ldy || (w.ups && w.S != 1)) return SV_E_UNSUPPORTED;
   const int cin = w.Cin_pad, cout = w.ldy, nt = w.ntaps;
@@ -812,20 +797,11 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
   // two-group form it is: 0.097 -> 0.064 ms incl. the reduce, B = 512.  SV_WGRAD_IM2COL_IDS=4 restores the GEMM.)
   // every layer takes the two-stage flush when a workspace is given: even d5 (6 of 16 slab columns
   // real) and e1 (3 of 16 rows real) beat the fp32 atomics (d5: 183 -> 133 us) since the reduce runs at HBM speed
-  const bool allow_slab = true;
   while (OY * OX < BM && (BM % (OY * OX))) BM >>= 1;
   if (BM < 64) return SV_E_UNSUPPORTED;
-  int y_lo = 127, y_hi = -127, x_lo = 127, x_hi = -127;
-  for (int i = 0; i < nt; ++i) {
-    y_lo = w.dy[i] < y_lo ? w.dy[i] : y_lo; y_hi = w.dy[i] > y_hi ? w.dy[i] : y_hi;
-    x_lo = w.dx[i] < x_lo ? w.dx[i] : x_lo; x_hi = w.dx[i] > x_hi ? w.dx[i] : x_hi;
-  }
-  const int lTW = OX >= 16 ? 4 : w.lOX;
-  int lTH = 0;
-  while ((1 << (lTW + lTH)) < BM && (1 << lTH) < OY) ++lTH;
-  int lNB = 0;
-  while ((1 << (lTW + lTH + lNB)) < BM) ++lNB;
-  const int TW = 1 << lTW, TH = 1 << lTH, NB = 1 << lNB;
+  const WgradTapBox box = wgrad_tap_box(w);
+  const WgradTileShape ts = wgrad_tile_shape(w, BM);
+  const int TW = 1 << ts.lTW, TH = 1 << ts.lTH, NB = 1 << ts.lNB;
   const int B = w.M >> (w.lOY + w.lOX);
   WgradTileArgs av[SV_WGRAD_MAX_MULTI];
   WgradTileArgs& a = av[0];
@@ -840,11 +816,11 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
   a.contig = (all_strided || strchr(strided_ids, '0' + id)) ? 0 : 1;
   a.CW = CW; a.ncg = cin / CW;
   a.cl2 = ilog2_exact(CW / 8);
-  a.lTW = lTW; a.lTH = lTH; a.lNB = lNB; a.OY = OY; a.OX = OX;
+  a.lTW = ts.lTW; a.lTH = ts.lTH; a.lNB = ts.lNB; a.OY = OY; a.OX = OX;
   a.tilesX = OX / TW; a.tilesY = OY / TH;
   a.ntiles = a.tilesX * a.tilesY * ((B + NB - 1) / NB);
-  a.TIW = (TW - 1) * w.SX + (x_hi - x_lo) + 1; a.TIH = (TH - 1) * w.S + (y_hi - y_lo) + 1;
-  a.y_lo = y_lo; a.x_lo = x_lo;
+  a.TIW = box.in_w(TW, w.SX); a.TIH = box.in_h(TH, w.S);
+  a.y_lo = box.y_lo; a.x_lo = box.x_lo;
   // 16 / 32 / 96 B: PS/32 odd (or a single 16-B chunk); at x stride 2 the K pixels are 2*PS apart: 80 B
   // SV_WT_PAD16: 16-channel slices at x stride 2 (packed d5) on a 96-B K-pixel pitch.  Measured: LDS bank conflicts
   // 46 % -> 1.3 %, LDS-active cycles -45 %, kernel time unchanged (110 us): the loop is not LDS-throughput-bound.
@@ -874,9 +850,8 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
   for (int i = n - 1; i >= 0; --i) {
     av[i] = a;
     av[i].A = wv[i].A; av[i].dY = wv[i].dY; av[i].dW = wv[i].dW; av[i].dbias = wv[i].dbias;
-    av[i].ws = allow_slab ? wv[i].ws : nullptr; av[i].ws_bytes = allow_slab ? wv[i].ws_bytes : 0;
+    av[i].ws = wv[i].ws; av[i].ws_bytes = wv[i].ws_bytes;
   }
-  sv_trace_note("wgrad_tile");
   // <TPW, CIF, COF, KC>
   switch (id) {
     case 0: if (KC == 8) return launch_wt<9, 2, 1, 8>(av, n, groups, st, wv[0].ev_mid); break;
@@ -899,58 +874,4 @@ int svk_wgrad_tile_multi(const WgradArgs* wv, int n, hipStream_t st) {
             if (KC == 8) return launch_wt<11, 2, 1, 8>(av, n, groups, st, wv[0].ev_mid); break;
   }
   return SV_E_UNSUPPORTED;
-}
-
-int svk_wgrad_tile(const WgradArgs& w, hipStream_t st) { return svk_wgrad_tile_multi(&w, 1, st); }
-
-int svk_wgrad_dispatch_multi(const WgradArgs* w, int n, int dtype, int cfg, hipStream_t st) {
-  const bool no_multi = sv_tune_no_multi();
-  if (dtype == SV_BF16 && !no_multi && n <= SV_WGRAD_MAX_MULTI) {
-    const int rc = svk_wgrad_tile_multi(w, n, st);
-    if (rc != SV_E_UNSUPPORTED) return rc;
-  }
-  if (dtype == SV_F32 && !no_multi && n <= SV_WGRAD_MAX_MULTI) {
-    const int rc = svk_wgrad_tile_f32_multi(w, n, st);
-    if (rc != SV_E_UNSUPPORTED) return rc;
-  }
-  // im2col kernel (no tile instantiation for this shape, or fp32): all of them in one launch
-  for (int i = 0; i < n; ++i)
-    if (w[i].s2d3 || w[i].clampin || w[i].dy_os || w[i].dy_s2d) return SV_E_UNSUPPORTED;      // views only the tile kernels form
-  const bool any_tile = no_multi || n > SV_WGRAD_IM2COL_MAX_MULTI;
-  int rc = SV_OK;
-  if (!any_tile) {
-    WgradArgs wi[SV_WGRAD_IM2COL_MAX_MULTI];
-    for (int i = 0; i < n; ++i) {
-      wi[i] = w[i];
-      wi[i].ev_mid[0] = wi[i].ev_mid[1] = nullptr;
-      if (n > 1) svg_wgrad_set_msplit(&wi[i], cfg, dtype, 512 / n);   // the problems share the chip
-    }
-    rc = svk_wgrad_multi(wi, n, dtype, cfg, st);
-  } else {
-    for (int i = 0; i < n && !rc; ++i) {
-      WgradArgs wi = w[i];
-      wi.ev_mid[0] = wi.ev_mid[1] = nullptr;
-      rc = svk_wgrad_dispatch(wi, dtype, cfg, st);
-    }
-  }
-  if (rc) return rc;
-  if (w[0].ev_mid[0]) { (void)hipEventRecord(w[0].ev_mid[0], st); (void)hipEventRecord(w[0].ev_mid[1], st); }   // no second stage on this path
-  return SV_OK;
-}
-
-int svk_wgrad_dispatch(const WgradArgs& w, int dtype, int cfg, hipStream_t st) {
-  if (dtype == SV_BF16) {
-    const int rc = svk_wgrad_tile(w, st);
-    if (rc != SV_E_UNSUPPORTED) return rc;
-  }
-  if (dtype == SV_F32) {
-    const int rc = svk_wgrad_tile_f32_multi(&w, 1, st);
-    if (rc != SV_E_UNSUPPORTED) {
-      sv_trace_note("wgrad_tile_f32");
-      return rc;
-    }
-  }
-  if (w.ups || w.fold_kw || w.s2d3 || w.clampin || w.dy_os || w.dy_s2d) return SV_E_UNSUPPORTED;    // the im2col kernel needs the materialised hi-res tensor / cannot fold / reads no views
-  sv_trace_note("wgrad_im2col");
-  return svk_wgrad(w, dtype, cfg, st);
 }

@@ -17,15 +17,9 @@
 #include "kernels.h"
 #include "tile_stage.hip.h"
 #include "conv_geom.h"
+#include "wgrad_host.h"
 
 namespace {
-
-// one LDS-DMA wave-instruction as inline assembly (base: wave-uniform tensor pointer, off: this lane's byte offset): the compiler orders every LDS access behind
-// the builtin's vmcnt(0); with the assembly form the double-buffered loop waits where IT wants to (latent_gemm.hip: nt_dma16)
-__device__ __forceinline__ void dma16_asm(const void* base, uint32_t off, const char* lds) {
-  const uint32_t l = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(l) : "memory", "m0");
-}
 
 // TPW taps per wave (4 waves: 4 * TPW taps per workgroup = all of them), COF 16-column fragments of dY.  A workgroup owns a 16-channel (8 for
 // an 8-channel input) slice of the input, blockIdx.y, and walks a contiguous run of tiles, blockIdx.x.
@@ -135,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tile_f32_kernel(const WgradTileM
         bool ok = b < g.B;
         if (g.clampin) { iy = min(max(iy, 0), g.IH - 1); ix = min(max(ix, 0), g.IW - 1); }
         else ok = ok && (unsigned)iy < (unsigned)g.IH && (unsigned)ix < (unsigned)g.IW;
-        if (ok) dma16_asm(Ab, (uint32_t)((((b * g.IH + iy) * g.IW + ix) * g.lda + c * 4) * 4), sI + base * 16);
+        if (ok) lds_dma16(Ab, (uint32_t)((((b * g.IH + iy) * g.IW + ix) * g.lda + c * 4) * 4), sI + base * 16);
         else *(uint4*)(sI + L * 16) = make_uint4(0, 0, 0, 0);
       }
       char* sY = sI + g.in_bytes;
@@ -149,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tile_f32_kernel(const WgradTileM
         if (g.dy_s2d) off = (uint32_t)((((b * 2 * g.OY + 2 * (ty0 + ty) + (c >> 2)) * (2 * g.OX) + 2 * (tx0 + tx) + ((c >> 1) & 1)) * 8 + (c & 1) * 4) * 4);
         else if (g.dy_os) off = (uint32_t)((((b * 2 * g.OY + 2 * (ty0 + ty) + g.dy_oy) * (2 * g.OX) + 2 * (tx0 + tx) + g.dy_ox) * g.ldy + c * 4) * 4);
         else off = (uint32_t)((((b * g.OY + ty0 + ty) * g.OX + tx0 + tx) * g.ldy + c * 4) * 4);
-        if (b < g.B) dma16_asm(Yb, off, sY + base * 16);
+        if (b < g.B) lds_dma16(Yb, off, sY + base * 16);
         else *(uint4*)(sY + q * 16) = make_uint4(0, 0, 0, 0);
       }
     };
@@ -430,11 +424,7 @@ int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
   // (an 8-channel input with an odd kernel width -- the first 3 x 3 layer of LG-SPAIR's object encoder -- runs without pairs: fragment rows 8..15
   //  hold the next pixel's channels and are dropped by the flush / the reduce)
   if (CW == 8 && !pairx && nt != 9) F32_REJ("8-channel input without tap pairs");
-  int y_lo = 127, y_hi = -127, x_lo = 127, x_hi = -127;
-  for (int i = 0; i < nt; ++i) {
-    y_lo = w.dy[i] < y_lo ? w.dy[i] : y_lo; y_hi = w.dy[i] > y_hi ? w.dy[i] : y_hi;
-    x_lo = w.dx[i] < x_lo ? w.dx[i] : x_lo; x_hi = w.dx[i] > x_hi ? w.dx[i] : x_hi;
-  }
+  const WgradTapBox box = wgrad_tap_box(w);
   // pixels per tile: the largest of 256 .. 32 whose input patch + dY tile leave two workgroups per CU their LDS
   WgradTileArgs a;
   const int bm_max = wtf32_bm_max(), wgs = wtf32_wgs();
@@ -452,15 +442,11 @@ int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
   for (;; BM >>= 1) {
     if (BM < 32) F32_REJ("tile");
     if (OY * OX < BM && (BM % (OY * OX))) continue;
-    const int lTW = OX >= 16 ? 4 : w.lOX;
-    int lTH = 0;
-    while ((1 << (lTW + lTH)) < BM && (1 << lTH) < OY) ++lTH;
-    int lNB = 0;
-    while ((1 << (lTW + lTH + lNB)) < BM) ++lNB;
-    const int TW = 1 << lTW, TH = 1 << lTH, NB = 1 << lNB;
+    const WgradTileShape ts = wgrad_tile_shape(w, BM);
+    const int NB = 1 << ts.lNB;
     memset(&a, 0, sizeof(a));
-    a.lTW = lTW; a.lTH = lTH; a.lNB = lNB;
-    a.TIW = (TW - 1) * w.SX + (x_hi - x_lo) + 1; a.TIH = (TH - 1) * w.S + (y_hi - y_lo) + 1;
+    a.lTW = ts.lTW; a.lTH = ts.lTH; a.lNB = ts.lNB;
+    a.TIW = box.in_w(1 << ts.lTW, w.SX); a.TIH = box.in_h(1 << ts.lTH, w.S);
     a.PS = CW * 4; a.YS = ldy * 4;
     a.in_bytes = (NB * a.TIH * a.TIW * a.PS + 64 + 15) / 16 * 16;      // slack: the masked lanes of a half-filled fragment read past the last pixel
     a.dy_bytes = BM * a.YS + 64;
@@ -478,7 +464,7 @@ int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
   a.dbg = dbg;
   a.OY = OY; a.OX = OX; a.tilesX = OX / TW; a.tilesY = OY / TH;
   a.ntiles = a.tilesX * a.tilesY * ((B + NB - 1) / NB);
-  a.y_lo = y_lo; a.x_lo = x_lo;
+  a.y_lo = box.y_lo; a.x_lo = box.x_lo;
   a.ldy = ldy; a.lycp = ilog2_exact(ldy / 4);
   if (a.lycp < 0) F32_REJ("dY pitch");
   a.Cin_real = w.Cin_real; a.N = w.N; a.ntaps = ntk; a.pairx = pairx ? 1 : 0;
@@ -488,10 +474,10 @@ int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
   int msplit = (wgs + groups * n - 1) / (groups * n);
   if (msplit > a.ntiles) msplit = a.ntiles;
   if (msplit < 1) msplit = 1;
-  const int64_t PER = 4LL * TPW * COF * 256;
-  const int64_t need = (int64_t)msplit * groups * PER * 4 + (int64_t)msplit * 128 * 4;
-  bool slab = true;                      // no (or a small) workspace: fp32 atomics straight into dW -- kept for the x-packed head and the layers behind
-  for (int i = 0; i < n; ++i) slab = slab && wv[i].ws && wv[i].ws_bytes >= need;          // a fused resize, which the im2col kernel cannot do; every other shape falls back to it
+  const WgradSlabs slabs{msplit, groups, 4LL * TPW * COF * 256};
+  // no (or a small) workspace: fp32 atomics straight into dW -- kept for the x-packed head and the layers behind a fused resize, which the im2col kernel
+  // cannot do; every other shape falls back to it
+  const bool slab = slabs.fits(wv, n);
   if (!slab && !w.fold_kw && !w.ups && !w.s2d3) F32_REJ("workspace");        // (s2d3: the im2col kernel cannot form the space-to-depth view: fp32 atomics flush)
   WgradTileArgs av[SV_WGRAD_MAX_MULTI];
   WgradReduceDesc rd[SV_WGRAD_MAX_MULTI];
@@ -499,7 +485,7 @@ int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
     av[i] = a;
     av[i].A = wv[i].A; av[i].dY = wv[i].dY; av[i].dW = wv[i].dW; av[i].dbias = wv[i].dbias;
     av[i].slab = slab ? wv[i].ws : nullptr;
-    av[i].bslab = slab && wv[i].dbias ? wv[i].ws + (int64_t)msplit * groups * PER : nullptr;
+    av[i].bslab = slab && wv[i].dbias ? slabs.bias_part(wv[i].ws) : nullptr;
     rd[i] = WgradReduceDesc{av[i].slab, wv[i].dW, av[i].bslab, wv[i].dbias, msplit, groups, a.ncg, CW, a.Cin_real, a.N, ntk, w.fold_kw, w.fold_c, a.pairx, a.assign, TPW, 1, COF, w.s2d3};
   }
   const size_t lds = ((size_t)a.in_bytes + a.dy_bytes) * (a.db ? 2 : 1);
@@ -531,13 +517,7 @@ int svk_wgrad_tile_f32_multi(const WgradArgs* wv, int n, hipStream_t st) {
 #undef F32_CASE
   else F32_REJ("no instantiation");
   if (rc != SV_OK) return rc;
-  if (w.ev_mid[0]) { (void)hipEventRecord(w.ev_mid[0], st); (void)hipEventRecord(w.ev_mid[1], st); }
-  if (!slab) return SV_OK;
-  if (w.defer && w.n_defer && *w.n_defer + n <= 64) {
-    for (int i = 0; i < n; ++i) w.defer[(*w.n_defer)++] = rd[i];
-    return SV_OK;
-  }
-  return svk_wgrad_reduce_all(rd, n, st);
+  return wgrad_finish(w, rd, slab ? n : 0, st);        // (the atomics flush leaves nothing to reduce)
 }
 
 
@@ -559,20 +539,17 @@ int svk_wgrad_polyc_f32_multi(const WgradArgs* cls, int n, int mask, WgradReduce
   const int OY = 1 << w.lOY, OX = 1 << w.lOX, cin = w.Cin_pad, CW = 16;
   if (OX < 4 || OY * OX < 16 || cin % CW) F32_REJ("grid / channels");
   const int bm_max = wtf32_bm_max(), wgs = wtf32_wgs(), lds_max = wtf32_lds_max();
+  const WgradTapBox cbox = {-2, 2, -2, 2};                  // the union of the classes' windows: offsets -2 .. 2
   WgradTileArgs a;
   int BM = bm_max;
   for (;; BM >>= 1) {
     if (BM < 32) F32_REJ("tile");
     if (OY * OX < BM && (BM % (OY * OX))) continue;
-    const int lTW = OX >= 16 ? 4 : w.lOX;
-    int lTH = 0;
-    while ((1 << (lTW + lTH)) < BM && (1 << lTH) < OY) ++lTH;
-    int lNB = 0;
-    while ((1 << (lTW + lTH + lNB)) < BM) ++lNB;
-    const int TW = 1 << lTW, TH = 1 << lTH, NB = 1 << lNB;
+    const WgradTileShape ts = wgrad_tile_shape(w, BM);
+    const int NB = 1 << ts.lNB;
     memset(&a, 0, sizeof(a));
-    a.lTW = lTW; a.lTH = lTH; a.lNB = lNB;
-    a.TIW = TW + 4; a.TIH = TH + 4;                          // the union of the classes' windows: offsets -2 .. 2
+    a.lTW = ts.lTW; a.lTH = ts.lTH; a.lNB = ts.lNB;
+    a.TIW = cbox.in_w(1 << ts.lTW, 1); a.TIH = cbox.in_h(1 << ts.lTH, 1);
     a.PS = CW * 4; a.YS = 32 * 4;
     a.in_bytes = (NB * a.TIH * a.TIW * a.PS + 64 + 15) / 16 * 16;
     a.dy_bytes = BM * a.YS + 64;
@@ -584,7 +561,7 @@ int svk_wgrad_polyc_f32_multi(const WgradArgs* cls, int n, int mask, WgradReduce
   a.contig = 1; a.CW = CW; a.ncg = cin / CW; a.cl2 = 2;
   a.OY = OY; a.OX = OX; a.tilesX = OX / TW; a.tilesY = OY / TH;
   a.ntiles = a.tilesX * a.tilesY * ((B + NB - 1) / NB);
-  a.y_lo = -2; a.x_lo = -2; a.ldy = 32; a.lycp = 3; a.Cin_real = w.Cin_real; a.N = 32;
+  a.y_lo = cbox.y_lo; a.x_lo = cbox.x_lo; a.ldy = 32; a.lycp = 3; a.Cin_real = w.Cin_real; a.N = 32;
   const int groups = a.ncg;
   int msplit = (wgs + groups * n - 1) / (groups * n);
   if (msplit > a.ntiles) msplit = a.ntiles;
@@ -601,13 +578,12 @@ int svk_wgrad_polyc_f32_multi(const WgradArgs* cls, int n, int mask, WgradReduce
       if (!(mask >> c & 1)) continue;
       const WgradArgs& wc = cls[c * n + i];
       const bool lead = c == c_lead;
-      const int64_t PER = 4LL * tpw[c] * 2 * 256;
-      const int64_t need = (int64_t)msplit * groups * PER * 4 + (lead ? (int64_t)msplit * 128 * 4 : 0);
-      if (!wc.ws || wc.ws_bytes < need) { *nrd = nrd0; F32_REJ("workspace"); }
+      const WgradSlabs slabs{msplit, groups, 4LL * tpw[c] * 2 * 256, lead};      // the bias partial rides with the lead class only
+      if (!slabs.fits(&wc, 1)) { *nrd = nrd0; F32_REJ("workspace"); }
       p.slab[c] = wc.ws;
       p.ntaps[c] = wc.ntaps;
       for (int t = 0; t < wc.ntaps; ++t) { p.cdy[c][t] = wc.dy[t]; p.cdx[c][t] = wc.dx[t]; }
-      if (lead) { p.g.dbias = wc.dbias; p.g.bslab = wc.dbias ? wc.ws + (int64_t)msplit * groups * PER : nullptr; }
+      if (lead) { p.g.dbias = wc.dbias; p.g.bslab = wc.dbias ? slabs.bias_part(wc.ws) : nullptr; }
       rd[(*nrd)++] = WgradReduceDesc{p.slab[c], wc.dW, lead ? p.g.bslab : nullptr, lead ? wc.dbias : nullptr, msplit, groups, a.ncg, CW, a.Cin_real, 32,
                                      wc.ntaps, 0, 0, 0, 1, tpw[c], 1, 2, 0};
     }
