@@ -308,6 +308,58 @@ int sv_draw_bounding_boxes(const float* images, const float* boxes, const float*
 int sv_spair_count_metrics(const float* z_pres_logits, int32_t ld, const float* labels, float* pred, float* metrics, int32_t* acc,
                            int32_t B, int32_t ncell, void* stream);
 
+/* Detection average precision on Multi-Bird canvases (detect_ap.hip; DESIGN.md 4.20 pins the definitions; no reference
+ * counterpart: spair/data.py drops the positions).  Plain loads and stores, no atomics, one fixed order for every sum: the same
+ * inputs give the same bits.  Every argument is checked before anything is enqueued.  Boxes are (ymin, xmin, ymax, xmax),
+ * normalised to the canvas (obj_bbox_mask's convention).
+ *
+ * Sprite extents: out[s] = (r0, c0, r1, c1), the inclusive tight bounds of the pixels of sprite s of bank [n,14,14,3] uint8 with
+ * max(r,g,b) > 0 (the renderer's mask rule); four -1 for an all-zero sprite.  SV_E_BADARG: a null pointer, n <= 0;
+ * SV_E_UNSUPPORTED: n > 2^20.  The _host entry is the same arithmetic in a plain loop; it needs no device. */
+int sv_sprite_extents_host(const uint8_t* bank, int32_t n, int32_t* out /* [n][4] */);
+int sv_sprite_extents(const uint8_t* bank, int32_t n, int32_t* out /* [n][4] */, void* stream);
+/* Ground truth of B canvases: for each k < count (clamped to 0..5) whose sprite[k] is inside the bank and has extents, the box
+ * ((row + r0) / 48, (col + c0) / 48, (row + r1 + 1) / 48, (col + c1 + 1) / 48) in correctly rounded fp32 -- the sprite's full
+ * extent, occluded or not -- packed in object order into boxes[b][0 .. n_gt[b] - 1]; the remaining slots are zero.
+ * SV_E_BADARG: a null or misaligned pointer, n_sprites or B <= 0; SV_E_UNSUPPORTED: n_sprites > 2^20. */
+int sv_multibird_gt_boxes_host(const sv_multibird_layout* layouts, const int32_t* extents, int32_t n_sprites, float* boxes /* [B][5][4] */,
+                               int32_t* n_gt /* [B] */, int32_t B);
+int sv_multibird_gt_boxes(const sv_multibird_layout* layouts, const int32_t* extents, int32_t n_sprites, float* boxes /* [B][5][4] */,
+                          int32_t* n_gt /* [B] */, int32_t B, void* stream);
+/* Matching of B images of `cells` cells (1..64) against their ground truth.  bbox: image b's cells at bbox + b * ld_bbox, four
+ * floats a cell (ld_bbox >= 4 * cells, in floats); logits: image b's at logits + b * ld_logits (ld_logits >= cells); gt_boxes
+ * [B][5][4], n_gt [B] (clamped to 0..5).  Cell j of image b is record id = (image_offset + b) * cells + j.
+ *   A detection is a cell with logit > 0 (NaN, +-0 and negatives are none).  rec_key[id] = (K << 32) | id with, for a detection,
+ *   K = ~(u ^ (u >> 31 ? 0xFFFFFFFF : 0x80000000)), u the logit's bits -- ascending keys are descending logits, ties to the lower
+ *   id -- and K = 0xFFFFFFFF for a non-detection, which sorts behind every detection.
+ *   A box is an area iff its coordinates are finite and ymax > ymin, xmax > xmin.  For two areas, in fp32 with every operation
+ *   rounded on its own: ih = min(ymax) - max(ymin), iw likewise; if both > 0, inter = ih * iw, a and b the two areas,
+ *   union = (a + b) - inter, iou = inter / union, and threshold t = 1..9 passes iff inter > 0 and 10 * inter >= t * union.
+ *   Anything else: iou 0, no threshold passes.
+ *   Per threshold the image's detections are walked in key order; each takes the unmatched box of highest iou among those that
+ *   pass (ties to the lower box index) and is a true positive, or takes none and is a false positive.
+ *   rec_tp[id]: bit t - 1 set iff the record is a true positive at threshold t / 10; 0 for a non-detection.
+ * Exactly the B * cells record slots from image_offset * cells are written.  SV_E_BADARG: a null or misaligned pointer (4 bytes;
+ * rec_key 8; rec_tp 2), B or cells <= 0, image_offset < 0, a pitch below its row; SV_E_UNSUPPORTED: cells > 64 or
+ * image_offset + B > (2^31 - 1) / 64. */
+int sv_detect_match_host(const float* bbox, int64_t ld_bbox, const float* logits, int64_t ld_logits, int32_t cells, const float* gt_boxes,
+                         const int32_t* n_gt, int32_t B, int64_t image_offset, uint64_t* rec_key, uint16_t* rec_tp);
+int sv_detect_match(const float* bbox, int64_t ld_bbox, const float* logits, int64_t ld_logits, int32_t cells, const float* gt_boxes,
+                    const int32_t* n_gt, int32_t B, int64_t image_offset, uint64_t* rec_key, uint16_t* rec_tp, void* stream);
+/* The curve over n_records records (1 .. 2^20) in any order.  M = the detections, G = sum of n_gt[0 .. n_images - 1] (each clamped
+ * to 0..5).  In ascending key order, TP_t(i) = the true positives among the first i detections and p_i = TP_t(i) / i in fp64:
+ *   out[0..8]   AP_t  = (1/G) sum_i [tp_i] max_{j >= i} p_j     (all-point interpolation)
+ *   out[9..17]  AP'_t = (1/G) sum_i [tp_i] p_i
+ *   out[18..26] TP_t(M), out[27] M, out[28] G                    (int64 in the same 8-byte slots)
+ * AP_t and AP'_t are 0 when G == 0 or M == 0.  rec_key / rec_tp are not modified; the workspace (16-byte aligned, at least
+ * sv_detect_ap_workspace_bytes, any contents) holds the sorted copy and the block partials.  sv_detect_ap_chunk_records: the
+ * records of one LDS sort chunk and scan block.  SV_E_BADARG: a null or misaligned pointer, n_images < 1; SV_E_UNSUPPORTED:
+ * n_records outside 1 .. 2^20, n_images > 2^20; SV_E_WORKSPACE: workspace_bytes too small. */
+int sv_detect_ap_chunk_records(void);
+int sv_detect_ap_workspace_bytes(int64_t n_records, int64_t* bytes);
+int sv_detect_ap_finish(const uint64_t* rec_key, const uint16_t* rec_tp, int64_t n_records, const int32_t* n_gt, int64_t n_images,
+                        void* workspace, int64_t workspace_bytes, double* out /* [29] */, void* stream);
+
 /* ---------------------------------------------------------------- K3-K10: NHWC conv (implicit GEMM on MFMA)
  * Replaces tf.keras.layers.Conv2D(padding='same') forward (vae/model.py:36-38,:153-156) and the
  * Conv2DBackpropInput / Conv2DBackpropFilter / BiasAddGrad / ReluGrad nodes of tape.gradient

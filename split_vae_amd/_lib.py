@@ -180,6 +180,15 @@ SYMBOLS = {
     "sv_spair_loss_dyn": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp, C.c_float, _vp]),
     "sv_draw_bounding_boxes": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "sv_spair_count_metrics": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "sv_sprite_extents_host": (C.c_int, [_vp, _i32, _vp]),
+    "sv_sprite_extents": (C.c_int, [_vp, _i32, _vp, _vp]),
+    "sv_multibird_gt_boxes_host": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32]),
+    "sv_multibird_gt_boxes": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "sv_detect_match_host": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _vp, _vp]),
+    "sv_detect_match": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _i64, _vp, _vp, _vp]),
+    "sv_detect_ap_chunk_records": (C.c_int, []),
+    "sv_detect_ap_workspace_bytes": (C.c_int, [_i64, C.POINTER(_i64)]),
+    "sv_detect_ap_finish": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sv_spair_zpres_kl_dyn": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp, C.c_float, C.c_float, _vp]),
     "sv_adam_step_clipnorm_dyn": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                             _i64, _vp, C.c_float, _vp]),

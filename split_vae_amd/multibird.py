@@ -168,6 +168,7 @@ def get_cub_dataset(name, size=48, channel=3, batch_size=32, data_dir="data", se
             x, y = read_labelled_tfrec(p, size, channel)
             tests.append(LabelledBatches(torch.from_numpy(x).to(device), torch.from_numpy(y).to(device), batch_size))
         return train, tests, shape, shape
+    from . import detection
     bg = name[4:]
     train_bank, test_bank, _ = load_banks(data_dir, seed)
     train_bank, test_bank = torch.from_numpy(train_bank).to(device), torch.from_numpy(test_bank).to(device)
@@ -176,6 +177,8 @@ def get_cub_dataset(name, size=48, channel=3, batch_size=32, data_dir="data", se
     for split, b in ((SPLIT_TEST, bg), (SPLIT_TEST_UNSEEN, "unseen_" + bg)):              # :239,247: the test sprite bank for both
         x, y = render(test_bank, BACKGROUNDS[b], n_test, seed, split)
         tests.append(LabelledBatches(x, y, batch_size))
+        # the canvases' ground-truth boxes (detection.py): attributes only, iteration yields what it always did
+        tests[-1].boxes, tests[-1].n_boxes = detection.ground_truth(test_bank, BACKGROUNDS[b], test_bank.shape[0], n_test, seed, split)
     return train, tests, shape, shape
 
 

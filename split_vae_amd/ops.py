@@ -450,6 +450,127 @@ def spair_count_metrics(z_pres_logits, labels, acc=None, want_pred=False):
     return metrics, pred
 
 
+# ------------------------------------------------------------------ detection average precision (csrc/detect_ap.hip)
+DETECT_AP_THRESHOLDS = 9           # IoU 0.1 .. 0.9
+DETECT_AP_MAX_CELLS, DETECT_AP_MAX_RECORDS, DETECT_AP_OUT = 64, 1 << 20, 29
+DETECT_NONDET = 0xFFFFFFFF         # high word of a non-detection's key
+
+
+def _np_ptr(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def sprite_extents_host(bank):
+    """uint8 [n,14,14,3] NumPy bank -> int32 [n,4] (r0, c0, r1, c1), -1 for an empty sprite (sv_sprite_extents_host; no device)."""
+    import numpy as np
+    bank = np.ascontiguousarray(bank, np.uint8)
+    assert bank.ndim == 4 and bank.shape[1:] == (14, 14, 3)
+    out = np.empty((bank.shape[0], 4), np.int32)
+    check(_lib.load().sv_sprite_extents_host(_np_ptr(bank), bank.shape[0], _np_ptr(out)), "sv_sprite_extents_host")
+    return out
+
+
+def sprite_extents(bank):
+    """uint8 [n,14,14,3] device bank -> int32 [n,4] on its device (sv_sprite_extents)."""
+    assert bank.dtype == torch.uint8 and bank.dim() == 4 and tuple(bank.shape[1:]) == (14, 14, 3)
+    out = torch.empty((bank.shape[0], 4), dtype=torch.int32, device=bank.device)
+    check(_lib.load().sv_sprite_extents(_p(bank), bank.shape[0], _p(out), _stream()), "sv_sprite_extents")
+    return out
+
+
+def multibird_gt_boxes_host(layouts, extents):
+    """layouts: structured array / int32 [B,20] NumPy, extents int32 [n,4] -> (boxes [B,5,4] fp32, n_gt [B] int32); no device."""
+    import numpy as np
+    lay = np.ascontiguousarray(layouts).view("<i4").reshape(-1, MULTIBIRD_LAYOUT_WORDS)
+    ext = np.ascontiguousarray(extents, np.int32)
+    B = lay.shape[0]
+    boxes, n_gt = np.empty((B, 5, 4), np.float32), np.empty((B,), np.int32)
+    check(_lib.load().sv_multibird_gt_boxes_host(_np_ptr(lay), _np_ptr(ext), ext.shape[0], _np_ptr(boxes), _np_ptr(n_gt), B),
+          "sv_multibird_gt_boxes_host")
+    return boxes, n_gt
+
+
+def multibird_gt_boxes(layouts, extents):
+    """layouts int32 [B,20] (ops.multibird_layouts), extents int32 [n,4] (ops.sprite_extents) -> (boxes [B,5,4] fp32, n_gt [B] int32)."""
+    assert layouts.dtype == torch.int32 and layouts.dim() == 2 and layouts.shape[1] == MULTIBIRD_LAYOUT_WORDS
+    assert extents.dtype == torch.int32 and extents.dim() == 2 and extents.shape[1] == 4
+    B = layouts.shape[0]
+    boxes = torch.empty((B, 5, 4), dtype=torch.float32, device=layouts.device)
+    n_gt = torch.empty((B,), dtype=torch.int32, device=layouts.device)
+    check(_lib.load().sv_multibird_gt_boxes(_p(layouts), _p(extents), extents.shape[0], _p(boxes), _p(n_gt), B, _stream()),
+          "sv_multibird_gt_boxes")
+    return boxes, n_gt
+
+
+def detect_match_host(bbox, logits, gt_boxes, n_gt, image_offset=0, rec_key=None, rec_tp=None):
+    """sv_detect_match_host over NumPy arrays: bbox [B,cells,4] fp32, logits [B,cells] fp32, gt_boxes [B,5,4] fp32, n_gt [B] int32 ->
+    (rec_key uint64, rec_tp uint16); given arrays are written at the records of image_offset .. image_offset + B - 1.  No device."""
+    import numpy as np
+    bbox, logits = np.ascontiguousarray(bbox, np.float32), np.ascontiguousarray(logits, np.float32)
+    gt_boxes, n_gt = np.ascontiguousarray(gt_boxes, np.float32), np.ascontiguousarray(n_gt, np.int32)
+    B, cells = logits.shape
+    assert bbox.shape == (B, cells, 4) and gt_boxes.shape == (B, 5, 4) and n_gt.shape == (B,)
+    n = (image_offset + B) * cells
+    if rec_key is None:
+        rec_key, rec_tp = np.zeros((n,), np.uint64), np.zeros((n,), np.uint16)
+    assert rec_key.dtype == np.uint64 and rec_tp.dtype == np.uint16 and rec_key.size >= n and rec_tp.size >= n
+    assert rec_key.flags.c_contiguous and rec_tp.flags.c_contiguous
+    check(_lib.load().sv_detect_match_host(_np_ptr(bbox), cells * 4, _np_ptr(logits), cells, cells, _np_ptr(gt_boxes), _np_ptr(n_gt), B,
+                                           image_offset, _np_ptr(rec_key), _np_ptr(rec_tp)), "sv_detect_match_host")
+    return rec_key, rec_tp
+
+
+def detect_match(bbox, logits, gt_boxes, n_gt, rec_key, rec_tp, image_offset=0):
+    """sv_detect_match: bbox [B,cells,4] and logits [B,cells(,...)] fp32 (an image's cells contiguous, images at any row pitch: the
+    tape's outputs are read in place), gt_boxes [B,5,4] fp32, n_gt [B] int32 -> the records of images image_offset .. + B - 1 of
+    rec_key (int64: the key's bits) and rec_tp (int16)."""
+    B = bbox.shape[0]
+    lg = logits.reshape(B, -1)
+    cells = lg.shape[1]
+    if lg.stride(1) != 1 or lg.data_ptr() % 4:
+        lg = lg.contiguous()
+    bb = bbox.reshape(B, cells, 4)
+    if bb.stride(2) != 1 or bb.stride(1) != 4 or bb.data_ptr() % 4:
+        bb = bb.contiguous()
+    assert bb.dtype == torch.float32 and lg.dtype == torch.float32 and bb.is_cuda and lg.is_cuda
+    assert gt_boxes.dtype == torch.float32 and tuple(gt_boxes.shape) == (B, 5, 4) and n_gt.dtype == torch.int32 and n_gt.numel() == B
+    assert rec_key.dtype == torch.int64 and rec_tp.dtype == torch.int16 and rec_key.dim() == 1 and rec_tp.dim() == 1
+    assert image_offset >= 0 and (image_offset + B) * cells <= min(rec_key.numel(), rec_tp.numel()), "record arrays too small"
+    ldb = bb.stride(0) if B > 1 else cells * 4
+    ldl = lg.stride(0) if B > 1 else cells
+    check(_lib.load().sv_detect_match(C.c_void_p(bb.data_ptr()), ldb, C.c_void_p(lg.data_ptr()), ldl, cells, _p(gt_boxes), _p(n_gt), B,
+                                      int(image_offset), _p(rec_key), _p(rec_tp), _stream()), "sv_detect_match")
+    return rec_key, rec_tp
+
+
+def detect_ap_chunk_records():
+    return int(_lib.load().sv_detect_ap_chunk_records())
+
+
+def detect_ap_workspace_bytes(n_records):
+    n = C.c_int64()
+    check(_lib.load().sv_detect_ap_workspace_bytes(int(n_records), C.byref(n)), "sv_detect_ap_workspace_bytes")
+    return int(n.value)
+
+
+def detect_ap_finish(rec_key, rec_tp, n_gt, n_records=None, workspace=None, out=None):
+    """sv_detect_ap_finish over the first n_records records (default: all) -> out [29] fp64 on the device: AP_t [0:9], AP'_t [9:18],
+    then int64 bits (out.view(torch.int64)) TP_t(M) [18:27], M [27], G [28].  workspace: uint8, at least detect_ap_workspace_bytes."""
+    assert rec_key.dtype == torch.int64 and rec_tp.dtype == torch.int16 and n_gt.dtype == torch.int32
+    n = int(rec_key.numel() if n_records is None else n_records)
+    assert 1 <= n <= min(rec_key.numel(), rec_tp.numel())
+    nbytes = detect_ap_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=rec_key.device)
+    assert workspace.dtype == torch.uint8
+    if out is None:
+        out = torch.empty((DETECT_AP_OUT,), dtype=torch.float64, device=rec_key.device)
+    assert out.dtype == torch.float64 and out.numel() == DETECT_AP_OUT
+    check(_lib.load().sv_detect_ap_finish(_p(rec_key), _p(rec_tp), n, _p(n_gt), n_gt.numel(), _p(workspace), workspace.numel(), _p(out),
+                                          _stream()), "sv_detect_ap_finish")
+    return out
+
+
 def adam_alpha(lr, beta1, beta2, t):
     """Keras Adam's bias-corrected step size of iteration t (what sv_adam_step* computes from lr and t)."""
     return float(_lib.load().sv_adam_alpha(float(lr), float(beta1), float(beta2), int(t)))

@@ -7,7 +7,7 @@
 csrc/multibird.hip) with the reference's two test sets (seen / unseen colours).  The CUB sprite blobs are not in the reference's
 repository (spair/data.py:14-15): they are read from --data_dir when present, a procedural stand-in bank is used otherwise.
 --synthetic: 48x48x3 canvases in [0,1] with 0-5 soft-edged blobs on a solid background and the blob count as the label.
-Extra flags (not in the reference): --synthetic, --data_dir, --seed, --log_every, --graph, --dtype, -viz.
+Extra flags (not in the reference): --synthetic, --data_dir, --seed, --log_every, --graph, --dtype, -viz, --detection_ap.
 """
 import argparse
 
@@ -51,6 +51,10 @@ def build_parser():
     ap.add_argument("-viz", action="store_true",
                     help="write the reference's figures (train_recon_it_<step>.png, spair/visualizer.py's test figures) under "
                          "output/<RUN_NAME>/ at every log step (spair_visualizer.py)")
+    ap.add_argument("--detection_ap", action="store_true",
+                    help="report the detection average precision (AP@IoU 0.1 .. 0.9, precision / recall at 0.5) of every test set after "
+                         "its count accuracy (split_vae_amd/detection.py); needs the kernel-rendered Multi-Bird canvases, whose "
+                         "ground-truth boxes are known")
     return ap
 
 
@@ -115,6 +119,10 @@ def main(argv=None):
 
         for t in test_batches:
             t.augment, t.label = (test_augmentor.augment if lg else None), bool(config.label)
+    if config.detection_ap and not all(getattr(t, "boxes", None) is not None for t in test_batches):
+        from . import detection
+        print(detection.UNAVAILABLE)                                        # synthetic canvases / TFRecord test sets: no boxes
+        config.detection_ap = False
     history = None
     for _ in range(args.runs):
         print('Creating model...')

@@ -304,10 +304,30 @@ class CountAccuracy:
         self.acc.zero_()
 
 
+def _detection_state(config, test_ds, det_aps, test_num, device, log):
+    """--detection_ap: the DetectionAP of test set `test_num` (made once), or None when the flag is off or the set carries no
+    ground-truth boxes (synthetic canvases, TFRecord files) -- said once."""
+    if not config.get("detection_ap"):
+        return None
+    if getattr(test_ds, "boxes", None) is None:
+        if not config.get("detection_ap_noted"):
+            from . import detection
+            log(detection.UNAVAILABLE)
+            config.detection_ap_noted = True
+        return None
+    if test_num not in det_aps:
+        from . import detection
+        from .spair_native import CELLS
+        det_aps[test_num] = detection.DetectionAP(device, int(test_ds.boxes.shape[0]), CELLS)
+    return det_aps[test_num]
+
+
 @torch.no_grad()
-def test_step(model, images, config, labels=None, noise=None, count_acc=None):
+def test_step(model, images, config, labels=None, noise=None, count_acc=None, detection=None):
     """spair/trainer.py:236-308 (the reference evaluates with model(images, training=True) too).  labels [B]: the MAE / MAPE of the
-    predicted object counts are appended (:294-300) and `count_acc` (CountAccuracy) counts the exact matches (:301)."""
+    predicted object counts are appended (:294-300) and `count_acc` (CountAccuracy) counts the exact matches (:301).
+    detection = (DetectionAP, gt_boxes [B,5,4], n_gt [B]): the batch's detections are matched against its ground truth
+    (detection.py; one launch on the pass's obj_bbox_mask and z_pres_logits)."""
     if _native_ok(model):
         ns = model.native(images.shape[0], config, training=True)
         lo = ns.run(images, step_scalars(config, 0.0, False), noise=noise, backward=False)
@@ -324,6 +344,8 @@ def test_step(model, images, config, labels=None, noise=None, count_acc=None):
             metrics, _ = ops.spair_count_metrics(ns.output("z_pres_logits"), labels,
                                                  acc=None if count_acc is None else count_acc.acc)
             losses = losses + [metrics[0], metrics[1]]
+        if detection is not None:
+            detection[0].update(ns.output("obj_bbox_mask"), ns.output("z_pres_logits"), detection[1], detection[2])
         return ns.outputs(names), losses
     out = model(images, training=True, noise=noise)
     _, losses = compute_losses(config, images, out, 0.0, training=False)
@@ -334,6 +356,8 @@ def test_step(model, images, config, labels=None, noise=None, count_acc=None):
         losses.append(100.0 * ((lab - pred_count).abs() / lab.abs().clamp_min(1e-7)).mean())
         if count_acc is not None:
             count_acc.update(labels, out[11])
+    if detection is not None:
+        detection[0].update(out[17], out[11], detection[1], detection[2])
     return out[:17] + out[18:], losses
 
 
@@ -354,6 +378,7 @@ def train_spair(model, optimizer, dataset, train_dataset, test_dataset, config, 
         run_dir = os.path.join("output", datetime.now().strftime("%Y%m%d-%H%M%S")) + "/"
         os.makedirs(run_dir, exist_ok=True)
     count_acc = None
+    det_aps = {}
     for step, images in enumerate(train_dataset):
         if config.graph:                                                  # one hipGraph replay per step (GraphedTrainStep)
             if graphed is None:
@@ -379,9 +404,14 @@ def train_spair(model, optimizer, dataset, train_dataset, test_dataset, config, 
                 if count_acc is None:
                     count_acc = CountAccuracy(model.device)
                 ts, tn = None, 0
+                det_ap, seen = _detection_state(config, test_ds, det_aps, test_num, model.device, log), 0
                 for batch in test_ds:
                     imgs, labels = batch if isinstance(batch, (tuple, list)) else (batch, None)
-                    _, tl = test_step(model, imgs, config, labels, count_acc=count_acc)
+                    det = None
+                    if det_ap is not None:
+                        det = (det_ap, test_ds.boxes[seen:seen + imgs.shape[0]], test_ds.n_boxes[seen:seen + imgs.shape[0]])
+                        seen += imgs.shape[0]
+                    _, tl = test_step(model, imgs, config, labels, count_acc=count_acc, detection=det)
                     tv = torch.stack([l.float() for l in tl])
                     ts = tv if ts is None else ts + tv
                     tn += 1
@@ -389,6 +419,12 @@ def train_spair(model, optimizer, dataset, train_dataset, test_dataset, config, 
                 log('Count accuracy' + str(test_num) + ': ' + str(acc))
                 rec["count_acc" + str(test_num)] = float(acc)
                 count_acc.reset_states()
+                if det_ap is not None and seen:
+                    from . import detection
+                    res = det_ap.result()
+                    log(detection.report_line(res, test_num))
+                    rec.update(detection.history_entries(res, test_num))
+                    det_ap.reset_states()
                 if tn:
                     te = dict(zip([nm + str(test_num) for nm in TEST_METRIC_NAMES], (ts / tn).tolist()))
                     log(te)

@@ -43,6 +43,9 @@ _lib_def.define("spair_loss(str mode, Tensor a, Tensor b, float prior_mean, floa
 # SPAIR evaluation (spair/visualizer.py:107-111, spair/trainer.py:294-301): not differentiable
 _lib_def.define("draw_bounding_boxes(Tensor images, Tensor boxes, Tensor colors, Tensor? gate=None) -> Tensor")
 _lib_def.define("spair_count_metrics(Tensor z_pres_logits, Tensor labels, Tensor(a!)? acc=None) -> (Tensor, Tensor)")
+# detection average precision (csrc/detect_ap.hip): not differentiable
+_lib_def.define("detect_match(Tensor bbox, Tensor logits, Tensor gt_boxes, Tensor n_gt, Tensor(a!) rec_key, Tensor(b!) rec_tp, int image_offset=0) -> ()")
+_lib_def.define("detect_ap_finish(Tensor rec_key, Tensor rec_tp, Tensor n_gt) -> Tensor")
 
 ACT = {None: 0, "none": 0, "relu": 1}
 
@@ -300,6 +303,18 @@ def _draw_bounding_boxes(images, boxes, colors, gate=None):
 def _spair_count_metrics(z_pres_logits, labels, acc=None):
     """-> (metrics [2] = (MAE, MAPE), pred_count [B]); acc: int32 [2] counters (matches, images seen), added to in place."""
     return ops.spair_count_metrics(z_pres_logits, labels, acc=acc, want_pred=True)
+
+
+@_impl("detect_match")
+def _detect_match(bbox, logits, gt_boxes, n_gt, rec_key, rec_tp, image_offset=0):
+    """The records (int64 key bits, int16 true-positive masks) of images image_offset .. image_offset + B - 1, written in place."""
+    ops.detect_match(bbox, logits, gt_boxes.contiguous(), n_gt.contiguous(), rec_key, rec_tp, image_offset=image_offset)
+
+
+@_impl("detect_ap_finish")
+def _detect_ap_finish(rec_key, rec_tp, n_gt):
+    """-> out [29] fp64: AP_t, AP'_t, then the int64 bits of TP_t(M), M, G (include/splitvae.h)."""
+    return ops.detect_ap_finish(rec_key.contiguous(), rec_tp.contiguous(), n_gt.contiguous())
 
 
 class _StnFn(torch.autograd.Function):
