@@ -876,6 +876,58 @@ int sv_latent_info_lse(const float* z, int32_t ldz, const float* mu, int32_t ldm
 int sv_latent_info_finish(const double* own, const double* prior, const double* lse, int32_t N, int32_t Ll, double* out /* [8] */,
                           void* stream);
 
+/* ---------------------------------------------------------------- label-free reconstruction quality (csrc/recon_quality.hip)
+ * The three decodes of the reference's labelled test step (vae/trainer.py:213-226: the reconstruction, decode(z_x, random z_l) and
+ * decode(random z_g, z_x_hat)) scored in image space instead of by the classifier whose weights are missing upstream: mean PSNR and
+ * mean SSIM against the original image.  The project's own stand-in for Table 1, as the k-NN probe is; needs no labels.
+ *   images       reference a = (x + 1) * 0.5 from channels 0..2 of the six-channel batch; decode b = clip((x_mean + 1) * 0.5, 0, 1),
+ *                which is decode(rescale=True) (vae/model.py:215), from channels 0..2 of the plan's out6_x; max_val = 1.  Both are
+ *                NHWC fp32 and read IN PLACE: base pointer, pixel pitch in floats, channel offset (three channels from there).
+ *   PSNR         per image 10 log10(1 / max(MSE_i, 1e-10)), MSE_i over H*W*3 (the tf.image.psnr convention; the floor only keeps an
+ *                exact copy finite: 100 dB); reported: the mean over images.
+ *   SSIM         the defaults of tf.image.ssim (Wang et al. 2004): 11 x 11 Gaussian window of sigma 1.5 normalised to sum 1
+ *                (separable: the outer product of sv_recon_window's 11 fp64 taps), population moments mu_a, mu_b, var_a = E[a^2] -
+ *                mu_a^2, var_b, cov = E[a b] - mu_a mu_b, C1 = 0.01^2, C2 = 0.03^2,
+ *                ((2 mu_a mu_b + C1)(2 cov + C2)) / ((mu_a^2 + mu_b^2 + C1)(var_a + var_b + C2)) over the VALID region only,
+ *                (H-10) x (W-10) windows, per channel; per image the mean over windows and the three channels; reported: the mean
+ *                over images.
+ *   arithmetic   every pixel is converted to fp64 when it is loaded and everything after that is fp64 (the rescale and the clip are
+ *                then exact): the moments' cancellation leaves ~1e-15 against C2 = 9e-4.
+ *   kept blocks  are the posterior MEANS (the reference keeps a posterior sample z_x / z_x_hat): the figures are a function of the
+ *                weights and the seed alone.
+ *   drawn blocks eps [B, Lg+Ll] (row pitch lde) pins the normals; NULL: Philox4x32-10 with a key constant of this report's own
+ *                (seed ^ 0x1a7e2c0a11f7) and counter (dimension j within its block, global image index sample_offset + b, 'rq' tag |
+ *                mode << 4 | 0 global / 1 local, 0) and the Box-Muller of sv_iw_advance: image i draws the same numbers whatever batch
+ *                it sits in.  The global block's prior is N(0, I) when pm, ps are NULL; otherwise the uniform mixture over the n rows
+ *                of pm, ps [n, Lg] (encode_y of the identity, vae/model.py:263-265): z_g = pm[c] + ps[c] * eps (fp32: one multiply,
+ *                one add), c = comp[b] clamped to 0..n-1, or with comp NULL floor(u32 * n / 2^32) of the first word of counter
+ *                (0, image, tag | 2, 0).
+ * sv_recon_draw: zcat [B, Lg+Ll] (row pitch ldz, dtype SV_F32 or SV_BF16: fp32 rounded to nearest even) = [z_g | z_l].
+ *   SV_RECON_MEANS: both blocks are z_mean_x [B,Lg] (ldg), z_mean_xh [B,Ll] (ldl); SV_RECON_KEEP_G: z_l is drawn from N(0, I);
+ *   SV_RECON_KEEP_L: z_g is drawn from its prior.  Ll = 0 is the one-branch model (z_mean_xh may be NULL).  One wave per image.
+ * sv_recon_quality: per_image [B,2] fp64 = (MSE_i, SSIM_i) of a against b (clip_b != 0: b is clipped to [0,1] after the rescale; a
+ *   never is).  Work is split over (image, band of 8 output rows, tile of up to 75 output columns); each tile leaves one fp64 pair in
+ *   the workspace (sv_recon_quality_workspace_bytes; 8-byte aligned; may hold anything on entry) and one thread per image adds them in
+ *   tile order.  Outputs are overwritten.  No atomics: the same inputs give the same bits.
+ * sv_recon_finish: acc [3] fp64 += (sum_i PSNR_i, sum_i SSIM_i, B) over per_image [B,2], added onto the accumulator in image order
+ *   by one thread (the caller zeroes acc once; one accumulator per variant, read back once per evaluation).
+ * Everything is enqueued on `stream`; no host synchronisation.  Accepted domain: B >= 1, 11 <= H, W <= 16384, B * tiles < 2^31,
+ * 0 <= offset, offset + 3 <= pitch <= 4096, 1 <= Lg <= 512, 0 <= Ll <= 512, 1 <= n <= 4096, row pitches >= their widths,
+ * sample_offset >= 0, a known mode and dtype: anything else SV_E_UNSUPPORTED; a null pointer (eps, comp, pm and ps may be NULL, pm and
+ * ps only together; z_mean_xh when Ll = 0) or a misaligned one: SV_E_BADARG; workspace_bytes too small: SV_E_WORKSPACE.  All checked
+ * before anything is enqueued. */
+enum { SV_RECON_MEANS = 0, SV_RECON_KEEP_G = 1, SV_RECON_KEEP_L = 2 };
+void sv_recon_window(double* w /* [11] */);
+int sv_recon_quality_workspace_bytes(int32_t B, int32_t H, int32_t W, int64_t* bytes);
+int sv_recon_draw(const float* z_mean_x, int32_t ldg, const float* z_mean_xh /* or NULL */, int32_t ldl, int32_t mode,
+                  const float* eps /* or NULL */, int32_t lde, const int32_t* comp /* [B] or NULL */, const float* pm /* or NULL */,
+                  const float* ps /* or NULL */, int32_t n, void* zcat, int32_t ldz, int32_t dtype, int32_t B, int32_t Lg, int32_t Ll,
+                  uint64_t seed, int64_t sample_offset, void* stream);
+int sv_recon_quality(const float* a, int32_t pitch_a, int32_t off_a, const float* b, int32_t pitch_b, int32_t off_b, int32_t clip_b,
+                     int32_t B, int32_t H, int32_t W, double* per_image /* [B,2] */, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int sv_recon_finish(const double* per_image /* [B,2] */, int32_t B, double* acc /* [3] */, void* stream);
+
 /* ---------------------------------------------------------------- SPLIT-SPAIR: Dense layers, exact fp32 on the matrix cores
  * tf.keras.layers.Dense (spair/spair.py:135-154, :185-202, :246-273, :341-366, :424-467) for ANY fan-in / fan-out, reading the Keras
  * [in, out] kernel as it lies in the variable buffer (dense_f32.hip).  x [M, ldx], y / dy [M, ldy], w [K, N] row-major.

@@ -21,6 +21,7 @@ PHASE_INFER = PHASE_PREP | PHASE_FORWARD
 IW_ACCUMULATE, IW_DRAW = 1, 2      # sv_iw_advance flags (include/splitvae.h)
 KNN_MAX_K, KNN_MAX_L, KNN_MAX_CLASSES = 32, 512, 64      # accepted domain of sv_knn_classify (include/splitvae.h)
 LATENT_INFO_MAX_L = 512            # accepted width of either latent block of sv_latent_info_* (include/splitvae.h)
+RECON_MEANS, RECON_KEEP_G, RECON_KEEP_L = 0, 1, 2        # sv_recon_draw modes (include/splitvae.h)
 
 STATUS = {0: "SV_OK", -1: "SV_E_BADARG", -2: "SV_E_UNSUPPORTED", -3: "SV_E_WORKSPACE", -4: "SV_E_STATE"}
 STATUS_BADARG, STATUS_UNSUPPORTED, STATUS_WORKSPACE, STATUS_STATE = -1, -2, -3, -4
@@ -290,6 +291,11 @@ SYMBOLS = {
     "sv_latent_info_draw": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _u64, _i64, _vp]),
     "sv_latent_info_lse": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
     "sv_latent_info_finish": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "sv_recon_window": (None, [C.POINTER(C.c_double)]),
+    "sv_recon_quality_workspace_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "sv_recon_draw": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _u64, _i64, _vp]),
+    "sv_recon_quality": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "sv_recon_finish": (C.c_int, [_vp, _i32, _vp, _vp]),
 }
 
 _lib = None

@@ -4,7 +4,7 @@
     python -m split_vae_amd.main --model gmvae --beta 40 --patch_size 4       (GMVAE baseline, Table 2)
 
 Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout, --mix_per_image,
---resident_data, --iw_samples, --gm_iw_samples, --knn_probe, --knn_refs, --latent_info.
+--resident_data, --iw_samples, --gm_iw_samples, --knn_probe, --knn_refs, --latent_info, --recon_quality.
 """
 import argparse
 
@@ -61,6 +61,10 @@ def build_parser():
                     help="N >= 2: after the report of every evaluation, the aggregate-posterior information report over the first N "
                          "test images: per latent block the KL term split into index-code mutual information and marginal KL, and the "
                          "mutual information of z_g and z_l (split_vae_amd/latent_info.py); needs no labels")
+    ap.add_argument("--recon_quality", type=int, default=0,
+                    help="N >= 1: after the report of every evaluation, the mean PSNR and SSIM against the original image, over the first "
+                         "N test images, of the reconstruction and of the decodes with z_l, then z_g, drawn from its prior "
+                         "(split_vae_amd/recon_quality.py); needs no labels")
     return ap
 
 
@@ -139,6 +143,8 @@ def main(argv=None):
     check_flags(args.knn_probe, args.knn_refs, args.no_label)
     from .latent_info import check_flags as check_latent_info
     check_latent_info(args.latent_info, args.global_latent_dims, args.local_latent_dims if args.model != 'gmvae' else 0)
+    from .recon_quality import check_flags as check_recon_quality
+    check_recon_quality(args.recon_quality)
     from . import configure_hw_queues
     configure_hw_queues()                            # before the first HIP call (split_vae_amd/__init__.py)
     config = dotdict(vars(args))

@@ -1019,6 +1019,98 @@ def latent_info_finish(own, prior, lse, Ll, out=None):
     return out
 
 
+# ------------------------------------------------------------------ label-free reconstruction quality (include/splitvae.h)
+def recon_window():
+    """The 11 fp64 taps of the SSIM window (sigma 1.5, normalised to sum 1) as the kernel uses them."""
+    w = (C.c_double * 11)()
+    _lib.load().sv_recon_window(w)
+    return list(w)
+
+
+def recon_quality_workspace_bytes(B, H, W):
+    n = C.c_int64()
+    check(_lib.load().sv_recon_quality_workspace_bytes(int(B), int(H), int(W), C.byref(n)), "sv_recon_quality_workspace_bytes")
+    return n.value
+
+
+def recon_draw(z_mean_x, z_mean_xh, mode, zcat, eps=None, comp=None, prior=None, seed=0, sample_offset=0):
+    """sv_recon_draw: zcat [B, Lg+Ll] (fp32 or bf16; a row pitch above its width is allowed) = [z_g | z_l] from the posterior means
+    z_mean_x [B,Lg], z_mean_xh [B,Ll] (None: Ll = 0).  mode: _lib.RECON_MEANS | RECON_KEEP_G (z_l ~ N(0, I)) | RECON_KEEP_L (z_g ~ its
+    prior: N(0, I), or with prior = (pm, ps) [n, Lg] the uniform mixture over their rows).  eps [B, Lg+Ll] pins the normals, comp [B]
+    int32 the components; otherwise image sample_offset + b draws from (seed, image, mode, block)."""
+    gp, ldg = _rows_f32(z_mean_x, "z_mean_x")
+    B, Lg = z_mean_x.shape
+    dev = z_mean_x.device
+    lp, ldl, Ll = None, 0, 0
+    if z_mean_xh is not None:
+        Ll = int(z_mean_xh.shape[1])
+        lp, ldl = _same_rows(z_mean_xh, "z_mean_xh", B, Ll, dev)
+    Lc = Lg + Ll
+    ep, lde = (None, 0) if eps is None else _same_rows(eps, "eps", B, Lc, dev)
+    if not torch.is_tensor(zcat) or zcat.dtype not in _SV_DT or tuple(zcat.shape) != (B, Lc) or zcat.device != dev or zcat.stride(1) != 1 or \
+            zcat.stride(0) < Lc:
+        raise ValueError("zcat must be a [%d,%d] fp32 / bf16 device tensor with contiguous rows" % (B, Lc))
+    if comp is not None and (comp.dtype != torch.int32 or tuple(comp.shape) != (B,) or not comp.is_contiguous() or comp.device != dev):
+        raise ValueError("comp must be a contiguous [%d] int32 device tensor" % B)
+    pmp, psp, n = None, None, 0
+    if prior is not None:
+        pm, ps = prior
+        n = int(pm.shape[0])
+        for t, name in ((pm, "pm"), (ps, "ps")):
+            if t.dtype != torch.float32 or tuple(t.shape) != (n, Lg) or not t.is_contiguous() or t.device != dev:
+                raise ValueError("%s must be a contiguous [n,%d] fp32 device tensor" % (name, Lg))
+        pmp, psp = _p(pm), _p(ps)
+    check(_lib.load().sv_recon_draw(gp, ldg, lp, ldl, int(mode), ep, lde, _p(comp), pmp, psp, n, C.c_void_p(zcat.data_ptr()),
+                                    int(zcat.stride(0)), sv_dtype(zcat.dtype), B, Lg, Ll, int(seed), int(sample_offset), _stream()),
+          "sv_recon_draw")
+    return zcat
+
+
+def _nhwc_f32(t, name, off):
+    if not torch.is_tensor(t) or t.dim() != 4 or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous [B,H,W,C] fp32 device tensor" % name)
+    if not 0 <= int(off) <= t.shape[3] - 3:
+        raise ValueError("%s: channels %d .. %d of %d" % (name, off, off + 2, t.shape[3]))
+    return _p(t), int(t.shape[3])
+
+
+def recon_quality(a, b, off_a=0, off_b=0, clip_b=True, per_image=None, workspace=None):
+    """sv_recon_quality: per_image [B,2] fp64 = (MSE_i, SSIM_i) of channels off_a .. off_a+2 of a [B,H,W,Ca] (the image in [-1,1])
+    against channels off_b .. off_b+2 of b [B,H,W,Cb] (the decoder mean), both rescaled by (x + 1) / 2 and b clipped to [0,1] when
+    clip_b; both are read in place.  workspace: a uint8 device tensor of at least recon_quality_workspace_bytes(B, H, W) bytes with any
+    contents (default: allocated here)."""
+    ap, pa = _nhwc_f32(a, "a", off_a)
+    bp, pb = _nhwc_f32(b, "b", off_b)
+    B, H, W = a.shape[:3]
+    if tuple(b.shape[:3]) != (B, H, W) or b.device != a.device:
+        raise ValueError("a %s and b %s must share B, H, W and the device" % (tuple(a.shape), tuple(b.shape)))
+    if per_image is None:
+        per_image = torch.empty((B, 2), dtype=torch.float64, device=a.device)
+    if per_image.dtype != torch.float64 or tuple(per_image.shape) != (B, 2) or not per_image.is_contiguous() or per_image.device != a.device:
+        raise ValueError("per_image must be a contiguous [%d,2] fp64 device tensor" % B)
+    nbytes = recon_quality_workspace_bytes(B, H, W)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=a.device) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous():
+        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    check(_lib.load().sv_recon_quality(ap, pa, int(off_a), bp, pb, int(off_b), int(bool(clip_b)), B, H, W, _p(per_image), _p(ws), ws.numel(),
+                                       _stream()), "sv_recon_quality")
+    return per_image
+
+
+def recon_finish(per_image, acc, n=None):
+    """sv_recon_finish: acc [3] fp64 += (sum PSNR_i, sum SSIM_i, n) over the first n rows of per_image [B,2] (default: all)."""
+    f64 = torch.float64
+    if per_image.dtype != f64 or per_image.dim() != 2 or per_image.shape[1] != 2 or not per_image.is_contiguous() or not per_image.is_cuda:
+        raise ValueError("per_image must be a contiguous [B,2] fp64 device tensor")
+    n = per_image.shape[0] if n is None else int(n)
+    if not 1 <= n <= per_image.shape[0]:
+        raise ValueError("recon_finish: n = %d of %d images" % (n, per_image.shape[0]))
+    if acc.dtype != f64 or acc.numel() != 3 or not acc.is_contiguous() or acc.device != per_image.device:
+        raise ValueError("acc must be a contiguous [3] fp64 device tensor")
+    check(_lib.load().sv_recon_finish(_p(per_image), n, _p(acc), _stream()), "sv_recon_finish")
+    return acc
+
+
 # ------------------------------------------------------------------ A9 SPLIT-GMVAE glue (vae/model.py:48-79,:116-135)
 ACT ={None: _lib.SV_ACT_NONE, "relu": _lib.SV_ACT_RELU, "elu": _lib.SV_ACT_ELU}
 

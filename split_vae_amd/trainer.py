@@ -215,6 +215,7 @@ def train_local_global_autoencoder(model, optimizer, dataset, train_dataset, tes
                 print(iw.report_line(config.iw_samples, iw.evaluate(model, test_dataset, config.iw_samples)))
             _knn_probe_report(model, test_dataset, config, step)
             _latent_info_report(model, test_dataset, config, step)
+            _recon_quality_report(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             # vae/trainer.py:405-414 resets x_recon / x_kl / total_kl but never the x_hat_* means
             metrics.reset_states(["x_recon_loss", "x_kl_loss", "total_kl_loss"])
@@ -247,6 +248,15 @@ def _latent_info_report(model, test_dataset, config, step):
         return None
     from . import latent_info
     return latent_info.report(model, test_dataset, config, step)
+
+
+def _recon_quality_report(model, test_dataset, config, step):
+    """--recon_quality N: the label-free reconstruction quality report (recon_quality.py) behind an evaluation's report; the figures
+    are kept in config.recon_quality_history: one dict per evaluation."""
+    if int(config.get("recon_quality") or 0) <= 0:
+        return None
+    from . import recon_quality
+    return recon_quality.report(model, test_dataset, config, step)
 
 
 def _gm_iw_report(model, test_dataset, config, step):
@@ -336,6 +346,7 @@ def _train_lggmvae(model, optimizer, train_dataset, test_dataset, config):
             _gm_iw_report(model, test_dataset, config, step)
             _knn_probe_report(model, test_dataset, config, step)
             _latent_info_report(model, test_dataset, config, step)
+            _recon_quality_report(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             acc, n_acc = None, 0
             start = time.time()
@@ -394,6 +405,7 @@ def _train_gmvae(model, optimizer, train_dataset, test_dataset, config):
             _gm_iw_report(model, test_dataset, config, step)
             _knn_probe_report(model, test_dataset, config, step)
             _latent_info_report(model, test_dataset, config, step)
+            _recon_quality_report(model, test_dataset, config, step)
             acc, n_acc = None, 0
             start = time.time()
         if step >= config.training_steps:
