@@ -167,6 +167,23 @@ int sv_dlogistic_nll(const float* images6, int32_t ch_off, const float* out6, fl
                      void* grad, int32_t grad_dtype, float grad_scale,
                      int32_t B, int32_t H, int32_t W, float* partial_ws, void* stream);
 int64_t sv_dlogistic_nll_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* The x and the x-hat reconstruction in one launch, as the plan calls it (for tests and host bindings): network e reads channels [3e, 3e+3)
+ * of images6 and its buffers lie e strides behind the given pointers -- out6 + e*zs_out, nll + e*zs_nll, grad + e*zs_grad, partial_ws +
+ * e*zs_part, strides in ELEMENTS of the buffer's type.  grad NULL: no gradients.  partial_ws holds 2 * sv_dlogistic_nll_workspace_bytes.
+ * The same bits as two sv_dlogistic_nll calls.  SV_E_BADARG: a null images6 / out6 / nll / partial_ws, B, H or W <= 0, a stride shorter than
+ * one network's buffer, an odd zs_out, images6 / out6 not 8-byte aligned; with grad: a dtype outside sv_dtype, grad not 16-byte aligned or
+ * zs_grad no multiple of the elements of 16 bytes. */
+int sv_dlogistic_nll_twin(const float* images6, const float* out6, int64_t zs_out, float* nll, int64_t zs_nll, void* grad, int64_t zs_grad,
+                          int32_t grad_dtype, float grad_scale, int32_t B, int32_t H, int32_t W, float* partial_ws, int64_t zs_part,
+                          void* stream);
+/* The step's loss finaliser (vae/trainer.py:127-135, :140-144), as the plan calls it (for tests and host bindings).  Per-image terms nll_x,
+ * nll_xh, kl_x, kl_xh [B] -> losses[6] = batch means {x_recon, x_kl, x_hat_recon, x_hat_kl, beta (x_kl + x_hat_kl), x_recon + x_hat_recon +
+ * total_kl}; a NULL nll_xh / kl_x / kl_xh counts as zeros (a one-branch model).  part_x [B][P] (and part_xh) given: nll_x (nll_xh) is first
+ * WRITTEN as the index-order sum of its P partials.  accumulate != 0: metric_acc[0..4] += losses[0..4], metric_acc[5] += 1.
+ * SV_E_BADARG: a null nll_x / losses, B <= 0, accumulate without metric_acc, part_xh without part_x, with part_x: P <= 0, or part_xh given
+ * and nll_xh not (or the reverse). */
+int sv_finalize_losses(float* nll_x, float* nll_xh, const float* kl_x, const float* kl_xh, const float* part_x, const float* part_xh,
+                       int32_t P, int32_t B, float beta, float* losses, float* metric_acc, int32_t accumulate, void* stream);
 
 /* ---------------------------------------------------------------- A4+A7: reparameterise + KL
  * Replaces Sampling.call (vae/model.py:9-13), the Dense bias/softplus epilogues of e4_mean/e4_sd

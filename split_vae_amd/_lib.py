@@ -159,6 +159,8 @@ SYMBOLS = {
     "sv_dataset_onehot": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "sv_dlogistic_nll": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _f, _i32, _i32, _i32, _vp, _vp]),
     "sv_dlogistic_nll_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "sv_dlogistic_nll_twin": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _f, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "sv_finalize_losses": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f, _vp, _vp, _i32, _vp]),
     "sv_reparam_kl_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32,
                                     _u64, _u64, _i32, _i64, _vp]),
     "sv_reparam_kl_bwd": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _f, _vp, _i32, _i32, _i32, _vp]),

@@ -283,6 +283,25 @@ extern "C" int sv_dlogistic_nll(const float* images6, int32_t ch_off, const floa
                                  0, 1, (hipStream_t)stream);
 }
 
+// the x and x-hat reconstructions in one launch as the plan makes it (nets = 2, ch_off = 0: the TWIN instantiation), for tests and host
+// bindings (include/splitvae.h): argument checks, then the launcher above
+extern "C" int sv_dlogistic_nll_twin(const float* images6, const float* out6, int64_t zs_out, float* nll, int64_t zs_nll, void* grad,
+                                     int64_t zs_grad, int32_t grad_dtype, float grad_scale, int32_t B, int32_t H, int32_t W,
+                                     float* partial_ws, int64_t zs_part, void* stream) {
+  if (!images6 || !out6 || !nll || !partial_ws || B <= 0 || H <= 0 || W <= 0) return SV_E_BADARG;
+  const int64_t npix = (int64_t)B * H * W;
+  // the second network's buffers may not overlap the first's; out6 is read by 8-byte pieces
+  if (zs_out < npix * 6 || (zs_out & 1) || zs_nll < B || zs_part < (int64_t)B * dll_parts(H * W)) return SV_E_BADARG;
+  if (grad) {
+    if (grad_dtype != SV_BF16 && grad_dtype != SV_F32) return SV_E_BADARG;
+    // grad is written by 16-byte pieces
+    if (zs_grad < npix * 8 || zs_grad % (grad_dtype == SV_BF16 ? 8 : 4) || ((uintptr_t)grad & 15)) return SV_E_BADARG;
+  }
+  if (((uintptr_t)images6 | (uintptr_t)out6) & 7) return SV_E_BADARG;
+  return svk_dlogistic_nll_multi(images6, 0, out6, zs_out, nll, zs_nll, grad, zs_grad, grad_dtype, grad_scale, B, H, W, partial_ws, zs_part,
+                                 2, (hipStream_t)stream);
+}
+
 // ============================================================================ A4 + A7 reparam / KL
 template <typename TZ>
 __device__ __forceinline__ void reparam_kl_fwd_body(const ReparamFwdArgs& g, int B, uint64_t seed, uint64_t step, int64_t sample_offset) {
@@ -587,17 +606,27 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, c
 struct GradPtrs { const float* g[SV_CLIP_MAX_TENSORS]; };
 __global__ __launch_bounds__(256) void sumsq_ptrs_kernel(const GradPtrs P, const int64_t* __restrict__ off, float* __restrict__ parts, float gscale) {
   const int t = blockIdx.y;
-  const int64_t n = off[t + 1] - off[t];
-  const float* __restrict__ g = P.g[t];                       // 16-byte aligned (its own allocation)
+  const int64_t lo = off[t], hi = off[t + 1];
+  const float* __restrict__ g = P.g[t] - lo;                  // g[i], i in [lo, hi): the flat index, as in adam_clip_ptrs_kernel
+  // the split of sumsq_kernel (head / float4 body / tail by the FLAT offset), so that a tensor's partial sums -- and with them its clip factor and
+  // the whole update -- are bit for bit those of the flat-buffer call wherever the tensor lies
+  int64_t a, b;
+  clip_split(lo, hi, a, b);
   float s = 0.f;
-  const int64_t n4 = n >> 2;
+  const int64_t n4 = (b - a) >> 2;
+  const bool galigned = ((a - lo) & 3) == 0;                  // the gradient tensor starts at its own 16-byte boundary
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)SV_CLIP_PARTS * 256) {
-    const float4 v = ((const float4*)g)[i];
+    const float* gi = g + a + 4 * i;
+    float4 v;
+    if (galigned) v = *(const float4*)gi;
+    else v = make_float4(gi[0], gi[1], gi[2], gi[3]);
     const float x = v.x * gscale, y = v.y * gscale, z = v.z * gscale, w = v.w * gscale;
     s += (x * x + y * y) + (z * z + w * w);
   }
-  if (blockIdx.x == 0)
-    for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += 256) { const float v = g[i] * gscale; s += v * v; }
+  if (blockIdx.x == 0) {                                   // head and tail (at most 3 elements each)
+    for (int64_t i = lo + threadIdx.x; i < a; i += 256) { const float v = g[i] * gscale; s += v * v; }
+    for (int64_t i = b + threadIdx.x; i < hi; i += 256) { const float v = g[i] * gscale; s += v * v; }
+  }
   __shared__ float red[4];
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -978,4 +1007,13 @@ int svk_finalize_losses(const float* nll_x, const float* nll_xh, const float* kl
                      beta, losses, metric_acc, accumulate, part_x, part_xh, P);
   SV_LAUNCH_CHECK();
   return SV_OK;
+}
+
+// the loss finaliser as the plan launches it, for tests and host bindings (include/splitvae.h): argument checks, then the launcher above
+extern "C" int sv_finalize_losses(float* nll_x, float* nll_xh, const float* kl_x, const float* kl_xh, const float* part_x,
+                                  const float* part_xh, int32_t P, int32_t B, float beta, float* losses, float* metric_acc,
+                                  int32_t accumulate, void* stream) {
+  if (!nll_x || !losses || B <= 0 || (accumulate && !metric_acc)) return SV_E_BADARG;
+  if (part_x ? (P <= 0 || !part_xh != !nll_xh) : part_xh != nullptr) return SV_E_BADARG;
+  return svk_finalize_losses(nll_x, nll_xh, kl_x, kl_xh, B, beta, losses, metric_acc, accumulate, (hipStream_t)stream, part_x, part_xh, P);
 }

@@ -52,21 +52,25 @@ def _p(t):
 
 
 # ------------------------------------------------------------------ A1 scramble (augmentation.py:43-57)
-def random_perm(B, n_patch, seed, step=0, sample_offset=0, device="cuda"):
-    perm = torch.empty((B, n_patch), dtype=torch.int32, device=device)
+def random_perm(B, n_patch, seed, step=0, sample_offset=0, device="cuda", out=None):
+    """out: an int32 buffer of at least B * n_patch elements to write instead of a fresh one (the rest of it is not touched)"""
+    perm = torch.empty((B, n_patch), dtype=torch.int32, device=device) if out is None else out
     check(_lib.load().sv_random_perm(_p(perm), B, n_patch, seed, step, sample_offset, _stream()), "sv_random_perm")
     return perm
 
 
-def scramble_gather(x, perm, patch, staged=None):
-    """x[B,H,W,3] fp32, perm[B,(H/patch)^2] int32 -> [B,H,W,6] = concat([x, x_aug], axis=-1)."""
+def scramble_gather(x, perm, patch, staged=None, out=None):
+    """x[B,H,W,3] fp32, perm[B,(H/patch)^2] int32 -> [B,H,W,6] = concat([x, x_aug], axis=-1).  out: a float32 buffer of at least
+    B*H*W*6 elements to write instead of a fresh one."""
     B, H, W, Cc = x.shape
     assert Cc == 3 and x.dtype == torch.float32 and perm.dtype == torch.int32
     assert perm.shape == (B, (H // patch) * (W // patch))
-    out = torch.empty((B, H, W, 6), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((B, H, W, 6), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.numel() >= B * H * W * 6
     if staged is not None:                       # (x8, xh8): a plan's in8_x / in8_xh buffers, filled in the same pass
         x8, xh8 = staged
-        assert x8.shape == (B, H, W, 8) and xh8.shape == (B, H, W, 8) and x8.dtype == xh8.dtype
+        assert x8.numel() >= B * H * W * 8 and xh8.numel() >= B * H * W * 8 and x8.dtype == xh8.dtype
         check(_lib.load().sv_scramble_gather_staged(_p(x), _p(perm), _p(out), _p(x8), _p(xh8), sv_dtype(x8.dtype), B, H, W, patch,
                                                     _stream()), "sv_scramble_gather_staged")
         return out
@@ -243,14 +247,19 @@ def multibird_canvases(sprites, bg, B, seed, split, sample_offset=0, index=None,
 
 
 # ------------------------------------------------------------------ A6 discretised logistic (vae/trainer.py:21-38)
-def dlogistic_nll(images6, ch_off, out6, grad_dtype=None, grad_scale=1.0):
+def dlogistic_nll(images6, ch_off, out6, grad_dtype=None, grad_scale=1.0, nll=None, grad=None, ws=None):
+    """nll / grad / ws: buffers to write instead of fresh ones (at least B, B*H*W*8 and sv_dlogistic_nll_workspace_bytes / 4 elements)"""
     B, H, W, _ = images6.shape
     lib = _lib.load()
-    nll = torch.empty((B,), dtype=torch.float32, device=images6.device)
-    ws = torch.empty((lib.sv_dlogistic_nll_workspace_bytes(B, H, W) // 4,), dtype=torch.float32, device=images6.device)
-    grad = None
+    if nll is None:
+        nll = torch.empty((B,), dtype=torch.float32, device=images6.device)
+    if ws is None:
+        ws = torch.empty((lib.sv_dlogistic_nll_workspace_bytes(B, H, W) // 4,), dtype=torch.float32, device=images6.device)
     gdt = 0
-    if grad_dtype is not None:
+    if grad is not None:
+        gdt = sv_dtype(grad.dtype)
+        assert grad.numel() >= B * H * W * 8
+    elif grad_dtype is not None:
         gdt = sv_dtype(grad_dtype)
         grad = torch.empty((B, H, W, 8), dtype=_TORCH_DT[gdt], device=images6.device)
     check(lib.sv_dlogistic_nll(_p(images6), ch_off, _p(out6), _p(nll), _p(grad), gdt, grad_scale, B, H, W, _p(ws),
@@ -258,26 +267,57 @@ def dlogistic_nll(images6, ch_off, out6, grad_dtype=None, grad_scale=1.0):
     return nll, grad
 
 
+def dlogistic_nll_twin(images6, out6, nll, ws, grad=None, grad_scale=1.0):
+    """sv_dlogistic_nll_twin: the x and x-hat reconstructions in one launch.  out6 [2, B, H, W, 6], nll [2, >= B], ws [2, >= workspace floats]
+    and grad [2, >= B*H*W*8] (or None) hold network e at index e of their first axis; its stride is what the call passes."""
+    B, H, W, _ = images6.shape
+    for t in (out6, nll, ws) + (() if grad is None else (grad,)):
+        assert t.shape[0] == 2 and t[0].is_contiguous()
+    check(_lib.load().sv_dlogistic_nll_twin(_p(images6), _pany(out6), out6.stride(0), _pany(nll), nll.stride(0), _pany(grad),
+                                            0 if grad is None else grad.stride(0), 0 if grad is None else sv_dtype(grad.dtype), grad_scale,
+                                            B, H, W, _pany(ws), ws.stride(0), _stream()), "sv_dlogistic_nll_twin")
+
+
+def dlogistic_nll_workspace_floats(B, H, W):
+    return _lib.load().sv_dlogistic_nll_workspace_bytes(B, H, W) // 4
+
+
+def finalize_losses(nll_x, beta, losses, nll_xh=None, kl_x=None, kl_xh=None, part_x=None, part_xh=None, P=0, metric_acc=None, accumulate=False,
+                    B=None):
+    """sv_finalize_losses: per-image terms [B] -> losses[6] (and the running sums metric_acc[6]); with part_x [B, P] (part_xh) the per-image
+    NLL sums are formed here from the partials and written to nll_x (nll_xh).  B defaults to nll_x.numel()."""
+    B = nll_x.numel() if B is None else B
+    check(_lib.load().sv_finalize_losses(_pany(nll_x), _pany(nll_xh), _pany(kl_x), _pany(kl_xh), _pany(part_x), _pany(part_xh), P, B,
+                                         float(beta), _pany(losses), _pany(metric_acc), int(bool(accumulate)), _stream()), "sv_finalize_losses")
+
+
 # ------------------------------------------------------------------ A4/A7 reparam + KL
-def reparam_kl_fwd(pre, bias, eps=None, z_dtype=torch.bfloat16, seed=0, step=0, stream_id=0, sample_offset=0):
+def reparam_kl_fwd(pre, bias, eps=None, z_dtype=torch.bfloat16, seed=0, step=0, stream_id=0, sample_offset=0, out=None):
+    """out: (z_mean, z_sig, z, z_lp, kl, eps_out) buffers to write instead of fresh ones: at least [B, L] ([B] for kl), z_lp in z_dtype"""
     B, L2 = pre.shape
     L = L2 // 2
     dev = pre.device
-    z_mean = torch.empty((B, L), dtype=torch.float32, device=dev)
-    z_sig = torch.empty_like(z_mean)
-    z = torch.empty_like(z_mean)
-    eps_out = torch.empty_like(z_mean)
-    kl = torch.empty((B,), dtype=torch.float32, device=dev)
-    z_lp = torch.empty((B, L), dtype=z_dtype, device=dev)
+    if out is not None:
+        z_mean, z_sig, z, z_lp, kl, eps_out = out
+        assert z_lp.dtype == z_dtype and min(t.numel() for t in (z_mean, z_sig, z, z_lp, eps_out)) >= B * L and kl.numel() >= B
+    else:
+        z_mean = torch.empty((B, L), dtype=torch.float32, device=dev)
+        z_sig = torch.empty_like(z_mean)
+        z = torch.empty_like(z_mean)
+        eps_out = torch.empty_like(z_mean)
+        kl = torch.empty((B,), dtype=torch.float32, device=dev)
+        z_lp = torch.empty((B, L), dtype=z_dtype, device=dev)
     check(_lib.load().sv_reparam_kl_fwd(_p(pre), _p(bias), _p(eps), _p(eps_out), _p(z_mean), _p(z_sig), _p(z),
                                         _p(z_lp), sv_dtype(z_dtype), L, 0, _p(kl), B, L, seed, step, stream_id,
                                         sample_offset, _stream()), "sv_reparam_kl_fwd")
     return z_mean, z_sig, z, z_lp, kl, eps_out
 
 
-def reparam_kl_bwd(dz, z_mean, z_sig, eps, kl_scale, g_dtype=torch.bfloat16, dz2=None):
+def reparam_kl_bwd(dz, z_mean, z_sig, eps, kl_scale, g_dtype=torch.bfloat16, dz2=None, out=None):
+    """out: a g_dtype buffer of at least B * 2L elements to write instead of a fresh one"""
     B, L = z_mean.shape
-    g = torch.empty((B, 2 * L), dtype=g_dtype, device=dz.device)
+    g = torch.empty((B, 2 * L), dtype=g_dtype, device=dz.device) if out is None else out
+    assert g.dtype == g_dtype and g.numel() >= B * 2 * L
     check(_lib.load().sv_reparam_kl_bwd(_p(dz), dz.shape[1], _p(dz2), 0 if dz2 is None else dz2.shape[1],
                                         _p(z_mean), _p(z_sig), _p(eps), kl_scale, _p(g), sv_dtype(g_dtype), B, L,
                                         _stream()), "sv_reparam_kl_bwd")
@@ -285,22 +325,27 @@ def reparam_kl_bwd(dz, z_mean, z_sig, eps, kl_scale, g_dtype=torch.bfloat16, dz2
 
 
 # ------------------------------------------------------------------ K14 Keras Adam (vae/main.py:65)
-def adam_step(p, g, m, v, t, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
-    check(_lib.load().sv_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, t, grad_scale,
+def adam_step(p, g, m, v, t, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, n=None):
+    """n: the number of elements to update (default: all of p)"""
+    check(_lib.load().sv_adam_step(_pany(p), _pany(g), _pany(m), _pany(v), p.numel() if n is None else n, lr, beta1, beta2, eps, t, grad_scale,
                                    _stream()), "sv_adam_step")
 
 
 # ------------------------------------------------------------------ K10a bilinear 2x (vae/model.py:163-167)
-def upsample2x_fwd(x):
+def upsample2x_fwd(x, out=None):
     B, H, W, Cc = x.shape
-    out = torch.empty((B, 2 * H, 2 * W, Cc), dtype=x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty((B, 2 * H, 2 * W, Cc), dtype=x.dtype, device=x.device)
+    assert out.dtype == x.dtype and out.numel() >= 4 * x.numel()
     check(_lib.load().sv_upsample2x_fwd(_p(x), _p(out), sv_dtype(x.dtype), B, H, W, Cc, _stream()), "sv_upsample2x_fwd")
     return out
 
 
-def upsample2x_bwd(g_hi, y_lo_mask=None):
+def upsample2x_bwd(g_hi, y_lo_mask=None, out=None):
     B, H2, W2, Cc = g_hi.shape
-    out = torch.empty((B, H2 // 2, W2 // 2, Cc), dtype=g_hi.dtype, device=g_hi.device)
+    if out is None:
+        out = torch.empty((B, H2 // 2, W2 // 2, Cc), dtype=g_hi.dtype, device=g_hi.device)
+    assert out.dtype == g_hi.dtype and out.numel() * 4 >= g_hi.numel()
     check(_lib.load().sv_upsample2x_bwd(_p(g_hi), _p(y_lo_mask), _p(out), sv_dtype(g_hi.dtype), B, H2 // 2, W2 // 2,
                                         Cc, _stream()), "sv_upsample2x_bwd")
     return out

@@ -169,8 +169,9 @@ def gumbel_uniforms(B, K, seed, step, sample_offset=0):
     return torch.from_numpy(philox_unit(seed, step, 7, np.uint64(sample_offset) + b, k))
 
 
-def head_eps(B, L, seed, step, sample_offset=0):
+def head_eps(B, L, seed, step, sample_offset=0, stream_id=0):
     """gm_head_fwd's draw: key = seed ^ 0xe9515eed, counter {j, gs, (gs >> 32) ^ 0x65707300, step}; eps = sqrt(-2 log u0) cos(2 pi u1), u0 / u1 from words 0 / 1.
+    stream_id: sv_reparam_kl_fwd draws the same way with 0x65707300 + stream_id in the third word (pointwise_ref.reparam_eps).
     The angle is formed as the kernel forms it -- float32(2 pi) times u1, rounded to float32 (that difference alone is 4e-7 rad, times |r| up to 5.8); log, sqrt
     and cos are float64.  -> float64 [B, L]"""
     gs = (np.uint64(sample_offset) + np.arange(B, dtype=np.uint64))[:, None] + np.zeros((1, L), dtype=np.uint64)
@@ -178,7 +179,7 @@ def head_eps(B, L, seed, step, sample_offset=0):
     ctr = np.zeros((B * L, 4), dtype=np.uint32)
     ctr[:, 0] = j.reshape(-1).astype(np.uint32)
     ctr[:, 1] = (gs.reshape(-1) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    ctr[:, 2] = (gs.reshape(-1) >> np.uint64(32)).astype(np.uint32) ^ np.uint32(0x65707300)
+    ctr[:, 2] = (gs.reshape(-1) >> np.uint64(32)).astype(np.uint32) ^ np.uint32((0x65707300 + stream_id) & 0xFFFFFFFF)
     ctr[:, 3] = np.uint32(step & 0xFFFFFFFF)
     w = philox4x32_10(ctr, (seed ^ 0xe9515eed) & 0xFFFFFFFFFFFFFFFF)
     u0, u1 = unit_open(w[:, 0]), unit_open(w[:, 1])

@@ -181,6 +181,9 @@ def test_kernel_entry_points_validate_arguments(lib_built):
     assert lib.sv_conv2d_wprep_elems(C.byref(d32), 0) == 16 * 42 * 32
     assert lib.sv_conv2d_wprep_elems(C.byref(d), 1) == 32 * 36 * 8        # dgrad contracts over Cout padded to 8
     assert lib.sv_dlogistic_nll_workspace_bytes(8, 64, 64) == 8 * 4 * 4
+    # the two-network loss launch and the loss finaliser: null arguments are refused before any launch (the rest: tests/test_pointwise_host.py)
+    assert lib.sv_dlogistic_nll_twin(None, None, 0, None, 0, None, 0, 0, 1.0, 1, 32, 32, None, 0, None) == _lib.STATUS_BADARG
+    assert lib.sv_finalize_losses(None, None, None, None, None, None, 0, 4, 40.0, None, None, 0, None) == _lib.STATUS_BADARG
 
 
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):

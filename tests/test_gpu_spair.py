@@ -348,4 +348,4 @@ def test_clipnorm_adam_over_separate_gradient_tensors(ops):
             ops.adam_step_clipnorm_tensors(p, grads, m, v, off, 1.0, 3, 1e-3)
         res.append((p, m, v))
     for a, b in zip(*res):
-        torch.testing.assert_close(a, b, rtol=1e-6, atol=1e-7)       # the norms' partial sums are taken in a different split
+        torch.testing.assert_close(a, b, rtol=1e-6, atol=1e-7)       # (both forms split a tensor's norm the same way: tests/test_gpu_pointwise.py holds them bit for bit)
