@@ -44,7 +44,8 @@ int sv_scramble_gather(const float* x, const int32_t* perm, float* images6,
                        int32_t B, int32_t H, int32_t W, int32_t patch, void* stream);
 /* The same, also writing the two zero-padded 8-channel NHWC tensors (x | x_aug, sv_dtype `dtype`) the first encoder layers of
  * sv_lgvae_step read -- pass the plan's in8_x / in8_xh buffers (sv_lgvae_buffer) and SV_PHASE_INPUTS_STAGED to the step: images6 is
- * read once less and the step's split / pad pass drops out (vae/main.py:57-61 + vae/model.py:190 in one kernel). */
+ * read once less and the step's split / pad pass drops out (vae/main.py:57-61 + vae/model.py:190 in one kernel).  x8 and xh8 are
+ * stored 16 bytes at a time: SV_E_BADARG for either not 16-byte aligned. */
 int sv_scramble_gather_staged(const float* x, const int32_t* perm, float* images6, void* x8, void* xh8, int32_t dtype, int32_t B,
                               int32_t H, int32_t W, int32_t patch, void* stream);
 /* tf.random.shuffle (augmentation.py:49) stand-in: one uniform permutation per image from a
@@ -59,9 +60,11 @@ int sv_random_perm(int32_t* perm, int32_t B, int32_t n_patch, uint64_t seed, uin
  * K = outer(v, v) / sum(outer(v, v)), v = Normal(mean, std).prob(-r..r), VALID -- run separably (row pass, column pass) in
  * fp32 with the taps formed in fp32, every sum in one fixed order (bit-reproducible).  SYMMETRIC mirrors including the edge
  * pixel (-1 -> 0, H -> H-1).  All filter entries: SV_E_BADARG for a null pointer or B, H, W <= 0 or a radius < 0;
- * SV_E_UNSUPPORTED for H != W, a radius > H or > 64, or (2r+1)*W*24 bytes above the 64 KiB of LDS a workgroup stages.
+ * SV_E_UNSUPPORTED for H != W, a radius > H or > 64, (2r+1)*W*24 bytes above the 64 KiB of LDS a workgroup stages, or
+ * B > 65535 (the image index is the grid's y dimension).
  * The _staged forms also write the plan's in8_x / in8_xh (channels 0-2 and 3-5, zero padded to 8, sv_dtype `dtype`):
- * the contract of sv_scramble_gather_staged, passed to the step as SV_PHASE_INPUTS_STAGED. */
+ * the contract of sv_scramble_gather_staged, passed to the step as SV_PHASE_INPUTS_STAGED.  x8 and xh8 are stored 16 bytes at
+ * a time: a pointer that is not 16-byte aligned is SV_E_BADARG (this holds for sv_scramble_gather_mixed_staged too). */
 /* gaussian_blur (augmentation.py:83-94): images6[B,H,W,6] = [x | blur(x)], radius[B] int32 and std[B] fp32 device arrays
  * (sv_blur_params draws them); a radius outside [0, max_radius] is clamped to it. */
 int sv_gauss_blur(const float* x, const int32_t* radius, const float* std, float* images6, int32_t B, int32_t H, int32_t W,

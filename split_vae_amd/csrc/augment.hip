@@ -17,6 +17,7 @@
 // (the contract of sv_scramble_gather_staged).
 constexpr int GAUSS_MAX_RADIUS = 64;
 constexpr int GAUSS_MAX_LDS = 64 * 1024;
+constexpr int GAUSS_MAX_BATCH = 65535;   // the image index is blockIdx.y
 
 __device__ __forceinline__ int sym_index(int i, int n) {   // valid for -n <= i < 2n
   return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i);
@@ -160,8 +161,12 @@ static int gauss_dispatch(const float* x, const int32_t* radius, const float* st
                    : gauss_launch<float, 9, true>(x, radius, stdv, fixed_r, mean, fixed_std, out, x8, xh8, B, H, W, rmax, s);
 }
 
+// the _staged kernels store x8 / xh8 as uint4
+static bool staged_aligned16(const void* x8, const void* xh8) { return (((uintptr_t)x8 | (uintptr_t)xh8) & 15) == 0; }
+
 static int gauss_check(int B, int H, int W, int r) {
   if (B <= 0 || H <= 0 || W <= 0 || r < 0) return SV_E_BADARG;
+  if (B > GAUSS_MAX_BATCH) return SV_E_UNSUPPORTED;
   if (H != W || r > H || r > GAUSS_MAX_RADIUS || gauss_band_rows(H, W, r) == 0) return SV_E_UNSUPPORTED;
   return SV_OK;
 }
@@ -178,6 +183,7 @@ extern "C" int sv_gauss_blur_staged(const float* x, const int32_t* radius, const
                                     int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t max_radius, void* stream) {
   if (!x || !radius || !stdv || !images6 || !x8 || !xh8) return SV_E_BADARG;
   if (dtype != SV_BF16 && dtype != SV_F32) return SV_E_BADARG;
+  if (!staged_aligned16(x8, xh8)) return SV_E_BADARG;
   const int rc = gauss_check(B, H, W, max_radius);
   if (rc) return rc;
   return gauss_dispatch(x, radius, stdv, 0, 0.f, 1.f, images6, 6, x8, xh8, dtype, true, B, H, W, max_radius, stream);
@@ -195,6 +201,7 @@ extern "C" int sv_high_low_pass_staged(const float* x, float* images9, void* x8,
                                        int32_t W, int32_t size, float mean, float std, void* stream) {
   if (!x || !images9 || !x8 || !xh8 || !(std > 0.f)) return SV_E_BADARG;
   if (dtype != SV_BF16 && dtype != SV_F32) return SV_E_BADARG;
+  if (!staged_aligned16(x8, xh8)) return SV_E_BADARG;
   const int rc = gauss_check(B, H, W, size);
   if (rc) return rc;
   return gauss_dispatch(x, nullptr, nullptr, size, mean, std, images9, 9, x8, xh8, dtype, true, B, H, W, size, stream);
@@ -385,6 +392,7 @@ extern "C" int sv_scramble_gather_mixed_staged(const float* x, const int32_t* pe
                                                void* x8, void* xh8, int32_t dtype, int32_t B, int32_t H, int32_t W, void* stream) {
   if (!x || !perm || !sizes || !images6 || !x8 || !xh8 || B <= 0 || H <= 0 || W <= 0 || ld <= 0) return SV_E_BADARG;
   if (dtype != SV_BF16 && dtype != SV_F32) return SV_E_BADARG;
+  if (!staged_aligned16(x8, xh8)) return SV_E_BADARG;
   if (H != W) return SV_E_UNSUPPORTED;
   if (dtype == SV_BF16) return mixed_launch<bf16_t, true>(x, perm, sizes, ld, images6, x8, xh8, B, H, W, stream);
   return mixed_launch<float, true>(x, perm, sizes, ld, images6, x8, xh8, B, H, W, stream);

@@ -71,6 +71,7 @@ extern "C" int sv_scramble_gather_staged(const float* x, const int32_t* perm, fl
                                          int32_t B, int32_t H, int32_t W, int32_t patch, void* stream) {
   if (!x || !perm || !images6 || !x8 || !xh8 || B <= 0 || H <= 0 || W <= 0 || patch <= 0) return SV_E_BADARG;
   if (dtype != SV_BF16 && dtype != SV_F32) return SV_E_BADARG;
+  if (((uintptr_t)x8 | (uintptr_t)xh8) & 15) return SV_E_BADARG;   // stored as uint4
   if (H != W || H % patch) return SV_E_UNSUPPORTED;
   const int64_t total = (int64_t)B * H * W;
   int grid = (int)((total + 255) / 256);

@@ -273,6 +273,8 @@ def test_pointwise_entry_points_refuse_before_launching(lib_built):
         assert lib.sv_upsample2x_bwd(a, None, a, dt, 1, 2, 2, c, None) == UNS
     assert lib.sv_upsample2x_fwd(a, a, 7, 1, 2, 2, 8, None) == BAD
     assert lib.sv_scramble_gather(a, a, a, 1, 8, 8, 3, None) == UNS and lib.sv_scramble_gather(a, a, a, 1, 8, 4, 2, None) == UNS
+    for dt in (_lib.SV_F32, _lib.SV_BF16):                          # x8 / xh8 are stored as uint4: a pointer off the 16-byte boundary is refused
+        assert lib.sv_scramble_gather_staged(a, a, a, a + 4, a, dt, 1, 8, 8, 4, None) == BAD and lib.sv_scramble_gather_staged(a, a, a, a, a + 8, dt, 1, 8, 8, 4, None) == BAD
     assert lib.sv_dlogistic_nll(a, 1, a, a, None, 0, 1.0, 1, 8, 8, a, None) == BAD
     # sv_dlogistic_nll_twin(images6, out6, zs_out, nll, zs_nll, grad, zs_grad, grad_dtype, grad_scale, B, H, W, partial_ws, zs_part, stream)
     ok = dict(images6=a, out6=a, zs_out=2 * 64 * 6, nll=a, zs_nll=2, grad=a, zs_grad=2 * 64 * 8, dt=_lib.SV_F32, B=2, H=8, W=8, ws=a, zs_part=2)
