@@ -697,6 +697,12 @@ int sv_lgvae_bucket_wait(sv_lgvae_plan* plan, int32_t bucket, void* stream);
  *   "bucket_skip_side" = 1 sv_lgvae_bucket_wait drops the side streams' events (the negative control of the dependency test).
  * SV_E_BADARG: unknown key / value out of range. */
 int sv_lgvae_plan_debug(sv_lgvae_plan* plan, const char* key, int64_t value);
+/* Test hook, no plan and no device call (tests/test_plan_state_host.py): the host state machine that tracks where dL/dz of the decoders lives between the phases
+ * of a step (csrc/plan_latent.h).  state: 0 zeroed, 1 stale (the encoders' forward skipped the zero fill: nothing accumulates), 2 summed in gz_*, 3 unsummed
+ * K-slice slabs in lat_ws_*.  event: 0 encoders' forward (slab_path: both split-K launches of the plan run on latent_gemm.hip), 1 decoders' backward that leaves
+ * the slabs, 2 decoders' backward with dL/dz in gz_* (slab_path: summed from slabs; 0: accumulated), 3 encoder heads' backward.  *next: the state after the event;
+ * *zero_range: what the phase zeroes first -- 0 nothing, 1 gz_x .., 2 pre_x .. gz_xh.  SV_E_BADARG: state / event outside 0 .. 3 or a null result. */
+int sv_lgvae_dz_transition(int32_t state, int32_t event, int32_t slab_path, int32_t* next, int32_t* zero_range);
 /* The library's side streams: hipStream_t `index` (0 .. 2) of the CURRENT device, created once per process and shared by every plan (weight-gradient
  * streams), tape (lanes) and by the SPLIT-GMVAE step's second encoder stream -- a stream per object put a later object's stream on the hardware queue of the
  * compute stream it should run beside (csrc/streams.hip).  A host binding that wants a library-compatible side stream of its own takes it from here.

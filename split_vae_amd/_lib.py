@@ -274,6 +274,7 @@ SYMBOLS = {
     "sv_lgvae_graph_enable": (C.c_int, [_vp, _i32]),
     "sv_lgvae_bucket_wait": (C.c_int, [_vp, _i32, _vp]),
     "sv_lgvae_plan_debug": (C.c_int, [_vp, C.c_char_p, _i64]),
+    "sv_lgvae_dz_transition": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "sv_side_stream": (C.c_int, [_i32, _vp]),
     "sv_lgvae_graph_count": (C.c_int, [_vp]),
     "sv_lgvae_profile_enable": (C.c_int, [_vp, _i32]),

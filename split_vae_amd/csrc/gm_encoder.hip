@@ -301,8 +301,7 @@ extern "C" int sv_gm_encoder_backward(sv_gm_encoder* e, const sv_gm_args* a, voi
   auto wg = [&](int l, const void* x, const void* dy) -> int {
     void* wst = stream;
     if (ws2) {
-      if (!e->ev_dy[l] && hipEventCreateWithFlags(&e->ev_dy[l], hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
-      if (hipEventRecord(e->ev_dy[l], st) != hipSuccess || hipStreamWaitEvent(ws2, e->ev_dy[l], 0) != hipSuccess) return (int)hipGetLastError();
+      if (!sv_event_handoff(&e->ev_dy[l], st, ws2)) return (int)hipGetLastError();
       wst = (void*)ws2;
       forked = true;
     }
@@ -345,10 +344,7 @@ extern "C" int sv_gm_encoder_backward(sv_gm_encoder* e, const sv_gm_args* a, voi
   SV_TRY(dg(C2, e->bp(B_g_c2), B_g_h1d));
   SV_TRY(act_bwd(B_g_h1d, dt, 128, -1, B_h1, 0.f, nullptr, B_g_c1, (int64_t)B * (H / 2) * (H / 2), 128));
   SV_TRY(wg(C1, a->in8_x, e->bp(B_g_c1)));
-  if (forked) {
-    if (!e->ev_wjoin && hipEventCreateWithFlags(&e->ev_wjoin, hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
-    if (hipEventRecord(e->ev_wjoin, ws2) != hipSuccess || hipStreamWaitEvent(st, e->ev_wjoin, 0) != hipSuccess) return (int)hipGetLastError();
-  }
+  if (forked && !sv_event_handoff(&e->ev_wjoin, ws2, st)) return (int)hipGetLastError();
   return SV_OK;
 }
 

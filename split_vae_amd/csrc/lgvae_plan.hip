@@ -17,15 +17,11 @@
 #include "kernels.h"
 #include "conv_geom.h"
 #include "buffer_table.h"
+#include "plan_streams.h"
+#include "plan_profile.h"
+#include "plan_latent.h"
 
 namespace {
-
-// test hook only (sv_lgvae_plan_debug "side_delay_us"): holds a stream back for a while
-__global__ void sv_plan_spin_kernel(long long ticks) {
-  const long long t0 = wall_clock64();
-  while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
-}
-static void sv_plan_spin(hipStream_t st, int us) { hipLaunchKernelGGL(sv_plan_spin_kernel, dim3(1), dim3(64), 0, st, (long long)us * 100); }   // wall_clock64: 100 MHz
 
 // THE workspace buffer list: id, public name (sv_lgvae_buffer) and position in the workspace, in this order.  ONE: a single buffer.  TWIN: one kind per
 // network -- id = the x network's buffer `<name>x`, id + 1 = the x-hat network's `<name>xh` right behind it (exactly `bytes` behind when the size is a multiple of
@@ -124,9 +120,6 @@ static int check_desc(const sv_lgvae_desc* d) {
   return SV_OK;
 }
 
-struct ProfEntry { std::string name; double flops, bytes, total_ms; int launches; double issued; };   // issued: see issued_flops() below
-struct ProfPending { int entry; hipEvent_t a, b; };
-
 // one conv-like layer instance with everything needed for fwd / dgrad / wgrad
 struct Layer {
   std::string ln, sc_fwd, sc_dgrad, sc_wgrad, sc_reduce;   // "d4" and its profile scopes "fwd.d4", "dgrad.d4", "wgrad.d4", "wgrad.d4.reduce" (build_layers)
@@ -159,160 +152,22 @@ struct sv_lgvae_plan {
   int dec_block0 = 0;           // first block of the decoders' jobs in the table (the encoders' jobs come first): the step prepares the two halves on two streams
   int64_t arena_elems;
   bool nll_fused = false;  // the last decoder forward evaluated the loss in the head's epilogue (nllpart_*, g5_* are valid)
-  bool gz_clean = false;   // dz accumulators zeroed by the last encoder-forward phase and not yet used
-  // the K-slice slabs of d1's input gradient are still unsummed in lat_ws_x / lat_ws_xh: reparam_kl_bwd sums them itself (one launch less)
-  bool dz_slabs = false;
-  bool dz_valid = false;        // the decoders' backward has run since the last encoder forward (dz is what reparam_kl_bwd may read)
-  bool gz_zero_skipped = false; // that forward did not zero dz (slab path): an encoder backward WITHOUT the decoders' (KL terms only) zeroes it first
+  LatentBlock lat;              // where dL/dz lives (DzState), the latched launch forms and the K-slice geometry: plan_latent.h
   unsigned polycw_bad = 0;      // decoder layers (bit = Layer::polycw) whose polyphase weight gradient was refused once: not tried again (one profile scope per launch)
-  bool lat_head_ok = false, lat_d1_ok = false;     // the heads' forward / d1's input gradient of this plan run on latent_gemm.hip (shapes are fixed per plan)
-  int dz_S[2] = {0, 0};
-  int64_t dz_stride[2] = {0, 0};
-  // weight gradients on a second stream (they feed only Adam / the all-reduce; the input-gradient chain is the critical
-  // path): fork = the side stream waits for the event recorded on the main stream when dY is ready, join before Adam and
-  // at the end of every sv_lgvae_step call
-  enum { SIDE_MAX = 4 };
-  hipStream_t side[SIDE_MAX] = {nullptr, nullptr, nullptr, nullptr};   // SV_SIDE_STREAMS of them, taken round-robin: the weight
-  hipEvent_t ev_fork = nullptr, ev_join[SIDE_MAX] = {nullptr, nullptr, nullptr, nullptr};   // gradients of different layers are independent
-  int side_use = 1;        // streams the current call hands layers to (run_phases)
-  int side_count = 0;      // layers forked since the last join
-  int nside = 0, side_next = 0, side_slot = 0;   // side_slot: which stream (and which slab workspace) the last wgrad_stream() gave out
-  bool side_pending = false;
-  // EARLY SIDE WORK (round 6): what the step's first launches do not need runs on side stream 0 beside them -- the decoders' weight images (the encoders' forward
-  // reads only its own) and the zero fill of the gradient buffer (first written by the backward).  Both are HBM-bound, the encoder convs beside them matrix-bound;
-  // batch-independent time off the critical path of every shard size.  ev_early is waited for before the decoders' forward / the backward / the end of the call.
-  hipEvent_t ev_early = nullptr;
-  bool early_pending = false;
-  // captured steps: SV_GRAPH_SIDE=1 lets the capture fork to the side streams too (every fork / join on its OWN event and only the streams a call really used are
-  // joined: round 3's capture, which re-recorded one fork event and joined every stream, replayed wrongly on ROCm 7.2).  Off by default: see DESIGN.md section 7.
-  static bool graph_side() { return sv_knob_graph_side(); }
-  bool side_allowed() const {
-    static const bool off = SV_TUNE_FLAG("SV_NO_SIDE");
-    return !(off || (prof_on && prof_filter.empty()) || ((graph_on || dyn) && !graph_side()));
-  }
-  // fork / join events: one per use while graph replay is on (a captured event node per dependency), the two fixed ones otherwise
-  enum { CAP_EV = 96 };
-  hipEvent_t ev_cap[CAP_EV] = {};
-  int n_cap = 0;
-  bool side_used[SIDE_MAX] = {false, false, false, false};
-  hipEvent_t fresh_event(hipEvent_t fixed) {
-    if (!(graph_on || dyn) || n_cap >= CAP_EV) return fixed;
-    if (!ev_cap[n_cap] && hipEventCreateWithFlags(&ev_cap[n_cap], hipEventDisableTiming) != hipSuccess) return fixed;
-    return ev_cap[n_cap++];
-  }
-  hipStream_t early_stream(hipStream_t st) {          // side stream 0, ordered behind everything `st` holds now; nullptr: no side streams (serial modes)
-    // OPT-IN (SV_EARLY_SIDE=1).  Measured (profiles/r06_ab.txt): the step is no shorter for it at any shard size -- fp32 512 images 9.152 against 9.138 ms without,
-    // 64 images 1.690 / 1.689, bf16 512 images 1.661 / 1.646: the encoders' first layers are HBM-bound themselves (e1 reads the whole batch), the weight images' 165 MB
-    // beside them slow them by what the overlap saves (fwd.e1 25 -> 52 us at 64 images).  Same finding as round 3's early optimizer tail: no idle resource to hide it in.
-    const bool on = sv_knob_early_side();
-    if (!on || !side_allowed() || !ensure_side()) return nullptr;
-    if (!ev_early && hipEventCreateWithFlags(&ev_early, hipEventDisableTiming) != hipSuccess) return nullptr;
-    hipEvent_t ef = fresh_event(ev_fork);
-    if (hipEventRecord(ef, st) != hipSuccess || hipStreamWaitEvent(side[0], ef, 0) != hipSuccess) return nullptr;
-    side_used[0] = true;
-    return side[0];
-  }
-  hipEvent_t ev_early_now = nullptr;
-  int early_done(hipStream_t side0) {                 // the early work is enqueued: mark it
-    ev_early_now = fresh_event(ev_early);
-    if (hipEventRecord(ev_early_now, side0) != hipSuccess) return (int)hipGetLastError();
-    early_pending = true;
-    return SV_OK;
-  }
-  int early_wait(hipStream_t st) {
-    if (!early_pending) return SV_OK;
-    early_pending = false;
-    return hipStreamWaitEvent(st, ev_early_now, 0) == hipSuccess ? SV_OK : (int)hipGetLastError();
-  }
-  bool ensure_side() {
-    if (nside) return true;
-    {
-      // (priority: streams.hip creates the shared streams at the lowest priority; SV_SIDE_PRIO_NORMAL is read there)
-      const int want = sv_knob_side_streams(2);      // taken; `side_use` of them are used per call
-      const int k = want < 1 ? 1 : want > SIDE_MAX - 1 ? SIDE_MAX - 1 : want;   // the last workspace slot belongs to the main stream
-      if (!ev_fork && hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess) return false;
-      for (int i = 0; i < k && i < SV_SHARED_STREAMS; ++i) {
-        side[i] = sv_shared_stream(i);               // the process's shared side streams (streams.hip): never a stream per plan
-        if (!side[i]) break;
-        (void)hipEventCreateWithFlags(&ev_join[i], hipEventDisableTiming);
-        ++nside;
-      }
-    }
-    return nside > 0;
-  }
-  hipStream_t wgrad_stream(hipStream_t st) {
-    side_slot = 0;
-    if (!side_allowed()) return st;     // the full per-kernel table wants serial launches; a captured fork/join replayed wrongly on ROCm 7.2 (corrupt gradients, then a crash): captures stay single-stream
-    if (!ensure_side()) return st;
-    const int use = side_use < nside ? side_use : nside;
-    static const char* order = SV_TUNE_STR("SV_SIDE_ORDER", nullptr);        // experiment: stream per forked layer in launch order, e.g. "0110" (repeats)
-    int slot = side_next % use;
-    if (order && order[0]) { const int c = order[side_count % (int)strlen(order)] - '0'; if (c >= 0 && c < use) slot = c; }
-    ++side_count;
-    hipEvent_t ef = fresh_event(ev_fork);
-    if (hipEventRecord(ef, st) != hipSuccess || hipStreamWaitEvent(side[slot], ef, 0) != hipSuccess) return st;
-    side_used[slot] = true;
-    // test hook (sv_lgvae_plan_debug "side_delay_us", tests/test_gpu_dist.py): hold the side stream back at its first use of a step, so that a consumer
-    // of the gradients that does not wait for the side stream's part (a missing bucket dependency) reads them before they exist
-    if (dbg_side_delay_us > 0 && side_count == 1) sv_plan_spin(side[slot], dbg_side_delay_us);
-    side_next = slot + 1;
-    side_slot = slot;
-    side_pending = true;
-    return side[slot];
-  }
-  int join_side(hipStream_t st) {
-    const bool cap = graph_on || dyn;
-    if (!side_pending && !(cap && side_used[0])) return SV_OK;        // (a captured call joins the early work's stream too: every forked stream must rejoin the capture)
-    side_pending = false;
-    side_next = 0;                     // every step hands the layers to the same streams
-    side_count = 0;
-    for (int i = 0; i < nside; ++i) {
-      if (cap && !side_used[i]) continue;                              // (an event of a stream outside the capture must not be waited for inside it)
-      hipEvent_t ej = fresh_event(ev_join[i]);
-      if (hipEventRecord(ej, side[i]) != hipSuccess || hipStreamWaitEvent(st, ej, 0) != hipSuccess) return (int)hipGetLastError();
-    }
-    return SV_OK;
-  }
-  // per-plan test hooks (sv_lgvae_plan_debug): never read from the environment, so nothing a job inherits can switch them on
-  int dbg_side_delay_us = 0;
-  bool dbg_bucket_skip_side = false;
-  // gradient-bucket events (SV_PHASE_BUCKET_EVENTS): [bucket][0 = compute stream, 1 + i = side stream i]
-  hipEvent_t ev_bucket[3][1 + SIDE_MAX] = {};
-  bool bucket_rec[3][1 + SIDE_MAX] = {};
-  void clear_buckets() {
-    for (auto& row : bucket_rec)
-      for (auto& b : row) b = false;
-  }
-  int record_bucket(int k, hipStream_t st) {
-    for (int i = 0; i <= SIDE_MAX; ++i) bucket_rec[k][i] = false;
-    for (int i = 0; i <= nside; ++i) {                    // every stream that may hold work of this bucket, in its own order
-      hipStream_t s = i == 0 ? st : side[i - 1];
-      if (i > 0 && !s) continue;
-      if (!ev_bucket[k][i] && hipEventCreateWithFlags(&ev_bucket[k][i], hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
-      if (hipEventRecord(ev_bucket[k][i], s) != hipSuccess) return (int)hipGetLastError();
-      bucket_rec[k][i] = true;
-    }
-    return SV_OK;
-  }
+  SideStreams side;             // weight-gradient / early side streams, their fork / join / bucket events and test hooks: plan_streams.h
+  Profiler prof;                // per-scope hipEvent timing: plan_profile.h
   // captured steps (sv_lgvae_graph_enable): one executable graph per distinct (phase mask, buffers, baked scalars)
   bool graph_on = false;
   const SvDynArgs* dyn = nullptr;   // non-null while a step is being captured
-  // host-side flags that a phase reads on entry and leaves behind on exit: they select launches (which buffer reparam_kl_bwd reads, whether dz is
-  // re-zeroed, whether the ELBO gradient comes from the fused head), so they are part of a captured graph's key and a replay must leave the
+  // host-side state that a phase reads on entry and leaves behind on exit: it selects launches (which buffer reparam_kl_bwd reads, whether dz is
+  // re-zeroed, whether the ELBO gradient comes from the fused head), so it is part of a captured graph's key and a replay must leave the
   // plan in the state the captured phases left it in
-  struct HostState { bool gz_clean, dz_slabs, dz_valid, gz_zero_skipped, nll_fused; };
-  HostState host_state() const { return {gz_clean, dz_slabs, dz_valid, gz_zero_skipped, nll_fused}; }
-  void set_host_state(const HostState& h) { gz_clean = h.gz_clean; dz_slabs = h.dz_slabs; dz_valid = h.dz_valid; gz_zero_skipped = h.gz_zero_skipped; nll_fused = h.nll_fused; }
-  uint64_t host_state_bits() const { return (uint64_t)gz_clean | (uint64_t)dz_slabs << 1 | (uint64_t)dz_valid << 2 | (uint64_t)gz_zero_skipped << 3 | (uint64_t)nll_fused << 4; }
+  struct HostState { DzState dz; bool nll_fused; };
+  HostState host_state() const { return {lat.dz, nll_fused}; }
+  void set_host_state(const HostState& h) { lat.dz = h.dz; nll_fused = h.nll_fused; }
+  uint64_t host_state_bits() const { return (uint64_t)lat.dz | (uint64_t)nll_fused << 2; }
   struct GraphEntry { hipGraphExec_t exec = nullptr; int seen = 0; HostState exit_state{}; };
   std::map<std::vector<uint64_t>, GraphEntry> graphs;
-  // profiling
-  bool prof_on;
-  std::string prof_filter;
-  std::vector<ProfEntry> prof;
-  std::map<std::string, int> profidx;
-  std::vector<ProfPending> pending;
-  std::vector<hipEvent_t> event_pool;
 
   size_t esz() const { return d.dtype == SV_BF16 ? 2 : 4; }
   int ndec() const { return d.global_only ? 1 : 2; }                       // decoders (and x / x-hat networks) the plan runs
@@ -328,74 +183,6 @@ namespace {
 
 // A/B: one launch per network for the small pointwise kernels (Sampling + KL and their adjoints) instead of one for the x / x-hat twins
 static bool no_twin_pointwise() { static const bool v = SV_TUNE_FLAG("SV_NO_TWIN_POINTWISE"); return v; }
-
-// SV_ROCTX=1: every plan scope ("fwd.d4", "wgrad.d4", "adam_step" ...) is also a roctx range, so a `rocprofv3 --marker-trace
-// --kernel-trace` timeline names the layers directly.  libroctx64 is bound at run time (no link dependency); off by default.
-#include <dlfcn.h>
-struct Roctx {
-  int (*push)(const char*) = nullptr;
-  int (*pop)() = nullptr;
-  Roctx() {
-    if (!sv_knob_roctx()) return;
-    void* h = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) h = dlopen("/opt/rocm/lib/libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) return;
-    push = (int (*)(const char*))dlsym(h, "roctxRangePushA");
-    pop = (int (*)())dlsym(h, "roctxRangePop");
-    if (!push || !pop) push = nullptr, pop = nullptr;
-  }
-};
-static const Roctx& roctx() { static const Roctx r; return r; }
-
-struct Scope {   // hipEvent bracket around one launch when profiling is on
-  sv_lgvae_plan* p; hipStream_t st; int entry = -1, entry2 = -1; hipEvent_t a = nullptr, b = nullptr, m1 = nullptr, m2 = nullptr;
-  bool on, on2 = false;
-  hipEvent_t get() {
-    hipEvent_t e;
-    if (!p->event_pool.empty()) { e = p->event_pool.back(); p->event_pool.pop_back(); }
-    else (void)hipEventCreate(&e);
-    return e;
-  }
-  int find(const char* name, double flops, double bytes) {
-    auto it = p->profidx.find(name);
-    if (it != p->profidx.end()) return it->second;
-    const int e = (int)p->prof.size();
-    p->profidx[name] = e;
-    p->prof.push_back(ProfEntry{name, flops, bytes, 0.0, 0, flops});
-    return e;
-  }
-  bool marked = false;
-  void issued(double fl) { if (entry >= 0) p->prof[entry].issued = fl; }      // the launch set runs a strength-reduced form: FLOPs it really multiplies
-  Scope(sv_lgvae_plan* p_, hipStream_t st_, const std::string& name, double flops, double bytes) : Scope(p_, st_, name.c_str(), flops, bytes) {}
-  Scope(sv_lgvae_plan* p_, hipStream_t st_, const char* name, double flops, double bytes) : p(p_), st(st_), on(p_->prof_on) {   // (a literal or a Layer's name: no string is built unless profiling books one)
-    if (roctx().push) { roctx().push(name); marked = true; }
-    if (on && !p->prof_filter.empty() && p->prof_filter != name) on = false;
-    if (!on) return;
-    entry = find(name, flops, bytes);
-    a = get(); b = get();
-    (void)hipEventRecord(a, st);
-  }
-  // a launch with a second stage (wgrad tile kernel -> slab reduce): the callee records ev[0], ev[1] between
-  // the two, and the second stage is booked under its own name
-  void split(const std::string& name2, double bytes2, hipEvent_t ev[2]) {
-    ev[0] = ev[1] = nullptr;
-    if (!p->prof_on) return;
-    on2 = p->prof_filter.empty() || p->prof_filter == name2;
-    if (!on && !on2) return;
-    if (on2) entry2 = find(name2.c_str(), 0, bytes2);
-    m1 = ev[0] = get(); m2 = ev[1] = get();
-    if (!b) b = get();
-  }
-  ~Scope() {
-    if (marked) roctx().pop();
-    if (!b) return;
-    (void)hipEventRecord(b, st);
-    if (!m1) { p->pending.push_back(ProfPending{entry, a, b}); return; }
-    if (on) p->pending.push_back(ProfPending{entry, a, m1}); else p->event_pool.push_back(m1);
-    if (on2) p->pending.push_back(ProfPending{entry2, m2, b});
-    else { p->event_pool.push_back(m2); p->event_pool.push_back(b); }
-  }
-};
 
 static void build_layers(sv_lgvae_plan* p) {
   const sv_lgvae_desc& d = p->d;
@@ -512,7 +299,7 @@ static void build_buffers(sv_lgvae_plan* p) {
   auto same = [&](int id, int64_t bytes) { twin(id, bytes, bytes); };
   sz[JOBS] = (int64_t)p->jobs.size() * sizeof(PrepJob);
   sz[WARENA] = p->arena_elems * es;
-  sz[WGRAD_WS] = SV_WGRAD_WS_BYTES * SV_WGRAD_MAX_MULTI * sv_lgvae_plan::SIDE_MAX;   // per side stream, per problem
+  sz[WGRAD_WS] = SV_WGRAD_WS_BYTES * SV_WGRAD_MAX_MULTI * SideStreams::SIDE_MAX;   // per side stream, per problem
   same(POLYFIX, svk_poly_fix_ws_bytes((int)B, (int)H / 2, (int)W / 2));   // border terms of the polyphase head (poly_fix.hip)
   {   // border terms of the per-class polyphase layers (d3, d4): one region per network, sized for the largest layer (the layers run one after the other)
     int64_t need = 256;
@@ -534,14 +321,19 @@ static void build_buffers(sv_lgvae_plan* p) {
     const int64_t Fd = (H / 8) * (W / 8) * 128;
     // the four launches that write them -- heads of x / x-hat (N = 2 Lg / 2 Ll), d1's input gradient of decoder_x / decoder_x-hat (N = Lg + Ll / Ll) --
     // pick their split PER PROBLEM: sized as the maximum of the four actual (split, N) products (with unequal latent sizes a
-    // per-problem split x N could exceed a product formed from two of them); the launch sites check the capacity again and fall back
+    // per-problem split x N could exceed a product formed from two of them).  The splits and slab strides are FIXED here: the launch sites and
+    // Sampling + KL read p->lat, so what is launched is what was sized
+    LatentBlock& lat = p->lat;
     int64_t need = 0;
-    for (const int64_t Nq : {2 * Lg, 2 * Ll, Lg + Ll, Ll}) {
-      if (go) break;
-      const int64_t b = (int64_t)svk_nt_gemm_pick_splitk((int)B, (int)Nq, (int)Fd, 2) * B * Nq * 4;
-      need = b > need ? b : need;
+    auto slabs = [&](int64_t Nq, int* S, int64_t* stride) {
+      *S = svk_nt_gemm_pick_splitk((int)B, (int)Nq, (int)Fd, 2);
+      *stride = B * Nq;
+      need = std::max<int64_t>(need, *S * *stride * 4);
+    };
+    for (int k = 0; k < p->ndec(); ++k) {
+      if (!go) slabs(2 * (k == 0 ? Lg : Ll), &lat.head_S[k], &lat.head_stride[k]);     // (GMVae: d1's input gradient only, N = Lg)
+      slabs(k == 0 ? Lc : Ll, &lat.d1_S[k], &lat.d1_stride[k]);
     }
-    if (go) need = (int64_t)svk_nt_gemm_pick_splitk((int)B, Lc, (int)Fd, 2) * B * Lc * 4;    // d1's input gradient only (N = Lg)
     same(LAT_WS, need);
   }
   sz[DYN] = sizeof(SvDynArgs);
@@ -634,6 +426,62 @@ static double conv_bytes(const sv_conv_desc& d, int kind, size_t es) {
     if (rc__) return rc__;   \
   } while (0)
 
+// ---- the latent block on latent_gemm.hip: one builder per problem kind, one launch ladder; the im2col fall-backs stay with the callers
+// out [M][ldo] = act(A [M][lda] . W^T + bias) gated by mask, W = the prepared image [N][ldw] at element w_off of the arena;
+// S > 0: the K slices' fp32 slabs [S][M][ldo] instead (no bias / act / mask: their consumer applies them)
+static NtGemmProb nt_prob(const sv_lgvae_plan* p, const void* A, int lda, int64_t w_off, int ldw, void* out, int ldo, int M, int N, int K,
+                          const float* bias = nullptr, int act = SV_ACT_NONE, const void* mask = nullptr, int S = 0) {
+  NtGemmProb g;
+  memset(&g, 0, sizeof(g));
+  g.f32 = p->d.dtype == SV_F32;
+  g.A = A; g.lda = lda;
+  g.W = (char*)p->buf(WARENA) + w_off * p->esz(); g.ldw = ldw;
+  g.out = out; g.ldo = ldo;
+  g.bias = bias; g.act = act; g.mask = mask;
+  g.M = M; g.N = N; g.K = K;
+  g.splitk = S > 0 ? S : 1; g.out_f32 = S > 0; g.slab_stride = S > 0 ? (int64_t)M * ldo : 0;
+  return g;
+}
+static TnWgradProb tn_prob(const sv_lgvae_plan* p, const void* X, int ldx, const void* dY, int ldy, float* dW, float* dbias, int M, int Kw, int Kw_real, int N) {
+  return TnWgradProb{X, ldx, dY, ldy, dW, dbias, M, Kw, Kw_real, N, p->d.dtype == SV_F32};
+}
+enum LatentRan { LAT_NOT_TAKEN, LAT_RAN, LAT_SLABS_LEFT };
+// n <= 2 problems as one launch under the scope `name`.  LAT_NOT_TAKEN: nothing was launched and no scope booked (latent_gemm.hip is switched off or has no
+// form for a problem): the caller's fall-back runs.  Slab problems are summed into sum_to[] right behind the launch (same scope), or with keep_slabs left
+// unsummed for their consumer: LAT_SLABS_LEFT.
+static int run_latent_nt(sv_lgvae_plan* p, const char* name, double fl, double by, NtGemmProb* q, int n, int bm, float* const* sum_to, bool keep_slabs,
+                         hipStream_t st, LatentRan* ran) {
+  *ran = LAT_NOT_TAKEN;
+  if (!latent_gemm_on(p)) return SV_OK;
+  for (int i = 0; i < n; ++i)
+    if (!svk_nt_gemm_supported(q[i])) return SV_OK;
+  Scope sc(p->prof, st, name, fl, by);
+  const int rc = svk_nt_gemm_multi(q, n, bm, st);
+  if (rc == SV_E_UNSUPPORTED) return SV_OK;
+  if (rc) return rc;
+  *ran = LAT_RAN;
+  if (!q[0].out_f32) return SV_OK;
+  if (!keep_slabs) return svk_nt_slab_reduce(q, sum_to, n, st);
+  *ran = LAT_SLABS_LEFT;
+  return SV_OK;
+}
+// the weight-gradient tile kernel: n <= 4 problems, whole batch per tile
+static int run_latent_tn(sv_lgvae_plan* p, const char* name, double fl, double by, const TnWgradProb* q, int n, hipStream_t st, bool* taken) {
+  *taken = false;
+  if (!latent_gemm_on(p) || n > 4) return SV_OK;
+  for (int i = 0; i < n; ++i)
+    if (!svk_tn_wgrad_supported(q[i])) return SV_OK;
+  Scope sc(p->prof, st, name, fl, by);
+  *taken = true;
+  return svk_tn_wgrad_multi(q, n, st);
+}
+// the memset a dz transition asks for (plan_latent.h).  GMVae has neither head pre-activations nor an x-hat network: its whole range is gz_x
+static int zero_dz(sv_lgvae_plan* p, DzZero z, hipStream_t st) {
+  if (z == DzZero::None) return SV_OK;
+  if (z == DzZero::PreGz && !p->d.global_only) return p->bufs.zero(PRE, GZ_XH, st);
+  return p->bufs.zero(GZ, GZ + p->ndec() - 1, st);
+}
+
 // The x and x-hat networks have twin layers of identical geometry: n of them go out as ONE launch
 // (blockIdx.z picks the problem), which halves the per-launch fixed cost that dominates at B<=512.
 struct FusedNll { const float* images6; void* grad[2]; float* part[2]; float gscale; int noout; };   // loss in the head's epilogue (tile_conv.hip)
@@ -654,23 +502,17 @@ static int run_fwd_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void* 
     fl += conv_flops(L[i]->d);
     by += conv_bytes(L[i]->d, 0, p->esz());
   }
-  Scope sc(p, st, L[0]->sc_fwd, fl, by);
-  if (latent_gemm_on(p) && !nll && L[0]->d.H == 1 && L[0]->d.W == 1 && L[0]->d.KH == 1 && !L[0]->d.y_f32) {   // Dense (d1): latent_gemm.hip
+  if (!nll && L[0]->d.H == 1 && L[0]->d.W == 1 && L[0]->d.KH == 1 && !L[0]->d.y_f32) {   // Dense (d1): latent_gemm.hip
     NtGemmProb q[2];
     for (int i = 0; i < n; ++i) {
       const sv_conv_desc& d = L[i]->d;
-      NtGemmProb& g = q[i];
-      memset(&g, 0, sizeof(g));
-        g.f32 = p->d.dtype == SV_F32;
-      g.A = x[i]; g.lda = d.ldx;
-      g.W = a[i].Wt; g.ldw = svg_cin_pad(&d);
-      g.out = y[i]; g.ldo = d.ldy;
-      g.bias = a[i].bias; g.act = d.act;
-      g.M = d.B; g.N = d.Cout; g.K = d.Cin; g.splitk = 1;
+      q[i] = nt_prob(p, x[i], d.ldx, L[i]->wf_off, svg_cin_pad(&d), y[i], d.ldy, d.B, d.Cout, d.Cin, a[i].bias, d.act);
     }
-    const int rc = svk_nt_gemm_multi(q, n, L[0]->d.B >= 256 ? 128 : 64, st);
-    if (rc != SV_E_UNSUPPORTED) return rc;
+    LatentRan ran;
+    SV_TRY(run_latent_nt(p, L[0]->sc_fwd.c_str(), fl, by, q, n, L[0]->d.B >= 256 ? 128 : 64, nullptr, false, st, &ran));
+    if (ran != LAT_NOT_TAKEN) return SV_OK;
   }
+  Scope sc(p->prof, st, L[0]->sc_fwd, fl, by);
   if (L[0]->polyc && !nll && n <= 2) {
     { double is = 0; for (int i = 0; i < n; ++i) is += poly_issued(L[i]->d, L[i]->d.KH == 6 ? 81 : 49, false); sc.issued(is); }
     // per-class polyphase (d4, d3): border kernel, then the four class problems of both networks in one launch
@@ -711,7 +553,7 @@ static int run_dgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
       fl += conv_flops(L[i]->d);
     }
     if (ok) {
-      Scope sc(p, st, L[0]->sc_dgrad, fl, by);
+      Scope sc(p->prof, st, L[0]->sc_dgrad, fl, by);
       const int rc = svk_conv_dispatch_multi(a, n, L[0]->d.dtype, svg_pick_cfg(a[0].N), st);
       if (rc != SV_E_UNSUPPORTED) return rc;
     }
@@ -740,7 +582,7 @@ static int run_dgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
   if (adj) {                            // no fused kernel for this geometry: nothing was launched, the caller falls back
     if (!svk_row_conv_supported(a, m, L[0]->d.dtype)) return SV_E_UNSUPPORTED;
   }
-  Scope sc(p, st, L[0]->sc_dgrad, fl, by);
+  Scope sc(p->prof, st, L[0]->sc_dgrad, fl, by);
   if (mixed) {   // split-K problems whose widths pick different tiles: one launch each
     for (int i = 0; i < m; ++i) {
       int c2 = svg_pick_cfg(L[0]->d.Cin);
@@ -758,7 +600,7 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
   WgradArgs a[SV_WGRAD_MAX_MULTI];
   double fl = 0, by = 0;
   for (int i = 0; i < n; ++i) by += conv_bytes(L[i]->d, 2, p->esz());
-  const int64_t wsb = p->bbytes(WGRAD_WS) / (SV_WGRAD_MAX_MULTI * sv_lgvae_plan::SIDE_MAX);   // one partial-sum slab region per stream and problem
+  const int64_t wsb = p->bbytes(WGRAD_WS) / (SV_WGRAD_MAX_MULTI * SideStreams::SIDE_MAX);   // one partial-sum slab region per stream and problem
   const std::string &ln = L[0]->ln, &nm = L[0]->sc_wgrad;
   // layers named in SV_WGRAD_MAIN keep their weight gradient on the main stream.  Measured (B = 512, 64x64): the side stream is
   // the critical path of the backward pass (it ends ~0.3 ms after the last input gradient), and d5's weight gradient slows the
@@ -781,25 +623,21 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
   // (two side streams, re-measured with round 4's kernels: "e1" 1.643-1.647 ms, "e1,e2" 1.651-1.653, "e1,d1" 1.650-1.655, "e2" 1.668, "e1,e3" 1.663:
   //  profiles/r04_b512_streams.txt;
   //  512 images per launch, one side stream: "e1" 1.067-1.070 against 1.071-1.074 (profiles/r04_b256_sweep.txt); 256 and 128: "e1,e2" stays)
-  const char* on_main = on_main_env ? on_main_env : !big ? (n * L[0]->d.B >= 512 ? "e1" : "e1,e2") : p->side_use >= 2 ? "e1" : (L[0]->d.dtype == SV_BF16 && !roll_off) ? "e1,e2,d4" :
+  const char* on_main = on_main_env ? on_main_env : !big ? (n * L[0]->d.B >= 512 ? "e1" : "e1,e2") : p->side.use >= 2 ? "e1" : (L[0]->d.dtype == SV_BF16 && !roll_off) ? "e1,e2,d4" :
                         L[0]->d.dtype == SV_F32 ? "e1,e2,e3" : "e1,e2,d5";
-  if (strstr(on_main, ln.c_str())) p->side_slot = sv_lgvae_plan::SIDE_MAX - 1;   // its own slab workspace: the side streams' slots are in use concurrently
-  else st = p->wgrad_stream(st);
-  if (latent_gemm_on(p) && L[0]->d.H == 1 && L[0]->d.W == 1 && L[0]->d.KH == 1 && n <= 4) {     // Dense (d1): latent_gemm.hip, whole batch per tile
+  if (strstr(on_main, ln.c_str())) p->side.slot = SideStreams::SIDE_MAX - 1;   // its own slab workspace: the side streams' slots are in use concurrently
+  else st = p->side.wgrad_stream(st);
+  if (L[0]->d.H == 1 && L[0]->d.W == 1 && L[0]->d.KH == 1 && n <= 4) {     // Dense (d1): latent_gemm.hip, whole batch per tile
     TnWgradProb q[4];
+    double flq = 0;
     for (int i = 0; i < n; ++i) {
       const sv_conv_desc& d = L[i]->d;
-      q[i] = TnWgradProb{x[i], d.ldx, dy[i], d.ldy, grads + p->params[L[i]->kparam].off, grads + p->params[L[i]->bparam].off, d.B, svg_cin_pad(&d),
-                         d.Cin, d.Cout, p->d.dtype == SV_F32};
-      fl += conv_flops(d);
+      q[i] = tn_prob(p, x[i], d.ldx, dy[i], d.ldy, grads + p->params[L[i]->kparam].off, grads + p->params[L[i]->bparam].off, d.B, svg_cin_pad(&d), d.Cin, d.Cout);
+      flq += conv_flops(d);
     }
-    bool ok = true;
-    for (int i = 0; i < n; ++i) ok = ok && svk_tn_wgrad_supported(q[i]);
-    if (ok) {
-      Scope sc(p, st, nm, fl, by);
-      return svk_tn_wgrad_multi(q, n, st);
-    }
-    fl = 0;
+    bool taken;
+    SV_TRY(run_latent_tn(p, nm.c_str(), flq, by, q, n, st, &taken));
+    if (taken) return SV_OK;
   }
   // the decoder head's weight gradient in polyphase form (poly_wgrad.hip) from ~768 images per launch (its three small
   // kernels cost more than they save below that: 16 images 42 vs 20 us; 1024 images 132 vs 184 us)
@@ -815,11 +653,11 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
     for (int i = 0; i < n; ++i) {
       svg_poly_wgrad_args(&L[i]->d, &a[i]);
       a[i].A = x[i]; a[i].dY = dy[i]; a[i].dW = pw[i]; a[i].dbias = pw[i] + 25 * Cin * 32;
-      a[i].ws = (float*)((char*)p->buf(WGRAD_WS) + (p->side_slot * SV_WGRAD_MAX_MULTI + i) * wsb); a[i].ws_bytes = wsb;
+      a[i].ws = (float*)((char*)p->buf(WGRAD_WS) + (p->side.slot * SV_WGRAD_MAX_MULTI + i) * wsb); a[i].ws_bytes = wsb;
       dwv[i] = grads + p->params[L[i]->kparam].off; dbv[i] = grads + p->params[L[i]->bparam].off;
       fl += conv_flops(L[i]->d);
     }
-    Scope sc(p, st, nm, fl, by);
+    Scope sc(p->prof, st, nm, fl, by);
     { double is = 0; for (int i = 0; i < n; ++i) is += poly_issued(L[i]->d, 100, false); sc.issued(is); }
     SV_TRY(svk_wgrad_bf16_forms_multi(a, n, st));        // wgrad_p5 or wgrad_tile
     const sv_conv_desc& d = L[0]->d;
@@ -832,10 +670,10 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
     float *dwv[2], *dbv[2], *slab[2];
     for (int i = 0; i < n; ++i) {
       dwv[i] = grads + p->params[L[i]->kparam].off; dbv[i] = grads + p->params[L[i]->bparam].off;
-      slab[i] = (float*)((char*)p->buf(WGRAD_WS) + (p->side_slot * SV_WGRAD_MAX_MULTI + i) * wsb);
+      slab[i] = (float*)((char*)p->buf(WGRAD_WS) + (p->side.slot * SV_WGRAD_MAX_MULTI + i) * wsb);
       fl += conv_flops(L[i]->d);
     }
-    Scope sc(p, st, nm, fl, by);
+    Scope sc(p->prof, st, nm, fl, by);
     { double is = 0; for (int i = 0; i < n; ++i) is += poly_issued(L[i]->d, svg_polyc_wgrad_form(&L[i]->d) == 2 ? 100 : 81, false); sc.issued(is); }
     const int rc = svk_polyc_wgrad_multi(&L[0]->d, n, x, dy, dwv, dbv, slab, wsb, p->fpair(L[0]->polycw), st);
     if (rc != SV_E_UNSUPPORTED) return rc;
@@ -849,18 +687,18 @@ static int run_wgrad_layers(sv_lgvae_plan* p, int n, Layer* const* L, const void
     a[i].A = x[i]; a[i].dY = dy[i];
     a[i].dW = grads + p->params[L[i]->kparam].off;
     a[i].dbias = grads + p->params[L[i]->bparam].off;
-    a[i].ws = (float*)((char*)p->buf(WGRAD_WS) + (p->side_slot * SV_WGRAD_MAX_MULTI + i) * wsb); a[i].ws_bytes = wsb;
+    a[i].ws = (float*)((char*)p->buf(WGRAD_WS) + (p->side.slot * SV_WGRAD_MAX_MULTI + i) * wsb); a[i].ws_bytes = wsb;
     fl += conv_flops(L[i]->d);
   }
-  Scope sc(p, st, nm, fl, by);
+  Scope sc(p->prof, st, nm, fl, by);
   sc.issued(fl);                        // (a polyphase form above may have been refused after booking its count)
   sc.split(L[0]->sc_reduce, 0, a[0].ev_mid);
   return svk_wgrad_dispatch_multi(a, n, L[0]->d.dtype, svg_pick_cfg(L[0]->d.Cout), st);
 }
 
-// early: side stream 0 (sv_lgvae_plan::early_stream) or nullptr -- the decoders' half of the job table goes there, the encoders' half stays in front of their forward
+// early: side stream 0 (SideStreams::early_stream) or nullptr -- the decoders' half of the job table goes there, the encoders' half stays in front of their forward
 static int phase_prep(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t st, hipStream_t early) {
-  Scope sc(p, st, "prep_weights", 0, (double)p->nparams * (4 + 2.0 * p->esz()));
+  Scope sc(p->prof, st, "prep_weights", 0, (double)p->nparams * (4 + 2.0 * p->esz()));
   const PrepJob* jobs = (const PrepJob*)p->buf(JOBS);
   if (!early || p->dec_block0 == 0) return svk_prep_weights(s->params, p->buf(WARENA), p->d.dtype, jobs, (int)p->jobs.size(), p->prep_blocks, st);
   SV_TRY(svk_prep_weights(s->params, p->buf(WARENA), p->d.dtype, jobs, (int)p->jobs.size(), p->prep_blocks - p->dec_block0, early, p->dec_block0));
@@ -874,28 +712,20 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
   const int B = d.B, H = d.H, W = d.W, dt = d.dtype;
   const int Lg = d.global_latent, Ll = d.local_latent, Lc = Lg + Ll;
   const bool no_twin = no_twin_pointwise();
+  LatentBlock& lat = p->lat;
   bool pre_slabs = false;
-  int pre_S[2] = {0, 0};
-  int64_t pre_stride[2] = {0, 0};
   const int nd = p->ndec();
-  if (do_enc && d.global_only) {
+  if (do_enc) {
+    // the head pre-activations (split-K partial sums) and dz (split-K dgrad of d1) accumulate with atomics: zeroed here -- not needed once both split-K launches
+    // of this plan have gone through latent_gemm.hip's slabs (nothing accumulates into these buffers, and the backward must not re-zero dz either).
     // GMVae: the caller's encoder_x is the only encoder -- this phase zeroes dz (split-K target of d1's input gradient) and fills in8_x
-    SV_TRY(p->bufs.zero(GZ, GZ, st));
-    p->gz_clean = true;
-    p->gz_zero_skipped = false;
-  } else if (do_enc && !(latent_gemm_on(p) && p->lat_head_ok && p->lat_d1_ok && !d.external_global_encoder)) {
-    // the head pre-activations (split-K partial sums) and dz (split-K dgrad of d1) accumulate with atomics
-    // (not needed once both split-K launches of this plan have gone through latent_gemm.hip's slabs: nothing accumulates into these buffers)
-    SV_TRY(p->bufs.zero(PRE, GZ_XH, st));
-    p->gz_clean = true;
-    p->gz_zero_skipped = false;
-  } else if (do_enc) {
-    p->gz_clean = true;                        // (nothing accumulates into dz either: the backward must not re-zero it)
-    p->gz_zero_skipped = true;
+    const bool slab_path = !d.global_only && latent_gemm_on(p) && lat.head_ok && lat.d1_ok && !d.external_global_encoder;
+    const DzStep t = dz_transition(lat.dz, DzEvent::EncFwd, slab_path);
+    SV_TRY(zero_dz(p, t.zero, st));
+    lat.dz = t.next;
   }
-  if (do_enc) { p->dz_slabs = false; p->dz_valid = false; }
   if (do_enc && !(s->phases & SV_PHASE_INPUTS_STAGED)) {      // (staged: sv_scramble_gather_staged filled in8_x / in8_xh for this images6)
-    Scope sc(p, st, "split_pad", 0, (double)B * H * W * (24 + 16.0 * p->esz()));
+    Scope sc(p->prof, st, "split_pad", 0, (double)B * H * W * (24 + 16.0 * p->esz()));
     SV_TRY(svk_split_pad(s->images6, p->buf(IN8, 0), p->buf(IN8, 1), dt, (int64_t)B * H * W, st));
   }
   if (d.global_only) do_enc = false;           // (that was all of the encoders' phase: the plan has none)
@@ -927,41 +757,25 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
       fl += conv_flops(Lh.d);
       by += conv_bytes(Lh.d, 0, p->esz());
     }
-    Scope sc(p, st, "fwd.head", fl, by);
-    bool done = false;
-    if (latent_gemm_on(p)) {
-      NtGemmProb q[2];
-      float* outs[2];
-      int nq = 0;
-      for (int e = e0; e < 2; ++e, ++nq) {
-        Layer& Lh = p->enc[e][3];
-        NtGemmProb& g = q[nq];
-        memset(&g, 0, sizeof(g));
-        g.f32 = p->d.dtype == SV_F32;
-        g.A = p->buf(A3, e); g.lda = Lh.d.Cin;
-        g.W = (char*)p->buf(WARENA) + Lh.wf_off * p->esz(); g.ldw = Lh.d.Cin;
-        g.out = p->buf(LAT_WS, e); g.ldo = Lh.d.Cout;
-        g.M = B; g.N = Lh.d.Cout; g.K = Lh.d.Cin; g.out_f32 = 1;
-        g.splitk = svk_nt_gemm_pick_splitk(B, g.N, g.K, 2);     // (as the slab buffers were sized)
-        g.slab_stride = (int64_t)B * g.ldo;
-        outs[nq] = (float*)p->buf(PRE, e);
-        if ((int64_t)g.splitk * g.slab_stride * 4 > p->bbytes(LAT_WS, e)) return SV_E_WORKSPACE;   // (cannot happen: sized from the same calls)
-      }
-      const int rc = svk_nt_gemm_multi(q, nq, 64, st);
-      if (rc == SV_OK) {
-        done = true;
-        p->lat_head_ok = true;
-        // Sampling + KL sum the slabs themselves, in slice order: the same bits (more than 16 slices: one wave per row reads them too slowly, B = 64: +4 %)
-        if (latent_fuse_on() && !e0 && !no_twin && q[0].splitk <= 16 && q[1].splitk <= 16) {
-          pre_slabs = true;
-          for (int e = 0; e < 2; ++e) { pre_S[e] = q[e].splitk; pre_stride[e] = q[e].slab_stride; }
-        } else SV_TRY(svk_nt_slab_reduce(q, outs, nq, st));
-      } else if (rc != SV_E_UNSUPPORTED) return rc;
+    NtGemmProb q[2];
+    float* outs[2];
+    for (int e = e0; e < 2; ++e) {
+      const sv_conv_desc& hd = p->enc[e][3].d;
+      q[e - e0] = nt_prob(p, p->buf(A3, e), hd.Cin, p->enc[e][3].wf_off, hd.Cin, p->buf(LAT_WS, e), hd.Cout, B, hd.Cout, hd.Cin, nullptr, SV_ACT_NONE, nullptr, lat.head_S[e]);
+      outs[e - e0] = (float*)p->buf(PRE, e);
     }
-    if (done) {}
-    else if (e0 || cfgs[0] == cfgs[1]) SV_TRY(svk_tap_gemm_multi(a, 2 - e0, dt, cfgs[0], st));
-    else
-      for (int e = 0; e < 2; ++e) SV_TRY(svk_tap_gemm(a[e], dt, cfgs[e], st));   // latent sizes with different tiles
+    // Sampling + KL sum the slabs themselves, in slice order: the same bits (more than 16 slices: one wave per row reads them too slowly, B = 64: +4 %)
+    const bool fuse = latent_fuse_on() && !e0 && !no_twin && lat.head_S[0] <= 16 && lat.head_S[1] <= 16;
+    LatentRan ran;
+    SV_TRY(run_latent_nt(p, "fwd.head", fl, by, q, 2 - e0, 64, outs, fuse, st, &ran));
+    if (ran != LAT_NOT_TAKEN) lat.head_ok = true;
+    pre_slabs = ran == LAT_SLABS_LEFT;
+    if (ran == LAT_NOT_TAKEN) {
+      Scope sc(p->prof, st, "fwd.head", fl, by);
+      if (e0 || cfgs[0] == cfgs[1]) SV_TRY(svk_tap_gemm_multi(a, 2 - e0, dt, cfgs[0], st));
+      else
+        for (int e = 0; e < 2; ++e) SV_TRY(svk_tap_gemm(a[e], dt, cfgs[e], st));   // latent sizes with different tiles
+    }
   }
   if (do_enc) {
     // Sampling + KL: both networks in one launch; one network per launch for SPLIT-GMVAE (the caller's encoder is the x network) and under SV_NO_TWIN_POINTWISE
@@ -972,15 +786,15 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
       // mean bias and sd bias are separate Keras tensors
       a[e] = {(const float*)p->buf(pre_slabs ? LAT_WS : PRE, e), s->params + p->params[Lh.kparam + 1].off, s->params + p->params[Lh.kparam + 3].off,
               e == 0 ? s->eps_x : s->eps_x_hat, (float*)p->buf(EPS, e), (float*)p->buf(Z_MEAN, e), (float*)p->buf(Z_SIG, e), (float*)p->buf(Z, e),
-              p->buf(ZCAT), (float*)p->buf(KL, e), Lc, e == 0 ? 0 : Lg, e == 0 ? Lg : Ll, e, pre_slabs ? pre_S[e] : 0, pre_slabs ? pre_stride[e] : 0};
+              p->buf(ZCAT), (float*)p->buf(KL, e), Lc, e == 0 ? 0 : Lg, e == 0 ? Lg : Ll, e, pre_slabs ? lat.head_S[e] : 0, pre_slabs ? lat.head_stride[e] : 0};
     }
     for (int e = e0; e < 2; e += per) {
-      Scope sc(p, st, "reparam_kl_fwd", 0, (double)B * (per == 2 ? Lg + Ll : a[e].L) * 16);
+      Scope sc(p->prof, st, "reparam_kl_fwd", 0, (double)B * (per == 2 ? Lg + Ll : a[e].L) * 16);
       SV_TRY(svk_reparam_kl_fwd(a + e, per, dt, B, s->seed, s->step, s->sample_offset, st, p->dyn));
     }
   }
   if (do_dec) {
-    SV_TRY(p->early_wait(st));               // the decoders' weight images (and the zeroed gradient buffer) of this call's early side work
+    SV_TRY(p->side.early_wait(st));               // the decoders' weight images (and the zeroed gradient buffer) of this call's early side work
     const void* zin[2] = {p->buf(ZCAT), (const char*)p->buf(ZCAT) + (size_t)Lg * p->esz()};
     {   // d1 differs between the twins (zcat vs local-only input): two shapes, one launch
       Layer* Ls[2] = {&p->dec[0][0], &p->dec[1][0]};
@@ -1001,7 +815,7 @@ static int phase_forward(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool do_
       for (int k = 0; k < nd; ++k) {
         xs[k] = p->buf(lo_id[l], k);
         if (!Ls[k]->d.ups_in) {
-          Scope sc(p, st, "upsample_fwd", 0, 0);
+          Scope sc(p->prof, st, "upsample_fwd", 0, 0);
           SV_TRY(sv_upsample2x_fwd(xs[k], p->buf(hi_id[l], k), dt, B, Ls[k]->d.H / 2, Ls[k]->d.W / 2, Ls[k]->d.Cin, st));
           xs[k] = p->buf(hi_id[l], k);
         }
@@ -1028,7 +842,7 @@ static int phase_loss(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool with_g
                                                        // forms the per-image sums itself (fixed order), no separate kernel
   if (!from_parts) {
     // algorithmic bytes: read x, m, log_scale (12 B/element) + write dm, dls (2 * esz B/element); both networks
-    Scope sc(p, st, "dlogistic_nll", 0, p->ndec() * d.B * d.H * d.W * 3.0 * (12.0 + (with_grad ? 2.0 * p->esz() : 0.0)));
+    Scope sc(p->prof, st, "dlogistic_nll", 0, p->ndec() * d.B * d.H * d.W * 3.0 * (12.0 + (with_grad ? 2.0 * p->esz() : 0.0)));
     auto zs = [&](int id, int64_t esz) {               // elements from the x network's record to the x-hat network's
       if (d.global_only) return (int64_t)0;            // (one network: no second record)
       return (int64_t)((char*)p->buf(id, 1) - (char*)p->buf(id, 0)) / esz;
@@ -1048,8 +862,16 @@ static int phase_loss(sv_lgvae_plan* p, const sv_lgvae_step_args* s, bool with_g
 
 static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t st) {
   const int nd = p->ndec();
-  if (!p->gz_clean) SV_TRY(p->bufs.zero(GZ, GZ + nd - 1, st));   // a second backward over the same forward: re-zero the split-K dz accumulators
-  p->gz_clean = false;
+  // What every decoders' backward needs before it starts (a second backward over the same forward: re-zero the split-K dz accumulators); how d1's input
+  // gradient leaves dz is known only at the end of the phase, where the transition that really happened is applied
+  LatentBlock& lat = p->lat;
+  const DzState dz_in = lat.dz;
+  // (t_in.zero is the zero of EVERY decoders'-backward transition out of dz_in, with one exception: Stale + accumulating, handled at d1 below -- see
+  //  dz_transition: DecBwdSlabs and DecBwdGz return the same `used ? Gz : None` but for that case.  So issuing t_in.zero here and the difference there
+  //  is the zero of the one transition that really happens, and both memsets precede the only writer of gz_*)
+  const DzStep t_in = dz_transition(dz_in, DzEvent::DecBwdSlabs, true);
+  SV_TRY(zero_dz(p, t_in.zero, st));
+  lat.dz = t_in.next;                  // (an error return below leaves a state that re-zeroes, as the memset above is spent)
   const sv_lgvae_desc& d = p->d;
   const int B = d.B, H = d.H, W = d.W, dt = d.dtype;
   const int Lg = d.global_latent;
@@ -1084,7 +906,7 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
         wp[k] = (const char*)p->buf(WARENA) + Ls[k]->wd_off[0] * p->esz();
         fl += conv_flops(Ls[k]->d); by += conv_bytes(Ls[k]->d, 1, p->esz());
       }
-      Scope sc(p, st, Ls[0]->sc_dgrad, fl, by);
+      Scope sc(p->prof, st, Ls[0]->sc_dgrad, fl, by);
       { double is = 0; for (int k = 0; k < nd; ++k) is += poly_issued(Ls[k]->d, 81, true); sc.issued(is); }
       frc = svk_polyd_dgrad_multi(&Ls[0]->d, nd, gy, wp, lo, gl, p->pair(POLYD), st);
     }
@@ -1098,7 +920,7 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
       const int64_t lo_bytes = (int64_t)B * h * w * c * p->esz();
       const bool contig = nd == 2 && (const char*)gu[1] == (const char*)gu[0] + 4 * lo_bytes &&
                           (const char*)lo[1] == (const char*)lo[0] + lo_bytes && (const char*)gl[1] == (const char*)gl[0] + lo_bytes;
-      Scope sc(p, st, ups_scope[l], 0, nd * 6.0 * lo_bytes);   // read g_hi (4x) + mask, write g_lo; both networks
+      Scope sc(p->prof, st, ups_scope[l], 0, nd * 6.0 * lo_bytes);   // read g_hi (4x) + mask, write g_lo; both networks
       if (contig) SV_TRY(sv_upsample2x_bwd(gu[0], lo[0], gl[0], dt, 2 * B, h, w, c, st));
       else
         for (int k = 0; k < nd; ++k) SV_TRY(sv_upsample2x_bwd(gu[k], lo[k], gl[k], dt, B, h, w, c, st));
@@ -1119,41 +941,28 @@ static int phase_bwd_decoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hip
     const BufPair g1 = p->pair(G1), gz = p->pair(GZ);
     SV_TRY(run_wgrad_layers(p, nd, Ls, zin, g1, s->grads, st));
     for (int k = 0; k < nd; ++k) Ld[k].d.ldx = Ld[k].d.Cin;   // dz has its own row pitch (Lz), not the zcat pitch
-    bool done = false;
-    p->dz_slabs = false;
-    p->dz_valid = true;
-    if (latent_gemm_on(p)) {
-      NtGemmProb q[2];
-      float* outs[2];
-      double fl = 0, by = 0;
-      for (int k = 0; k < nd; ++k) {
-        const sv_conv_desc& dd = Ld[k].d;
-        NtGemmProb& g = q[k];
-        memset(&g, 0, sizeof(g));
-        g.f32 = p->d.dtype == SV_F32;
-        g.A = g1[k]; g.lda = dd.ldy;
-        g.W = (char*)p->buf(WARENA) + Ld[k].wd_off[0] * p->esz(); g.ldw = svg_gdy(&dd);
-        g.out = p->buf(LAT_WS, k); g.ldo = dd.Cin;
-        g.M = B; g.N = dd.Cin; g.K = dd.Cout; g.out_f32 = 1;
-        g.splitk = svk_nt_gemm_pick_splitk(B, g.N, g.K, 2);
-        g.slab_stride = (int64_t)B * g.ldo;
-        if ((int64_t)g.splitk * g.slab_stride * 4 > p->bbytes(LAT_WS, k)) return SV_E_WORKSPACE;           // (cannot happen: sized from the same calls)
-        outs[k] = (float*)gz[k];
-        fl += conv_flops(dd); by += conv_bytes(dd, 1, p->esz());
-      }
-      Scope sc(p, st, "dgrad.d1", fl, by);
-      const int rc = svk_nt_gemm_multi(q, nd, 64, st);
-      if (rc == SV_OK) {
-        done = true;
-        p->lat_d1_ok = true;
-        const bool no_twin = no_twin_pointwise();
-        if (latent_fuse_on() && !d.external_global_encoder && !no_twin && q[0].splitk <= 16 && q[1].splitk <= 16) {     // reparam_kl_bwd sums the slabs (SPLIT-GMVAE reads gz_x: summed here)
-          p->dz_slabs = true;
-          for (int k = 0; k < 2; ++k) { p->dz_S[k] = q[k].splitk; p->dz_stride[k] = q[k].slab_stride; }
-        } else SV_TRY(svk_nt_slab_reduce(q, outs, nd, st));
-      } else if (rc != SV_E_UNSUPPORTED) return rc;
+    NtGemmProb q[2];
+    float* outs[2];
+    double fl = 0, by = 0;
+    for (int k = 0; k < nd; ++k) {
+      const sv_conv_desc& dd = Ld[k].d;
+      q[k] = nt_prob(p, g1[k], dd.ldy, Ld[k].wd_off[0], svg_gdy(&dd), p->buf(LAT_WS, k), dd.Cin, B, dd.Cin, dd.Cout, nullptr, SV_ACT_NONE, nullptr, lat.d1_S[k]);
+      outs[k] = (float*)gz[k];
+      fl += conv_flops(dd); by += conv_bytes(dd, 1, p->esz());
     }
-    if (!done) SV_TRY(run_dgrad_layers(p, nd, Lds, g1, none, gz, true, st));
+    // reparam_kl_bwd sums the slabs (SPLIT-GMVAE and GMVae read gz_x: summed here)
+    const bool fuse = latent_fuse_on() && !d.external_global_encoder && !no_twin_pointwise() && lat.d1_S[0] <= 16 && lat.d1_S[1] <= 16;
+    LatentRan ran;
+    SV_TRY(run_latent_nt(p, "dgrad.d1", fl, by, q, nd, 64, outs, fuse, st, &ran));
+    if (ran != LAT_NOT_TAKEN) lat.d1_ok = true;
+    if (ran != LAT_SLABS_LEFT) {       // (slabs left: lat.dz is t_in.next already)
+      // dz in gz_*: summed from the slabs (which overwrites gz_*), or accumulated by the im2col kernel's split-K atomics into a gz_* that must be zero --
+      // after a forward that skipped the zero fill (DzState::Stale; no current shape reaches this fall-back) it is zeroed here
+      const DzStep t = dz_transition(dz_in, DzEvent::DecBwdGz, ran == LAT_RAN);
+      if (t.zero != t_in.zero) SV_TRY(zero_dz(p, t.zero, st));
+      lat.dz = t.next;
+      if (ran == LAT_NOT_TAKEN) SV_TRY(run_dgrad_layers(p, nd, Lds, g1, none, gz, true, st));
+    }
   }
   return SV_OK;
 }
@@ -1165,17 +974,20 @@ static int phase_bwd_encoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, boo
   const float kl_scale = d.beta / (float)B;
   const int e0 = d.external_global_encoder ? 1 : 0;
   if (d.global_only) return SV_OK;            // GMVae: the only encoder is the caller's (it reads dL/dz_x from gz_x)
-  if (do_heads && !p->dz_valid && p->gz_zero_skipped) {       // KL terms only (no decoder backward since the forward): dz = 0
-    SV_TRY(p->bufs.zero(GZ, GZ_XH, st));
-    p->gz_zero_skipped = false;
+  LatentBlock& lat = p->lat;
+  if (do_heads) {                             // (KL terms only -- no decoder backward since a forward that skipped the zero fill: dz = 0)
+    const DzStep t = dz_transition(lat.dz, DzEvent::EncHeadBwd, false);
+    SV_TRY(zero_dz(p, t.zero, st));
+    lat.dz = t.next;
   }
   if (do_heads) {
     // the adjoint of Sampling + KL, launched as the forward is (phase_forward).  decoder_x's dz is [B, Lc]: columns [0, Lg) belong to z_x, [Lg, Lc) to z_x-hat,
-    // which also gets decoder_x-hat's dz.  dz_slabs (twin launch only): the K-slice slabs of d1's input gradient instead, summed in the kernel
-    Scope sc(p, st, "reparam_kl_bwd", 0, 0);
-    const int per = no_twin_pointwise() ? 1 : 2 - e0, src = p->dz_slabs ? LAT_WS : GZ;
-    const int S0 = p->dz_slabs ? p->dz_S[0] : 0, S1 = p->dz_slabs ? p->dz_S[1] : 0;
-    const int64_t sd0 = p->dz_slabs ? p->dz_stride[0] : 0, sd1 = p->dz_slabs ? p->dz_stride[1] : 0;
+    // which also gets decoder_x-hat's dz.  DzState::InSlabs (twin launch only): the K-slice slabs of d1's input gradient instead, summed in the kernel
+    Scope sc(p->prof, st, "reparam_kl_bwd", 0, 0);
+    const bool slabs = lat.dz == DzState::InSlabs;
+    const int per = no_twin_pointwise() ? 1 : 2 - e0, src = slabs ? LAT_WS : GZ;
+    const int S0 = slabs ? lat.d1_S[0] : 0, S1 = slabs ? lat.d1_S[1] : 0;
+    const int64_t sd0 = slabs ? lat.d1_stride[0] : 0, sd1 = slabs ? lat.d1_stride[1] : 0;
     const float* dzx = (const float*)p->buf(src, 0);
     const ReparamBwdArgs a[2] = {
         {dzx, nullptr, (const float*)p->buf(Z_MEAN, 0), (const float*)p->buf(Z_SIG, 0), (const float*)p->buf(EPS, 0), p->buf(GHEAD, 0), Lc, 0, Lg, S0, 0, sd0, 0},
@@ -1203,46 +1015,30 @@ static int phase_bwd_encoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, boo
       }
     }
     {
-      hipStream_t ws = p->wgrad_stream(st);
-      Scope sc(p, ws, "wgrad.head", fl, by);
-      bool done = false;
-      if (latent_gemm_on(p) && n <= 4) {
-        TnWgradProb q[4];
-        bool ok = true;
-        for (int i = 0; i < n; ++i) {
-          q[i] = TnWgradProb{a[i].A, a[i].lda, a[i].dY, a[i].ldy, a[i].dW, a[i].dbias, B, a[i].Cin_pad, a[i].Cin_real, a[i].N, dt == SV_F32};
-          ok = ok && svk_tn_wgrad_supported(q[i]);
-        }
-        if (ok) { SV_TRY(svk_tn_wgrad_multi(q, n, ws)); done = true; }
+      hipStream_t ws = p->side.wgrad_stream(st);
+      TnWgradProb q[4];
+      for (int i = 0; i < n; ++i) q[i] = tn_prob(p, a[i].A, a[i].lda, a[i].dY, a[i].ldy, a[i].dW, a[i].dbias, B, a[i].Cin_pad, a[i].Cin_real, a[i].N);
+      bool taken;
+      SV_TRY(run_latent_tn(p, "wgrad.head", fl, by, q, n, ws, &taken));
+      if (!taken) {
+        Scope sc(p->prof, ws, "wgrad.head", fl, by);
+        const int cg = svg_pick_cfg(Lg), cl = svg_pick_cfg(Ll);      // the narrower tile serves both widths
+        SV_TRY(svk_wgrad_dispatch_multi(a, n, dt, e0 ? cl : (cg > cl ? cg : cl), ws));
       }
-      const int cg = svg_pick_cfg(Lg), cl = svg_pick_cfg(Ll);      // the narrower tile serves both widths
-      if (!done) SV_TRY(svk_wgrad_dispatch_multi(a, n, dt, e0 ? cl : (cg > cl ? cg : cl), ws));
     }
     Layer* Ls[2] = {&p->enc[0][3], &p->enc[1][3]};
     const BufPair gh = p->pair(GHEAD), a3 = p->pair(A3), ga3 = p->pair(GA3);
-    bool done = false;
-    if (latent_gemm_on(p)) {
-      NtGemmProb q[2];
-      int nq = 0;
-      double fl = 0, by = 0;
-      for (int e = e0; e < 2; ++e, ++nq) {
-        Layer& Lh = p->enc[e][3];
-        NtGemmProb& g = q[nq];
-        memset(&g, 0, sizeof(g));
-        g.f32 = p->d.dtype == SV_F32;
-        g.A = gh[e]; g.lda = Lh.d.Cout;
-        g.W = (char*)p->buf(WARENA) + Lh.wd_off[0] * p->esz(); g.ldw = Lh.d.Cout;
-        g.out = ga3[e]; g.ldo = Lh.d.Cin; g.mask = a3[e];
-        g.M = B; g.N = Lh.d.Cin; g.K = Lh.d.Cout; g.splitk = 1;
-        fl += conv_flops(Lh.d); by += conv_bytes(Lh.d, 1, p->esz());
-      }
-      Scope sc(p, st, "dgrad.head", fl, by);
-      const int rc = svk_nt_gemm_multi(q, nq, B >= 256 ? 128 : 64, st);
-      if (rc == SV_OK) done = true;
-      else if (rc != SV_E_UNSUPPORTED) return rc;
+    NtGemmProb q[2];
+    double flh = 0, byh = 0;
+    for (int e = e0; e < 2; ++e) {
+      const sv_conv_desc& hd = p->enc[e][3].d;
+      q[e - e0] = nt_prob(p, gh[e], hd.Cout, p->enc[e][3].wd_off[0], hd.Cout, ga3[e], hd.Cin, B, hd.Cin, hd.Cout, nullptr, SV_ACT_NONE, a3[e]);
+      flh += conv_flops(hd); byh += conv_bytes(hd, 1, p->esz());
     }
-    if (!done) SV_TRY(run_dgrad_layers(p, 2 - e0, Ls + e0, gh + e0, a3 + e0, ga3 + e0, false, st));
-    if (buckets) SV_TRY(p->record_bucket(1, st));       // the heads' weight gradients are enqueued (main or side stream)
+    LatentRan ran;
+    SV_TRY(run_latent_nt(p, "dgrad.head", flh, byh, q, 2 - e0, B >= 256 ? 128 : 64, nullptr, false, st, &ran));
+    if (ran == LAT_NOT_TAKEN) SV_TRY(run_dgrad_layers(p, 2 - e0, Ls + e0, gh + e0, a3 + e0, ga3 + e0, false, st));
+    if (buckets) SV_TRY(p->side.record_bucket(1, st));       // the heads' weight gradients are enqueued (main or side stream)
   }
   if (do_convs) {
     static const BufId act_id[3] = {IN8, A1, A2}, g_id[3] = {GA1, GA2, GA3};
@@ -1253,7 +1049,7 @@ static int phase_bwd_encoders(sv_lgvae_plan* p, const sv_lgvae_step_args* s, boo
       if (l == 0) break;
       SV_TRY(run_dgrad_layers(p, 2 - e0, Ls + e0, gy + e0, x + e0, p->pair(g_id[l - 1]) + e0, false, st));
     }
-    if (buckets) SV_TRY(p->record_bucket(2, st));
+    if (buckets) SV_TRY(p->side.record_bucket(2, st));
   }
   return SV_OK;
 }
@@ -1289,7 +1085,7 @@ extern "C" int sv_lgvae_plan_create(const sv_lgvae_desc* d, sv_lgvae_plan** out)
   if (p->d.global_only) p->d.local_latent = p->d.global_latent;   // (ignored in this mode: keep the derived sizes well defined)
   p->params = build_params(d);
   p->nparams = p->params.back().off + (p->params.back().count + 3) / 4 * 4;
-  p->bound = false; p->prof_on = false;
+  p->bound = false;
   build_layers(p);
   for (int e = 0; e < 2 && !p->d.global_only; ++e)
     for (int l = 0; l < 4; ++l)
@@ -1307,19 +1103,8 @@ extern "C" int sv_lgvae_plan_create(const sv_lgvae_desc* d, sv_lgvae_plan** out)
 
 extern "C" void sv_lgvae_plan_destroy(sv_lgvae_plan* p) {
   if (!p) return;
-  for (auto& pe : p->pending) { (void)hipEventDestroy(pe.a); (void)hipEventDestroy(pe.b); }
-  for (auto e : p->event_pool) (void)hipEventDestroy(e);
-  for (int i = 0; i < p->nside; ++i) {
-    (void)hipStreamSynchronize(p->side[i]);          // (shared with every other plan / tape of the process: not destroyed)
-    (void)hipEventDestroy(p->ev_join[i]);
-  }
-  if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
-  if (p->ev_early) (void)hipEventDestroy(p->ev_early);
-  for (auto e : p->ev_cap)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& row : p->ev_bucket)
-    for (auto e : row)
-      if (e) (void)hipEventDestroy(e);
+  p->prof.destroy();
+  p->side.destroy();
   if (!p->graphs.empty()) (void)hipDeviceSynchronize();   // a replay may still be in flight
   for (auto& kv : p->graphs)
     if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
@@ -1341,30 +1126,16 @@ extern "C" int sv_lgvae_buffer(const sv_lgvae_plan* p, const char* name, int64_t
 
 static int run_phases(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t st) {
   const int ph = s->phases;
-  p->n_cap = 0;                                  // this call's fork / join events and the side streams it uses
-  for (auto& u : p->side_used) u = false;
-  {
-    // Two weight-gradient side streams for a whole step at >= 768 images per launch, one otherwise.  Re-measured in round 3 (round 2: +-0):
-    // B = 512 2.056 -> 2.005 ms (three launches in flight fill the CUs the rolling-window d4 kernel and the row-ring input gradients leave);
-    // B = 256 +1.8 %, 128 +6 %, 64 +3 % (launches too small to share the chip three ways); a data-parallel step (phase-split calls: the
-    // communication stream is a further active queue) 2.14 -> 2.15 ms over torch's nccl, 2.12 -> 3.31 ms over sv_comm (four active streams
-    // on GPU_MAX_HW_QUEUES = 3): one.  SV_SIDE_STREAMS forces a count.
-    const int forced = sv_knob_side_streams(0);
-    const bool whole = (ph & SV_PHASE_ALL) == SV_PHASE_ALL;
-    // fp32 (round 5, polyphase decoder layers + 52-KB weight-gradient tiles): two side streams 9.60-9.62 -> 9.37-9.39 ms at B = 512 (profiles/r05_f32_streams.txt)
-    // (fp32, 256 images per network: 5.14 -> 5.09 ms; 128: 2.84 -> 2.87: from 256)
-    // (round 6, with the process's fixed side streams: bf16 256 images per network 1.068-1.080 -> 1.054-1.056 ms with two: the bf16 threshold moved from 768 to 512 too;
-    //  profiles/r06_sweep_bf16.txt)
-    p->side_use = forced > 0 ? forced : (whole && p->ndec() * p->d.B >= 512) ? 2 : 1;
-  }
+  const bool capture = p->graph_on || p->dyn;
+  p->side.begin_call(p->prof.serial(), capture, (ph & SV_PHASE_ALL) == SV_PHASE_ALL, p->ndec() * p->d.B);
   // early side work: the decoders' weight images and the gradient buffer's zero fill on side stream 0 beside the encoders' forward (see early_stream)
   const bool zero_here = (ph & SV_PHASE_LOSS) && s->grads;
-  hipStream_t early = ((ph & SV_PHASE_PREP) && (ph & SV_PHASE_FWD_ENCODERS)) ? p->early_stream(st) : nullptr;
+  hipStream_t early = ((ph & SV_PHASE_PREP) && (ph & SV_PHASE_FWD_ENCODERS)) ? p->side.early_stream(st) : nullptr;
   if (early && zero_here) {
     if (hipMemsetAsync(s->grads, 0, (size_t)p->nparams * 4, early) != hipSuccess) return (int)hipGetLastError();
   }
   if (ph & SV_PHASE_PREP) SV_TRY(phase_prep(p, s, st, early));
-  if (early) SV_TRY(p->early_done(early));
+  if (early) SV_TRY(p->side.early_done(early));
   static const bool no_fused_nll = SV_TUNE_FLAG("SV_NO_FUSED_NLL");    // A/B: dlogistic_kernel after the forward
   static const bool no_fused_nll_f32 = SV_TUNE_FLAG("SV_NO_FUSED_NLL_F32");    // (fp32 since round 6; A/B)
   const bool want_nll = !no_fused_nll && (ph & SV_PHASE_FWD_DECODERS) && (ph & SV_PHASE_LOSS) && s->grads && s->images6 &&
@@ -1373,25 +1144,25 @@ static int run_phases(sv_lgvae_plan* p, const sv_lgvae_step_args* s, hipStream_t
   if (ph & SV_PHASE_FORWARD) SV_TRY(phase_forward(p, s, ph & SV_PHASE_FWD_ENCODERS, ph & SV_PHASE_FWD_DECODERS, st, want_nll));
   if (ph & SV_PHASE_LOSS) {
     if (s->grads && !early) {
-      Scope sc(p, st, "zero_grads", 0, (double)p->nparams * 4);
+      Scope sc(p->prof, st, "zero_grads", 0, (double)p->nparams * 4);
       if (hipMemsetAsync(s->grads, 0, (size_t)p->nparams * 4, st) != hipSuccess) return (int)hipGetLastError();
     }
     SV_TRY(phase_loss(p, s, s->grads != nullptr, st));
   }
-  SV_TRY(p->early_wait(st));                 // (a call without the decoders' forward: before any gradient is written, at the latest here)
-  const bool buckets = (ph & SV_PHASE_BUCKET_EVENTS) && !p->graph_on && !p->dyn;      // (not in captured steps: the events belong to eager launches)
+  SV_TRY(p->side.early_wait(st));                 // (a call without the decoders' forward: before any gradient is written, at the latest here)
+  const bool buckets = (ph & SV_PHASE_BUCKET_EVENTS) && !capture;      // (not in captured steps: the events belong to eager launches)
   // a backward phase invalidates the events of every earlier step: sv_lgvae_bucket_wait must never succeed against events that belong to gradients
   // of a previous step (it returns SV_E_STATE instead, and the trainer falls back to ordering the collective behind the compute stream)
-  if (ph & SV_PHASE_BACKWARD) p->clear_buckets();
+  if (ph & SV_PHASE_BACKWARD) p->side.clear_buckets();
   if (ph & SV_PHASE_BWD_DECODERS) {
     SV_TRY(phase_bwd_decoders(p, s, st));
-    if (buckets) SV_TRY(p->record_bucket(0, st));
+    if (buckets) SV_TRY(p->side.record_bucket(0, st));
   }
   if (ph & (SV_PHASE_BWD_ENC_HEADS | SV_PHASE_BWD_ENC_CONVS))
     SV_TRY(phase_bwd_encoders(p, s, ph & SV_PHASE_BWD_ENC_HEADS, ph & SV_PHASE_BWD_ENC_CONVS, st, buckets));
-  SV_TRY(p->join_side(st));
+  SV_TRY(p->side.join_side(st));
   if (ph & SV_PHASE_ADAM) {
-    Scope sc(p, st, "adam_step", 0, (double)p->nparams * 28);
+    Scope sc(p->prof, st, "adam_step", 0, (double)p->nparams * 28);
     SV_TRY(svk_adam_step(s->params, s->grads, s->adam_m, s->adam_v, p->nparams, s->lr, s->beta1, s->beta2,
                          s->adam_eps, s->t, s->grad_scale, p->dyn, st));
   }
@@ -1420,7 +1191,7 @@ extern "C" int sv_lgvae_step(sv_lgvae_plan* p, const sv_lgvae_step_args* s, void
   if (train && !s->grads) return SV_E_BADARG;
   if ((ph & SV_PHASE_ADAM) && (!s->grads || !s->adam_m || !s->adam_v || s->t <= 0)) return SV_E_BADARG;
   // no capture on the legacy default stream (HIP forbids it): callers that want replay run on a created stream
-  if (!p->graph_on || p->prof_on || !st) return run_phases(p, s, st);
+  if (!p->graph_on || p->prof.on || !st) return run_phases(p, s, st);
 
   // hipGraph replay: the first step with a given key runs eagerly (it also raises the kernels' dynamic-LDS caps, which
   // must not happen inside a capture), the second is captured, every later one is one graph launch.
@@ -1466,26 +1237,22 @@ extern "C" int sv_lgvae_graph_enable(sv_lgvae_plan* p, int32_t enable) {
 
 extern "C" int sv_lgvae_bucket_wait(sv_lgvae_plan* p, int32_t bucket, void* stream) {
   if (!p || bucket < 0 || bucket > 3) return SV_E_BADARG;
-  int n = 0;
-  for (int k = (bucket == 3 ? 1 : bucket); k <= (bucket == 3 ? 2 : bucket); ++k)
-    for (int i = 0; i <= sv_lgvae_plan::SIDE_MAX; ++i)
-      if (p->bucket_rec[k][i]) {
-        // test hook (negative control of tests/test_gpu_dist.py::test_buckets_wait_for_the_side_stream): drop the side streams' events
-        if (p->dbg_bucket_skip_side && i > 0) continue;
-        if (hipStreamWaitEvent((hipStream_t)stream, p->ev_bucket[k][i], 0) != hipSuccess) return (int)hipGetLastError();
-        ++n;
-      }
-  return n ? SV_OK : SV_E_STATE;
+  return p->side.bucket_wait(bucket, (hipStream_t)stream);
 }
 
-// per-plan test hooks: "side_delay_us" (hold the first side-stream launch of every step back by that long), "bucket_skip_side" (sv_lgvae_bucket_wait
-// drops the side streams' events: the negative control of the bucket-dependency test).  Deliberately an explicit call on one plan, not an environment
-// variable: nothing a training job inherits can switch them on.
+// per-plan test hooks (SideStreams::debug)
 extern "C" int sv_lgvae_plan_debug(sv_lgvae_plan* p, const char* key, int64_t value) {
   if (!p || !key) return SV_E_BADARG;
-  if (!strcmp(key, "side_delay_us")) { if (value < 0 || value > 1000000) return SV_E_BADARG; p->dbg_side_delay_us = (int)value; return SV_OK; }
-  if (!strcmp(key, "bucket_skip_side")) { p->dbg_bucket_skip_side = value != 0; return SV_OK; }
-  return SV_E_BADARG;
+  return p->side.debug(key, value);
+}
+
+// test hook: the dz state machine of the latent block (plan_latent.h) as plain integers; no device call
+extern "C" int sv_lgvae_dz_transition(int32_t state, int32_t event, int32_t slab_path, int32_t* next, int32_t* zero_range) {
+  if (state < 0 || state > 3 || event < 0 || event > 3 || !next || !zero_range) return SV_E_BADARG;
+  const DzStep t = dz_transition((DzState)state, (DzEvent)event, slab_path != 0);
+  *next = (int32_t)t.next;
+  *zero_range = (int32_t)t.zero;
+  return SV_OK;
 }
 
 extern "C" int sv_lgvae_graph_count(const sv_lgvae_plan* p) {
@@ -1497,55 +1264,25 @@ extern "C" int sv_lgvae_graph_count(const sv_lgvae_plan* p) {
 
 extern "C" int sv_lgvae_profile_enable(sv_lgvae_plan* p, int32_t enable) {
   if (!p) return SV_E_BADARG;
-  p->prof_on = enable != 0;
-  if (enable) {
-    for (auto& pe : p->pending) { p->event_pool.push_back(pe.a); p->event_pool.push_back(pe.b); }
-    p->pending.clear();
-    p->prof.clear();
-    p->profidx.clear();
-  }
+  p->prof.enable(enable != 0);
   return SV_OK;
 }
 
 extern "C" int sv_lgvae_profile_filter(sv_lgvae_plan* p, const char* name) {
   if (!p) return SV_E_BADARG;
-  p->prof_filter = name ? name : "";
+  p->prof.filter = name ? name : "";
   return SV_OK;
 }
 
 extern "C" int sv_lgvae_profile_read(sv_lgvae_plan* p, int32_t max_entries, char names[][64], double* total_ms,
                                      int32_t* launches, double* flops_per_launch, double* bytes_per_launch) {
   if (!p) return SV_E_BADARG;
-  for (auto& pe : p->pending) {
-    (void)hipEventSynchronize(pe.b);
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, pe.a, pe.b) == hipSuccess) {
-      p->prof[pe.entry].total_ms += ms;
-      p->prof[pe.entry].launches += 1;
-    }
-    p->event_pool.push_back(pe.a);
-    p->event_pool.push_back(pe.b);
-  }
-  p->pending.clear();
-  int n = (int)p->prof.size();
-  if (n > max_entries) n = max_entries;
-  for (int i = 0; i < n; ++i) {
-    if (names) snprintf(names[i], 64, "%s", p->prof[i].name.c_str());
-    if (total_ms) total_ms[i] = p->prof[i].total_ms;
-    if (launches) launches[i] = p->prof[i].launches;
-    if (flops_per_launch) flops_per_launch[i] = p->prof[i].flops;
-    if (bytes_per_launch) bytes_per_launch[i] = p->prof[i].bytes;
-  }
-  return n;
+  return p->prof.read(max_entries, names, total_ms, launches, flops_per_launch, bytes_per_launch);
 }
 
-// FLOPs per launch the scope's chosen algorithm really multiplies (polyphase forms: fewer than the direct count flops_per_launch), same order as sv_lgvae_profile_read
 extern "C" int sv_lgvae_profile_read_issued(sv_lgvae_plan* p, int32_t max_entries, double* issued_flops_per_launch) {
   if (!p || !issued_flops_per_launch) return SV_E_BADARG;
-  int n = (int)p->prof.size();
-  if (n > max_entries) n = max_entries;
-  for (int i = 0; i < n; ++i) issued_flops_per_launch[i] = p->prof[i].issued;
-  return n;
+  return p->prof.read_issued(max_entries, issued_flops_per_launch);
 }
 
 extern "C" const char* sv_version(void) { return "splitvae-hip 0.1 (gfx950)"; }

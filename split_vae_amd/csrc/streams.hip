@@ -36,6 +36,17 @@ hipStream_t sv_shared_stream(int k) {
   return d.s[k];
 }
 
+// The cross-stream dependency every fork / join of the library is made of: *ev is created on first use (timing disabled; its owner destroys it) and recorded on
+// `from`.  false: the failing HIP call's status is what hipGetLastError() returns next.
+bool sv_event_record(hipEvent_t* ev, hipStream_t from) {
+  if (!*ev && hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) return false;
+  return hipEventRecord(*ev, from) == hipSuccess;
+}
+// ... and `to` waits for it
+bool sv_event_handoff(hipEvent_t* ev, hipStream_t from, hipStream_t to) {
+  return sv_event_record(ev, from) && hipStreamWaitEvent(to, *ev, 0) == hipSuccess;
+}
+
 extern "C" int sv_side_stream(int32_t index, void** stream) {
   if (!stream) return SV_E_BADARG;
   *stream = nullptr;

@@ -1015,8 +1015,7 @@ hipStream_t lane_stream(sv_tape* t, int lane, hipStream_t st) {
 }
 int lanes_fork(sv_tape* t, hipStream_t st) {             // every lane behind what the caller's stream holds now (a single-lane tape: nothing)
   if (t->nlanes < 2) return SV_OK;
-  if (!t->ev_fork && hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
-  if (hipEventRecord(t->ev_fork, st) != hipSuccess) return (int)hipGetLastError();
+  if (!sv_event_record(&t->ev_fork, st)) return (int)hipGetLastError();
   for (int l = 1; l < t->nlanes; ++l) {
     hipStream_t s = lane_stream(t, l, st);
     if (s != st && hipStreamWaitEvent(s, t->ev_fork, 0) != hipSuccess) return (int)hipGetLastError();
@@ -1027,8 +1026,7 @@ int lanes_join(sv_tape* t, hipStream_t st) {             // the caller's stream 
   for (int l = 1; l < t->nlanes; ++l) {
     hipStream_t s = lane_stream(t, l, st);
     if (s == st) continue;
-    if (!t->ev_join[l] && hipEventCreateWithFlags(&t->ev_join[l], hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
-    if (hipEventRecord(t->ev_join[l], s) != hipSuccess || hipStreamWaitEvent(st, t->ev_join[l], 0) != hipSuccess) return (int)hipGetLastError();
+    if (!sv_event_handoff(&t->ev_join[l], s, st)) return (int)hipGetLastError();
   }
   return SV_OK;
 }
@@ -1046,10 +1044,7 @@ int run_pass(sv_tape* t, int pass, const sv_tape_run_args* a, bool with_grad, hi
     else if (e - b > 1 && !s.per_part) SV_TRY(group_backward(t, b, e, q));
     else
       for (size_t i = e; i-- > b;) SV_TRY(node_backward(t, i, a, s.part == SV_TAPE_PART_ALL ? PART_ALL : 1 << (s.part - 1), s.lane, q));
-    if (s.records) {
-      if (!ev[k] && hipEventCreateWithFlags(&ev[k], hipEventDisableTiming) != hipSuccess) return (int)hipGetLastError();
-      if (hipEventRecord(ev[k], q) != hipSuccess) return (int)hipGetLastError();
-    }
+    if (s.records && !sv_event_record(&ev[k], q)) return (int)hipGetLastError();
   }
   return lanes_join(t, st);
 }

@@ -127,10 +127,10 @@ def test_replay_sees_a_changed_learning_rate(ops):
 
 
 def test_replay_restores_the_host_flags_the_phases_leave_behind(ops):
-    """a replayed graph must leave the plan's host-side flags (dz_slabs, gz_zero_skipped, dz_valid, nll_fused, gz_clean) as
-    the captured phases left them -- they select which buffer the next phase's reparam_kl_bwd reads.  Scenario: whole training steps (the
-    slab path is live, the dz slabs hold a real gradient), then a REPLAYED forward-only call followed by an EAGER encoder backward without
-    the decoders' (the KL terms' gradient only, vae/trainer.py:12-13).  With stale flags that backward reads the heads' forward slabs as dz.
+    """a replayed graph must leave the plan's host-side state (the latent block's DzState of csrc/plan_latent.h -- zeroed, stale,
+    in gz_*, in slabs -- and nll_fused) as the captured phases left it -- it selects which buffer the next phase's reparam_kl_bwd reads.  Scenario: whole
+    training steps (the slab path is live, the dz slabs hold a real gradient: InSlabs), then a REPLAYED forward-only call (Stale) followed by an EAGER encoder
+    backward without the decoders' (the KL terms' gradient only, vae/trainer.py:12-13).  With the state of before the replay that backward reads the heads' forward slabs as dz.
     The encoder_x_hat head-bias gradients have a closed form in z_mean / z_sig."""
     from split_vae_amd import data
     from split_vae_amd._lib import PHASE_ALL, PHASE_PREP, PHASE_FORWARD, PHASE_LOSS, PHASE_BWD_ENC_HEADS, PHASE_BWD_ENC_CONVS

@@ -476,3 +476,32 @@ def test_encoder_head_adjoint_at_small_sigma(lib_built):
         if not err <= 1e-4 * top:
             bad.append((v, err / top))
     assert not bad, bad
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("switches,bitwise", [({}, True), ({"SV_NO_LATENT_GEMM_F32": "1"}, False)], ids=["slabs", "accumulating"])
+def test_second_backward_over_one_forward_recomputes_dz(lib_built, switches, bitwise):
+    """LOSS, BWD_DECODERS, BWD_ENC_HEADS | BWD_ENC_CONVS twice over ONE forward (fp32, B = 8, 32 x 32, latents 128 / 128, after two warm-up steps; a fresh
+    process per case, tests/second_backward_probe.py, so that the switches are read fresh): the second backward recomputes dL/dz of the decoders instead of adding
+    to the first one's, whatever state the latent block's host state machine (csrc/plan_latent.h: DzState) is in.
+    slabs: the default switches -- d1's input gradient is left as K-slice slabs (InSlabs; the re-zero of gz_* is issued and unused).  The fp32 step has no atomics
+    there: the two gradient sets are bitwise equal (so they were in the parent commit of the state machine, 08c7130, measured with this probe).
+    accumulating: SV_NO_LATENT_GEMM_F32=1, the im2col kernel's split-K atomics add into gz_* (InGz), where a missed re-zero doubles dz and moves the encoders'
+    gradients by order 1.  The atomics reorder fp32 sums (parent and this commit: 4.2e-7 of a tensor's maximum at most), so every gradient tensor is held within 2e-3 of
+    its own maximum, DESIGN section 2's gradient bar."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "second_backward_probe.py")], capture_output=True, text=True,
+                       env=dict(os.environ, **switches), cwd=root, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("SECOND_BACKWARD ")][-1].split(" ", 1)[1])
+    worst = max(res["per"].items(), key=lambda kv: kv[1][0] / max(kv[1][1], 1e-30))
+    print("second backward:", switches, "bitwise", res["bitwise"], "worst", worst)
+    assert res["finite"] and len(res["per"]) == 40
+    for name, (diff, gmax) in res["per"].items():
+        assert gmax > 0, name
+        assert diff <= 2e-3 * gmax, (name, diff, gmax)
+    if bitwise:
+        assert res["bitwise"]
