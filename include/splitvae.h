@@ -902,6 +902,54 @@ int sv_latent_info_lse(const float* z, int32_t ldz, const float* mu, int32_t ldm
 int sv_latent_info_finish(const double* own, const double* prior, const double* lse, int32_t N, int32_t Ll, double* out /* [8] */,
                           void* stream);
 
+/* ---------------------------------------------------------------- per-dimension latent report (csrc/latent_dims.hip)
+ * No reference counterpart.  Which dimensions of a latent block carry anything (Burda et al. 2016: active units) and Chen et al.
+ * 2018's decomposition of the block's KL term into index-code MI, total correlation and dimension-wise KL, from scores under the
+ * per-dimension aggregate posterior q_j(z_j) = 1/N sum_n q(z_j | x_n).  One block of width L per call (a column range of the
+ * arrays of sv_latent_info_draw, addressed by base pointer and row pitch), N images, one sample z_i per image: the bits
+ * sv_latent_info_draw writes.  fp32 inputs, ALL FINITE, sig > 0, taken exactly.
+ *   lc_nj    = -log sig_nj - 1/2 log(2 pi): fp32, (float)(-(double)logf(sig) - 1/2 log 2 pi); an INPUT of sv_latent_dims_lse;
+ *   e_inj    = lc_nj - 1/2 ((z_ij - mu_nj) * rsig_nj)^2 in this DIRECT form in fp32: subtract, multiply, square, then one rounding
+ *              of lc - 0.5 * square.  Only non-negative terms, as in sv_latent_info_lse;
+ *   lse_ij   = logsumexp_n e_inj - log Nr;
+ *   own_ij   = lc_ij - 1/2 eps_ij^2 (fp64, from the fp32 lc: the rounding of lc cancels in own - lse);
+ *   prior_ij = -1/2 log(2 pi) - 1/2 z_ij^2 (fp64);
+ *   per dimension  mean_j, var_j: the mean and the POPULATION variance of mu_.j over the images (fp64, two passes); a dimension
+ *              is active when var_j > 0.01 (Burda et al.'s threshold: the caller's comparison);
+ *              KL_j = mean_i [1/2 (mu_ij^2 + sig_ij^2 - 1) - log sig_ij]: the closed form, fp64 throughout;
+ *              MI_j = mean_i (own_ij - lse_ij), dwKL_j = mean_i (lse_ij - prior_ij), mlse_j = mean_i lse_ij;
+ *   per block  TC = mean_i lse_block_i - sum_j mlse_j (= mean_i (lse_block_i - sum_j lse_ij)), lse_block: row 0 (z_g) or 1 (z_l) of
+ *              sv_latent_info_lse on the same z; dwKL = sum_j dwKL_j.  With KL and MI of sv_latent_info_finish on the same draws
+ *              KL = MI + TC + dwKL holds term by term (the sums telescope).  Every MI-type figure saturates at log N.
+ * sv_latent_dims_prepare: mu, sig [N, L] (pitches ldm, lds) -> lc [N, L] fp32 (ldc), own [N, L] fp64 (dense) and cols [3, L] fp64 =
+ *   (mean_j, var_j, KL_j).  eps [N, L] (lde) pins the draw; NULL: the Philox stream of sv_latent_info_draw at (seed, sample_offset + i,
+ *   block: 0 global / 1 local, j), the same numbers that call drew.  Column sums: one workgroup per dimension, thread t takes the
+ *   images t, t + 256, ... in ascending order, then the 256 partial sums are added in thread order.  No atomics.
+ * sv_latent_dims_lse: queries z [Nq, L] (ldz) against the references mu, rsig, lc [Nr, L] (ldm, ldr, ldc) -> lse [Nq, L] fp64 (row
+ *   pitch ldl).  Nq and Nr are independent.  The references are cut into chunks of sv_latent_dims_chunk_rows() rows; within a chunk
+ *   they are pushed onto a per-(query, dimension) running (max, sum) in groups of 8 consecutive rows (the group's maximum, one
+ *   rescale of the sum, then one exponential per element, added in row order); one fp32 (max, sum) per (query, chunk, dimension)
+ *   is left in the workspace (sv_latent_dims_workspace_bytes; 16-byte aligned; may hold anything on entry) and a merge kernel folds
+ *   them in chunk order in fp64.  The Nq x Nr x L scores never exist in memory.  No atomics.  lse_ij depends on row i of z and
+ *   column j of the references only: the same inputs give the same bits wherever the query row or the column sits.
+ * sv_latent_dims_finish: lse [N, L] (ldl), own [N, L] (dense), z [N, L] (ldz), lse_block [N] -> out [3 L + 2] fp64 = (MI_j [L],
+ *   dwKL_j [L], mlse_j [L], TC, dwKL).  The means in the fixed order of sv_latent_dims_prepare's column sums; TC and dwKL add
+ *   the dimensions in ascending order.
+ * Everything is enqueued on `stream`; no host synchronisation.  Accepted domain: 1 <= L <= 512, N, Nq, Nr >= 1 (Nr at most 65535
+ * chunks), row pitches >= L, block 0 or 1, sample_offset >= 0: anything else SV_E_UNSUPPORTED; a null pointer (eps may be NULL) or
+ * a misaligned one (4 bytes; fp64 arrays 8; workspace 16): SV_E_BADARG; workspace_bytes below sv_latent_dims_workspace_bytes:
+ * SV_E_WORKSPACE.  All checked before anything is enqueued. */
+int sv_latent_dims_chunk_rows(void);
+int sv_latent_dims_workspace_bytes(int32_t Nq, int32_t Nr, int32_t L, int64_t* bytes);
+int sv_latent_dims_prepare(const float* mu, int32_t ldm, const float* sig, int32_t lds, const float* eps /* or NULL */, int32_t lde,
+                           float* lc, int32_t ldc, double* own /* [N,L] */, double* cols /* [3,L] */, int32_t N, int32_t L,
+                           int32_t block, uint64_t seed, int64_t sample_offset, void* stream);
+int sv_latent_dims_lse(const float* z, int32_t ldz, const float* mu, int32_t ldm, const float* rsig, int32_t ldr, const float* lc,
+                       int32_t ldc, int32_t Nq, int32_t Nr, int32_t L, double* lse, int32_t ldl, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int sv_latent_dims_finish(const double* lse, int32_t ldl, const double* own, const float* z, int32_t ldz, const double* lse_block,
+                          int32_t N, int32_t L, double* out /* [3 L + 2] */, void* stream);
+
 /* ---------------------------------------------------------------- label-free reconstruction quality (csrc/recon_quality.hip)
  * The three decodes of the reference's labelled test step (vae/trainer.py:213-226: the reconstruction, decode(z_x, random z_l) and
  * decode(random z_g, z_x_hat)) scored in image space instead of by the classifier whose weights are missing upstream: mean PSNR and

@@ -294,6 +294,11 @@ SYMBOLS = {
     "sv_latent_info_draw": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _u64, _i64, _vp]),
     "sv_latent_info_lse": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
     "sv_latent_info_finish": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "sv_latent_dims_chunk_rows": (C.c_int, []),
+    "sv_latent_dims_workspace_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
+    "sv_latent_dims_prepare": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _u64, _i64, _vp]),
+    "sv_latent_dims_lse": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp]),
+    "sv_latent_dims_finish": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "sv_recon_window": (None, [C.POINTER(C.c_double)]),
     "sv_recon_quality_workspace_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
     "sv_recon_draw": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _u64, _i64, _vp]),

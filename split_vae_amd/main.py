@@ -4,7 +4,7 @@
     python -m split_vae_amd.main --model gmvae --beta 40 --patch_size 4       (GMVAE baseline, Table 2)
 
 Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, --data_dir, --gm_dropout, --mix_per_image,
---resident_data, --iw_samples, --gm_iw_samples, --knn_probe, --knn_refs, --latent_info, --recon_quality.
+--resident_data, --iw_samples, --gm_iw_samples, --knn_probe, --knn_refs, --latent_info, --recon_quality, --latent_dims.
 """
 import argparse
 
@@ -65,6 +65,11 @@ def build_parser():
                     help="N >= 1: after the report of every evaluation, the mean PSNR and SSIM against the original image, over the first "
                          "N test images, of the reconstruction and of the decodes with z_l, then z_g, drawn from its prior "
                          "(split_vae_amd/recon_quality.py); needs no labels")
+    ap.add_argument("--latent_dims", type=int, default=0,
+                    help="N >= 2: after the report of every evaluation, the per-dimension latent report over the first N test images: "
+                         "active units per block (Burda et al. 2016: variance of the posterior mean over the images above 0.01), the "
+                         "largest per-dimension KL, the total correlation and the dimension-wise KL of Chen et al. 2018's "
+                         "decomposition (split_vae_amd/latent_dims.py); needs no labels")
     return ap
 
 
@@ -145,6 +150,8 @@ def main(argv=None):
     check_latent_info(args.latent_info, args.global_latent_dims, args.local_latent_dims if args.model != 'gmvae' else 0)
     from .recon_quality import check_flags as check_recon_quality
     check_recon_quality(args.recon_quality)
+    from .latent_dims import check_flags as check_latent_dims
+    check_latent_dims(args.latent_dims, args.global_latent_dims, args.local_latent_dims if args.model != 'gmvae' else 0)
     from . import configure_hw_queues
     configure_hw_queues()                            # before the first HIP call (split_vae_amd/__init__.py)
     config = dotdict(vars(args))

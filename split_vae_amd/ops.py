@@ -1064,6 +1064,90 @@ def latent_info_finish(own, prior, lse, Ll, out=None):
     return out
 
 
+# ------------------------------------------------------------------ per-dimension latent report (include/splitvae.h)
+def latent_dims_chunk_rows():
+    return int(_lib.load().sv_latent_dims_chunk_rows())
+
+
+def latent_dims_workspace_bytes(Nq, Nr, L):
+    n = C.c_int64()
+    check(_lib.load().sv_latent_dims_workspace_bytes(int(Nq), int(Nr), int(L), C.byref(n)), "sv_latent_dims_workspace_bytes")
+    return n.value
+
+
+def _dense_f64(t, name, shape, device):
+    if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
+        raise ValueError("%s must be a contiguous %s fp64 tensor on %s" % (name, list(shape), device))
+    return _p(t)
+
+
+def _rows_f64(t, name, shape, device):
+    if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or t.device != device or \
+            t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise ValueError("%s must be a %s fp64 tensor on %s with contiguous rows (a row pitch >= its width is allowed)" %
+                         (name, list(shape), device))
+    return C.c_void_p(t.data_ptr()), int(t.stride(0))
+
+
+def latent_dims_prepare(mu, sig, eps=None, block=0, seed=0, sample_offset=0, out=None):
+    """sv_latent_dims_prepare: mu, sig [N, L] fp32 of ONE block (column views of wider arrays are fine) -> (lc [N,L] fp32, own [N,L]
+    fp64, cols [3,L] fp64 = mean_j, var_j, KL_j).  eps [N,L] pins the draw; otherwise the numbers ops.latent_info_draw drew for
+    (seed, sample_offset + i, block).  out: that 3-tuple, to write into (lc may have a row pitch above its width)."""
+    mp, ldm = _rows_f32(mu, "mu")
+    N, L = mu.shape
+    dev = mu.device
+    sp, lds = _same_rows(sig, "sig", N, L, dev)
+    ep, lde = (None, 0) if eps is None else _same_rows(eps, "eps", N, L, dev)
+    if out is None:
+        out = (torch.empty((N, L), dtype=torch.float32, device=dev), torch.empty((N, L), dtype=torch.float64, device=dev),
+               torch.empty((3, L), dtype=torch.float64, device=dev))
+    lc, own, cols = out
+    cp, ldc = _same_rows(lc, "lc", N, L, dev)
+    op, kp = _dense_f64(own, "own", (N, L), dev), _dense_f64(cols, "cols", (3, L), dev)
+    check(_lib.load().sv_latent_dims_prepare(mp, ldm, sp, lds, ep, lde, cp, ldc, op, kp, N, L, int(block), int(seed), int(sample_offset),
+                                             _stream()), "sv_latent_dims_prepare")
+    return out
+
+
+def latent_dims_lse(z, mu, rsig, lc, lse=None, workspace=None):
+    """sv_latent_dims_lse: lse [Nq, L] fp64, lse_ij = logsumexp_n log q(z_ij | x_n) - log Nr of the queries z [Nq, L] under the
+    references mu, rsig, lc [Nr, L] (fp32; each may have a row pitch above L).  workspace: a uint8 device tensor of at least
+    latent_dims_workspace_bytes(Nq, Nr, L) bytes with any contents (default: allocated here)."""
+    zp, ldz = _rows_f32(z, "z")
+    Nq, L = z.shape
+    Nr = mu.shape[0]
+    dev = z.device
+    mp, ldm = _same_rows(mu, "mu", Nr, L, dev)
+    rp, ldr = _same_rows(rsig, "rsig", Nr, L, dev)
+    cp, ldc = _same_rows(lc, "lc", Nr, L, dev)
+    if lse is None:
+        lse = torch.empty((Nq, L), dtype=torch.float64, device=dev)
+    lp, ldl = _rows_f64(lse, "lse", (Nq, L), dev)
+    nbytes = latent_dims_workspace_bytes(Nq, Nr, L)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous():
+        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    check(_lib.load().sv_latent_dims_lse(zp, ldz, mp, ldm, rp, ldr, cp, ldc, Nq, Nr, L, lp, ldl, _p(ws), ws.numel(), _stream()),
+          "sv_latent_dims_lse")
+    return lse
+
+
+def latent_dims_finish(lse, own, z, lse_block, out=None):
+    """sv_latent_dims_finish: out [3 L + 2] fp64 = (MI_j [L], dwKL_j [L], mean_i lse_ij [L], TC, dwKL) of lse [N,L] (latent_dims_lse
+    with Nq = Nr = N), own [N,L] (latent_dims_prepare), the samples z [N,L] fp32 and lse_block [N] fp64: the block's row of
+    ops.latent_info_lse on the same z."""
+    zp, ldz = _rows_f32(z, "z")
+    N, L = z.shape
+    dev = z.device
+    lp, ldl = _rows_f64(lse, "lse", (N, L), dev)
+    op, bp = _dense_f64(own, "own", (N, L), dev), _dense_f64(lse_block, "lse_block", (N,), dev)
+    if out is None:
+        out = torch.empty((3 * L + 2,), dtype=torch.float64, device=dev)
+    qp = _dense_f64(out, "out", (3 * L + 2,), dev)
+    check(_lib.load().sv_latent_dims_finish(lp, ldl, op, zp, ldz, bp, N, L, qp, _stream()), "sv_latent_dims_finish")
+    return out
+
+
 # ------------------------------------------------------------------ label-free reconstruction quality (include/splitvae.h)
 def recon_window():
     """The 11 fp64 taps of the SSIM window (sigma 1.5, normalised to sum 1) as the kernel uses them."""

@@ -216,6 +216,7 @@ def train_local_global_autoencoder(model, optimizer, dataset, train_dataset, tes
             _knn_probe_report(model, test_dataset, config, step)
             _latent_info_report(model, test_dataset, config, step)
             _recon_quality_report(model, test_dataset, config, step)
+            _latent_dims_report(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             # vae/trainer.py:405-414 resets x_recon / x_kl / total_kl but never the x_hat_* means
             metrics.reset_states(["x_recon_loss", "x_kl_loss", "total_kl_loss"])
@@ -257,6 +258,15 @@ def _recon_quality_report(model, test_dataset, config, step):
         return None
     from . import recon_quality
     return recon_quality.report(model, test_dataset, config, step)
+
+
+def _latent_dims_report(model, test_dataset, config, step):
+    """--latent_dims N: the per-dimension latent report (latent_dims.py) behind an evaluation's report; the figures are kept in
+    config.latent_dims_history: one dict per evaluation."""
+    if int(config.get("latent_dims") or 0) <= 0:
+        return None
+    from . import latent_dims
+    return latent_dims.report(model, test_dataset, config, step)
 
 
 def _gm_iw_report(model, test_dataset, config, step):
@@ -347,6 +357,7 @@ def _train_lggmvae(model, optimizer, train_dataset, test_dataset, config):
             _knn_probe_report(model, test_dataset, config, step)
             _latent_info_report(model, test_dataset, config, step)
             _recon_quality_report(model, test_dataset, config, step)
+            _latent_dims_report(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             acc, n_acc = None, 0
             start = time.time()
@@ -406,6 +417,7 @@ def _train_gmvae(model, optimizer, train_dataset, test_dataset, config):
             _knn_probe_report(model, test_dataset, config, step)
             _latent_info_report(model, test_dataset, config, step)
             _recon_quality_report(model, test_dataset, config, step)
+            _latent_dims_report(model, test_dataset, config, step)
             acc, n_acc = None, 0
             start = time.time()
         if step >= config.training_steps:
