@@ -3,7 +3,10 @@
 text from its label to its function end and its .amdhsa_kernel resource block (VGPR / AGPR / SGPR / LDS / scratch).  Comments and the function
 index inside local labels (.LBB<fn>_<bb>) are not compared: both renumber when another kernel of the file goes away.
 Usage: python scripts/kernel_asm_diff.py OLD_TREE NEW_TREE [WORK_DIR]     (a tree = a checkout, e.g. `git worktree add /tmp/old HEAD^`)
-Prints kernels compared / identical / differing / removed / added with the names; exit status 1 when a kernel differs."""
+Prints kernels compared / identical / differing / removed / added with the names; exit status 1 when a kernel differs.
+A differing kernel is classed further: RENAMED = same resource block and the same opcode sequence (only registers, immediates' homes or
+label targets differ); RESCHEDULED = same resource block and the same opcodes the same number of times, in another order; DIFFERS = anything
+else ("(resources)" when the resource block changed)."""
 import glob, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 
@@ -42,6 +45,18 @@ def kernels(out):
     return found
 
 
+def opcodes(text):
+    """the opcode of every instruction line of a kernel's text, in order (labels and directives dropped)"""
+    return [l.split()[0] for l in text.split("\n") if l.startswith("\t") and l.split() and not l.split()[0].startswith(".")]
+
+
+def classify(old, new):
+    if old[2] != new[2]:
+        return "DIFFERS"
+    a, b = opcodes(old[1]), opcodes(new[1])
+    return "RENAMED" if a == b else "RESCHEDULED" if sorted(a) == sorted(b) else "DIFFERS"
+
+
 if __name__ == "__main__":
     work = sys.argv[3] if len(sys.argv) > 3 else tempfile.mkdtemp(prefix="kernel_asm_diff_")
     both = []
@@ -54,7 +69,12 @@ if __name__ == "__main__":
     removed, added = [n for n in old if n not in new], [n for n in new if n not in old]
     print("kernels: old %d, new %d; compared %d: identical %d, differing %d; removed %d, added %d" %
           (len(old), len(new), len(same) + len(differ), len(same), len(differ), len(removed), len(added)))
-    for tag, names, src in (("DIFFERS", differ, new), ("REMOVED", removed, old), ("ADDED", added, new)):
+    kind = {n: classify(old[n], new[n]) for n in differ}
+    print("differing: renamed %d, rescheduled %d, other %d" % tuple(sum(k == t for k in kind.values()) for t in ("RENAMED", "RESCHEDULED", "DIFFERS")))
+    for n in differ:
+        print(kind[n], new[n][0], n, "%d -> %d instructions" % (len(opcodes(old[n][1])), len(opcodes(new[n][1]))),
+              "(resources)" if old[n][2] != new[n][2] else "")
+    for tag, names, src in (("REMOVED", removed, old), ("ADDED", added, new)):
         for n in names:
-            print(tag, src[n][0], n, ("(resources)" if tag == "DIFFERS" and old[n][2] != new[n][2] else ""))
+            print(tag, src[n][0], n)
     sys.exit(1 if differ else 0)

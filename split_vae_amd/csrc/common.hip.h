@@ -125,6 +125,11 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // numerically stable helpers used by the ELBO kernels
 __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x))); }
@@ -169,6 +174,15 @@ struct Philox {
 
 __device__ __forceinline__ float u32_to_unit_open(uint32_t u) {   // (0,1]
   return ((float)(u >> 8) + 1.0f) * (1.0f / 16777216.0f);
+}
+
+// One standard normal per counter (j, image lo, image hi ^ tag, word3): Box-Muller of the block's first two words.  Every Sampling /
+// report stream of the library draws through this layout (j: latent dimension, gs: global image index, tag: stream id, word3: step or sample).
+__device__ __forceinline__ float philox_normal(const Philox& ph, uint32_t j, uint64_t gs, uint32_t tag, uint32_t word3) {
+  uint32_t c[4] = {j, (uint32_t)gs, (uint32_t)(gs >> 32) ^ tag, word3};
+  ph(c);
+  const float u1 = u32_to_unit_open(c[0]), u2 = u32_to_unit_open(c[1]);
+  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
 // Raise a kernel's dynamic-LDS cap (hipFuncAttributeMaxDynamicSharedMemorySize) when a launch needs more than any launch

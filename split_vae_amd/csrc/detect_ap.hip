@@ -10,7 +10,7 @@
 // same bits.  The per-image and per-sprite arithmetic is __host__ __device__: the *_host entries run it without a device.
 #include <math.h>
 
-#include "common.hip.h"
+#include "eval_common.hip.h"
 
 #pragma clang fp contract(off)                     // inter, the areas and the union are individually rounded (also -ffp-contract=off)
 
@@ -215,7 +215,6 @@ int match_check(const float* bbox, int64_t ld_bbox, const float* logits, int64_t
 }
 
 // ---------------------------------------------------------------------------- the curve
-inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
 inline int64_t da_blocks(int64_t n) { return (n + DA_CHUNK - 1) / DA_CHUNK; }
 struct ApLayout { int64_t key[2], tp[2], cnt, mx, sum, total; };
 inline ApLayout ap_layout(int64_t n) {

@@ -7,12 +7,9 @@
 // and per image a streamed log-sum-exp (m, s) of each weight plus the running sum of lw_joint, in fp64.
 // One wave per image, lanes striding the latent dimensions; lane 0 owns the image's state.  No atomics, nothing depends on
 // the launch order: same inputs -> same bits.
-#include "common.hip.h"
+#include "eval_common.hip.h"
 
 namespace {
-
-constexpr uint64_t IW_KEY = 0x1a7e17a11eedULL;     // Philox key constant of this stream (no other kernel of the library uses it)
-constexpr uint32_t IW_TAG = 0x69770000u;           // 'iw' | stream id (0: global latent, 1: local latent)
 
 struct IwArgs {
   const float* z_mean[2]; const float* z_sig[2];   // [B,Lg], [B,Ll]
@@ -24,13 +21,6 @@ struct IwArgs {
   int B, L[2], k, flags;
   uint64_t seed; int64_t sample_offset;
 };
-
-// (m, s) <- (m, s) + exp(lw): m' = max(m, lw), s' = s exp(m - m') + exp(lw - m')
-__device__ __forceinline__ void lse_push(double& m, double& s, double lw) {
-  const double mn = fmax(m, lw);
-  s = s * exp(m - mn) + exp(lw - mn);
-  m = mn;
-}
 
 template <typename TZ>
 __global__ __launch_bounds__(256) void iw_advance_kernel(const IwArgs g) {
@@ -61,15 +51,7 @@ __global__ __launch_bounds__(256) void iw_advance_kernel(const IwArgs g) {
     const int e = jj >= Lg, j = e ? jj - Lg : jj, L = g.L[e];
     const float mu = g.z_mean[e][(int64_t)b * L + j];
     const float sg = g.z_sig[e][(int64_t)b * L + j];
-    float ep;
-    if (g.eps) {
-      ep = g.eps[(int64_t)b * Lc + jj];
-    } else {
-      uint32_t c[4] = {(uint32_t)j, (uint32_t)gs, (uint32_t)(gs >> 32) ^ (IW_TAG + (uint32_t)e), (uint32_t)g.k};
-      ph(c);
-      const float u1 = u32_to_unit_open(c[0]), u2 = u32_to_unit_open(c[1]);
-      ep = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);   // Box-Muller, as reparam_kl_fwd_body
-    }
+    float ep = g.eps ? g.eps[(int64_t)b * Lc + jj] : philox_normal(ph, (uint32_t)j, gs, IW_TAG + (uint32_t)e, (uint32_t)g.k);   // as reparam_kl_fwd_body
     float zz = mu + sg * ep;                       // vae/model.py:13, the expression of reparam_kl_fwd_body
     const TZ zs = from_f32<TZ>(zz);
     z_lp[(int64_t)b * g.ldz + jj] = zs;

@@ -8,12 +8,10 @@
 // in LDS; dimensions past GM_ZCAP are read back from zcat).  Densities: thread (c, s) = (t / S, t % S) sums component c over
 // d = s, s + S, ...; S = min(64, 256 / pow2ceil(n)) adjacent lanes share a component, so one log2(S)-step xor butterfly finishes all
 // 2 n sums together; wave 0 then takes both log-sum-exps over n (two components per lane) in one pass.  No atomics.
-#include "common.hip.h"
+#include "eval_common.hip.h"
 
 namespace {
 
-constexpr uint64_t IW_KEY = 0x1a7e17a11eedULL;     // as csrc/iw.hip: the key constant of the IW stream
-constexpr uint32_t IW_TAG = 0x69770000u;           // 'iw' | stream id (0: global latent, 1: local latent, 2: component pick)
 constexpr int GM_NMAX = 128;                       // mixture components
 constexpr int GM_ZCAP = 2048;                      // dimensions of z_g kept in LDS (8 KB)
 
@@ -26,12 +24,6 @@ struct IwGmArgs {
   int B, n, Lg, Ll, k, flags, lgS;
   uint64_t seed; int64_t sample_offset;
 };
-
-__device__ __forceinline__ void lse_push(double& m, double& s, double lw) {
-  const double mn = fmax(m, lw);
-  s = s * exp(m - mn) + exp(lw - mn);
-  m = mn;
-}
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -107,15 +99,7 @@ __global__ __launch_bounds__(256) void iw_gm_advance_kernel(const IwGmArgs g) {
     const int e = jj >= Lg, j = e ? jj - Lg : jj;
     const float mu = e ? g.z_mean_l[(int64_t)b * Ll + j] : mu_g[j];
     const float sg = e ? g.z_sig_l[(int64_t)b * Ll + j] : sg_g[j];
-    float ep;
-    if (g.eps) {
-      ep = g.eps[(int64_t)b * Lc + jj];
-    } else {
-      uint32_t ctr[4] = {(uint32_t)j, (uint32_t)gs, (uint32_t)(gs >> 32) ^ (IW_TAG + (uint32_t)e), (uint32_t)g.k};
-      ph(ctr);
-      const float u1 = u32_to_unit_open(ctr[0]), u2 = u32_to_unit_open(ctr[1]);
-      ep = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);   // Box-Muller, as reparam_kl_fwd_body
-    }
+    const float ep = g.eps ? g.eps[(int64_t)b * Lc + jj] : philox_normal(ph, (uint32_t)j, gs, IW_TAG + (uint32_t)e, (uint32_t)g.k);   // as reparam_kl_fwd_body
     const TZ zs = from_f32<TZ>(mu + sg * ep);
     z_lp[jj] = zs;
     const float zz = to_f32(zs);                   // every density below is evaluated at the latent the decoder consumes

@@ -13,7 +13,7 @@
 // LDS: operands as [k][m] images with rows of 80 floats (320 B: 16-B aligned; the ds_read_b32 bank is dword % 32 per 32-lane half,
 // a half reads k rows 2 apart in lk = 0 / 1, 80 % 32 = 16: conflict-free; the staging writes put 32 consecutive m of one k row
 // into a half: conflict-free); the distance tile as [m][68] (the accumulator rows lk 4 apart land 16 banks apart).
-#include "common.hip.h"
+#include "eval_common.hip.h"
 
 namespace {
 
@@ -202,7 +202,6 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const KnnArgs g) {
   }
 }
 
-inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
 struct KnnLayout { int64_t nq, nr, d, i, total; int nchunks; };
 inline KnnLayout knn_layout(int64_t Nq, int64_t Nr, int64_t k) {
   KnnLayout w;
@@ -217,7 +216,6 @@ inline KnnLayout knn_layout(int64_t Nq, int64_t Nr, int64_t k) {
 inline bool knn_sizes_ok(int32_t Nq, int32_t Nr, int32_t k) {
   return Nq >= 1 && k >= 1 && k <= KMAX && Nr >= k && (Nr + KNN_CHUNK - 1) / KNN_CHUNK <= 65535;
 }
-inline bool al(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 

@@ -19,17 +19,13 @@
 //   ld_block_kernel   one workgroup: TC and the block's dwKL, the dimensions added in ascending order
 // No atomics; the partial of (query, dimension, chunk) depends on z_ij and column j of the chunk's rows only: the same inputs give
 // the same bits wherever the query row or the column sits.
-#include "common.hip.h"
+#include "eval_common.hip.h"
 
 namespace {
 
-constexpr uint64_t LI_KEY = 0x1a7e27140f0ULL;      // the Philox stream of sv_latent_info_draw (latent_info.hip): eps = NULL must
-constexpr uint32_t LI_TAG = 0x6c690000u;           // reproduce the numbers that call drew
 constexpr int LD_CHUNK = 4096;                     // reference rows per chunk (sv_latent_dims_chunk_rows)
 constexpr int QT = 32, QW = 8, RT = 32, DT = 64, GR = 8;   // queries per workgroup / per wave, rows per tile, dimensions, rows per group
 constexpr int LMAX = 512;
-constexpr double HALF_LOG_2PI = 0.91893853320467274178;
-constexpr float LOG2E = 1.44269504088896340736f;
 
 struct ElemArgs {
   const float* mu; const float* sig; const float* eps;
@@ -44,30 +40,11 @@ __global__ __launch_bounds__(256) void ld_elem_kernel(const ElemArgs g) {
   const int64_t b = idx / g.L;
   const int j = (int)(idx - b * g.L);
   const float sg = g.sig[b * g.lds + j];
-  float ep;
-  if (g.eps) {
-    ep = g.eps[b * g.lde + j];
-  } else {
-    Philox ph(g.seed ^ LI_KEY);
-    const uint64_t gs = (uint64_t)(g.sample_offset + b);
-    uint32_t c[4] = {(uint32_t)j, (uint32_t)gs, (uint32_t)(gs >> 32) ^ (LI_TAG + (uint32_t)g.block), 0u};
-    ph(c);
-    const float u1 = u32_to_unit_open(c[0]), u2 = u32_to_unit_open(c[1]);
-    ep = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
-  }
+  // eps = NULL: the numbers sv_latent_info_draw drew for this image, block and dimension
+  const float ep = g.eps ? g.eps[b * g.lde + j] : LATENT_INFO_EPS(latent_info_stream(g.seed), (uint64_t)(g.sample_offset + b), g.block, j);
   const float lc = (float)(-(double)logf(sg) - HALF_LOG_2PI);
   g.lc[b * g.ldc + j] = lc;
   g.own[idx] = (double)lc - 0.5 * (double)ep * (double)ep;
-}
-
-// the 256 partial sums of a workgroup, added in thread order; every thread adds them alike and gets the total
-__device__ __forceinline__ double block_sum_ordered(double v, double* part) {
-  __syncthreads();                                 // the previous use of `part` is over
-  part[threadIdx.x] = v;
-  __syncthreads();
-  double tot = 0.0;
-  for (int i = 0; i < 256; ++i) tot += part[i];    // every thread adds the same values in the same order
-  return tot;
 }
 
 __global__ __launch_bounds__(256) void ld_cols_kernel(const ElemArgs g) {
@@ -213,14 +190,7 @@ __global__ __launch_bounds__(256) void ld_merge_kernel(const LseArgs g) {
   const int64_t qi = idx / g.L;
   const int j = (int)(idx - qi * g.L);
   double m = -__builtin_inf(), s = 0.0;
-  for (int c = 0; c < g.nchunks; ++c) {
-    const float* w = g.ws + ((qi * g.nchunks + c) * g.L + j) * 2;
-    const double m2 = (double)w[0], s2 = (double)w[1];
-    if (!(s2 > 0.0)) continue;                     // an empty partial: every score of the chunk was -inf
-    const double mn = fmax(m, m2);
-    s = (s > 0.0 ? s * exp(m - mn) : 0.0) + s2 * exp(m2 - mn);
-    m = mn;
-  }
+  for (int c = 0; c < g.nchunks; ++c) lse_fold_partial(m, s, g.ws + ((qi * g.nchunks + c) * g.L + j) * 2);
   g.lse[qi * g.ldl + j] = m + log(s) - log((double)g.Nr);
 }
 
@@ -258,11 +228,9 @@ __global__ __launch_bounds__(256) void ld_block_kernel(const FinArgs g) {
   }
 }
 
-inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
 inline int ld_nchunks(int64_t Nr) { return (int)((Nr + LD_CHUNK - 1) / LD_CHUNK); }
 inline bool ld_sizes_ok(int32_t Nq, int32_t Nr, int32_t L) { return Nq >= 1 && Nr >= 1 && ld_nchunks(Nr) <= 65535 && L >= 1 && L <= LMAX; }
 inline int64_t ld_bytes(int64_t Nq, int64_t Nr, int64_t L) { return up256(Nq * ld_nchunks(Nr) * L * 2 * 4); }
-inline bool al(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 

@@ -17,17 +17,13 @@
 //   li_finish_kernel  one workgroup: the fp64 means, summed in one fixed order
 // No atomics; the partial of (query, chunk) depends on the query row and the chunk's rows only: same inputs -> same bits, wherever
 // the query sits.
-#include "common.hip.h"
+#include "eval_common.hip.h"
 
 namespace {
 
-constexpr uint64_t LI_KEY = 0x1a7e27140f0ULL;      // Philox key constant of this stream (no other kernel of the library uses it)
-constexpr uint32_t LI_TAG = 0x6c690000u;           // 'li' | block (0: global latent, 1: local latent)
 constexpr int LI_CHUNK = 1024;                     // reference rows per chunk (sv_latent_info_chunk_rows)
 constexpr int QT = 64, QW = 16, RT = 64, DK = 32;  // queries per workgroup / per wave, references per pass, dimensions per step
 constexpr int LMAX = 512;
-constexpr double HALF_LOG_2PI = 0.91893853320467274178;
-constexpr float LOG2E = 1.44269504088896340736f;
 
 struct DrawArgs {
   const float* mu; const float* sig; const float* eps;
@@ -36,17 +32,11 @@ struct DrawArgs {
   uint64_t seed; int64_t sample_offset;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void li_draw_kernel(const DrawArgs g) {
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (b >= g.N) return;                            // whole waves leave
-  Philox ph(g.seed ^ LI_KEY);
+  const Philox ph = latent_info_stream(g.seed);
   const uint64_t gs = (uint64_t)(g.sample_offset + b);
   const int Lg = g.Lg, Lc = g.Lg + g.Ll;
   double slog[2] = {0.0, 0.0}, seps[2] = {0.0, 0.0}, sz[2] = {0.0, 0.0};
@@ -54,15 +44,7 @@ __global__ __launch_bounds__(256) void li_draw_kernel(const DrawArgs g) {
     const int e = jj >= Lg, j = e ? jj - Lg : jj;
     const float mu = g.mu[b * g.ldm + jj];
     const float sg = g.sig[b * g.lds + jj];
-    float ep;
-    if (g.eps) {
-      ep = g.eps[b * g.lde + jj];
-    } else {
-      uint32_t c[4] = {(uint32_t)j, (uint32_t)gs, (uint32_t)(gs >> 32) ^ (LI_TAG + (uint32_t)e), 0u};
-      ph(c);
-      const float u1 = u32_to_unit_open(c[0]), u2 = u32_to_unit_open(c[1]);
-      ep = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);   // Box-Muller, as sv_iw_advance
-    }
+    const float ep = g.eps ? g.eps[b * g.lde + jj] : LATENT_INFO_EPS(ph, gs, e, j);
     const float zz = mu + sg * ep;
     g.z[b * g.ldz + jj] = zz;
     g.rsig[b * g.ldr + jj] = 1.f / sg;
@@ -249,14 +231,7 @@ __global__ __launch_bounds__(256) void li_merge_kernel(const LseArgs g) {
   const double logN = log((double)g.Nr);
   for (int t = 0; t < ns; ++t) {
     double m = -__builtin_inf(), s = 0.0;
-    for (int c = 0; c < g.nchunks; ++c) {
-      const float* w = g.ws + ((qi * g.nchunks + c) * 3 + t) * 2;
-      const double m2 = (double)w[0], s2 = (double)w[1];
-      if (!(s2 > 0.0)) continue;                   // an empty partial: every score of the chunk was -inf
-      const double mn = fmax(m, m2);
-      s = (s > 0.0 ? s * exp(m - mn) : 0.0) + s2 * exp(m2 - mn);
-      m = mn;
-    }
+    for (int c = 0; c < g.nchunks; ++c) lse_fold_partial(m, s, g.ws + ((qi * g.nchunks + c) * 3 + t) * 2);
     g.lse[(int64_t)t * g.Nq + qi] = m + log(s) - logN;
   }
 }
@@ -289,12 +264,10 @@ __global__ __launch_bounds__(256) void li_finish_kernel(const double* __restrict
   }
 }
 
-inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
 inline int li_nchunks(int64_t Nr) { return (int)((Nr + LI_CHUNK - 1) / LI_CHUNK); }
 inline bool li_sizes_ok(int32_t Nq, int32_t Nr) { return Nq >= 1 && Nr >= 1 && li_nchunks(Nr) <= 65535; }
 inline bool li_widths_ok(int32_t Lg, int32_t Ll) { return Lg >= 1 && Lg <= LMAX && Ll >= 0 && Ll <= LMAX; }
 inline int64_t li_bytes(int64_t Nq, int64_t Nr) { return up256(Nq * li_nchunks(Nr) * 3 * 2 * 4); }
-inline bool al(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 

@@ -18,7 +18,7 @@
 //   rq_finish_kernel  one workgroup: PSNR_i = 10 log10(1 / max(MSE_i, 1e-10)) in parallel, then one thread adds (PSNR_i, SSIM_i, 1)
 //                     onto acc [3] in image order
 // No atomics, outputs overwritten, the workspace may hold anything on entry: the same inputs give the same bits.
-#include "common.hip.h"
+#include "eval_common.hip.h"
 
 namespace {
 
@@ -29,8 +29,6 @@ constexpr int RQ_TR = 8;                           // output rows per band
 constexpr int RQ_TC = 75, RQ_IN = RQ_TC + RQ_PAD;  // output / input columns per tile: 85 * 3 channels = 255 threads
 constexpr int LMAX = 512, NMAX = 4096;
 constexpr double RQ_C1 = 0.01 * 0.01, RQ_C2 = 0.03 * 0.03, RQ_MSE_FLOOR = 1e-10;
-
-inline bool al(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // ---------------------------------------------------------------- sv_recon_draw
 struct DrawArgs {
@@ -66,15 +64,7 @@ __global__ __launch_bounds__(256) void rq_draw_kernel(const DrawArgs g) {
     const int e = jj >= Lg, j = e ? jj - Lg : jj;
     float v;
     if (e ? draw_l : draw_g) {
-      float ep;
-      if (g.eps) {
-        ep = g.eps[b * g.lde + jj];
-      } else {
-        uint32_t ctr[4] = {(uint32_t)j, (uint32_t)gs, (uint32_t)(gs >> 32) ^ (tag + (uint32_t)e), 0u};
-        ph(ctr);
-        const float u1 = u32_to_unit_open(ctr[0]), u2 = u32_to_unit_open(ctr[1]);
-        ep = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);   // Box-Muller, as sv_iw_advance
-      }
+      const float ep = g.eps ? g.eps[b * g.lde + jj] : philox_normal(ph, (uint32_t)j, gs, tag + (uint32_t)e, 0u);   // as sv_iw_advance
       v = ep;
       if (!e && g.pm) v = g.pm[(int64_t)c * Lg + j] + g.ps[(int64_t)c * Lg + j] * ep;
     } else {
@@ -93,15 +83,9 @@ struct QArgs {
 
 inline int rq_nrb(int H) { return (H - RQ_PAD + RQ_TR - 1) / RQ_TR; }
 inline int rq_nct(int W) { return (W - RQ_PAD + RQ_TC - 1) / RQ_TC; }
-inline int64_t rq_bytes(int64_t B, int H, int W) { return (B * rq_nrb(H) * rq_nct(W) * 2 * 8 + 255) / 256 * 256; }
+inline int64_t rq_bytes(int64_t B, int H, int W) { return up256(B * rq_nrb(H) * rq_nct(W) * 2 * 8); }
 inline bool rq_sizes_ok(int32_t B, int32_t H, int32_t W) {
   return B >= 1 && H >= RQ_WIN && W >= RQ_WIN && H <= 16384 && W <= 16384 && (int64_t)B * rq_nrb(H) * rq_nct(W) <= 0x7fffffffLL;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(256) void rq_tile_kernel(const QArgs g) {

@@ -9,9 +9,10 @@ import math
 
 import torch
 
-from . import ops
+from . import ops, reports
 from ._lib import IW_ACCUMULATE, IW_DRAW, PHASE_FWD_DECODERS, PHASE_FWD_ENCODERS, PHASE_LOSS, PHASE_PREP
 from .model import LGVae
+from .utils import images_of
 
 REFUSAL = ("--iw_samples covers --model lgvae only: for lggmvae / gmvae the prior is the y-conditional mixture and q contains a "
            "relaxed categorical, which needs a different estimator")
@@ -80,7 +81,7 @@ def evaluate(model, batches, K, seed=None):
     acc = torch.zeros((4,), dtype=torch.float64, device=model.device)
     prepped, offset = set(), 0
     for batch in batches:
-        images6 = batch[0] if isinstance(batch, (tuple, list)) else batch
+        images6 = images_of(batch)
         B = images6.shape[0]
         log_likelihood(model, images6, K, seed=seed, sample_offset=offset, acc=acc, prep=B not in prepped)
         prepped.add(B)
@@ -96,6 +97,12 @@ def evaluate(model, batches, K, seed=None):
 
 def report_line(K, res):
     return REPORT.format(int(K), res["iw_joint"], res["iw_x"], res["bits_per_dim_x"])
+
+
+def report(model, test_batches, config, step=None):
+    """--iw_samples K behind an evaluation's report (trainer.py, evaluate.py): prints the line and returns the figures (no history is
+    kept); None when the flag is off or the model is not an LGVae."""
+    return reports.run("iw_samples", model, test_batches, config, step)
 
 
 # ---------------------------------------------------------------- the mixture models: LGGMVae and GMVae (sv_iw_gm_advance)
@@ -197,7 +204,7 @@ def mixture_evaluate(model, batches, K, seed=None):
     acc = torch.zeros((4,), dtype=torch.float64, device=model.device)
     prepped, offset = set(), 0
     for batch in batches:
-        images = batch[0] if isinstance(batch, (tuple, list)) else batch
+        images = images_of(batch)
         B = images.shape[0]
         mixture_log_likelihood(model, images, K, seed=seed, sample_offset=offset, acc=acc, prep=B not in prepped)
         prepped.add(B)
@@ -213,3 +220,9 @@ def mixture_evaluate(model, batches, K, seed=None):
 
 def mixture_report_line(K, res):
     return MIXTURE_REPORT.format(int(K), res["gm_iw_joint"], res["gm_iw_x"], res["gm_bits_per_dim_x"])
+
+
+def mixture_report(model, test_batches, config, step=None):
+    """--gm_iw_samples K behind an evaluation's report: prints the line, keeps dict(step, gm_iw_joint, gm_iw_x, gm_bits_per_dim_x) in
+    config.gm_iw_history and returns the figures; None when the flag is off or the model is an LGVae."""
+    return reports.run("gm_iw_samples", model, test_batches, config, step)

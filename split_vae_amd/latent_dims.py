@@ -14,7 +14,7 @@ z_l; gmvae the z_g figures of lggmvae.
 """
 import torch
 
-from . import ops
+from . import ops, reports
 from ._lib import LATENT_INFO_MAX_L
 from .latent_info import posteriors
 from .model import LGVae
@@ -104,15 +104,4 @@ def report(model, test_batches, config, step=None):
     """--latent_dims N behind an evaluation's report (trainer.py, evaluate.py): prints the line, keeps the figures in
     config.latent_dims_history (one dict(step, ...) per evaluation, the per-dimension lists included) and returns them; None when the
     flag is off."""
-    n = int(config.get("latent_dims") or 0)
-    if n <= 0:
-        return None
-    res = evaluate(model, test_batches, n)
-    if res["n_images"] < n and not config.get("latent_dims_clipped"):
-        print(CLIPPED.format(n, res["n_images"]))
-        config.latent_dims_clipped = True
-    print(report_line(res))
-    if config.get("latent_dims_history") is None:
-        config.latent_dims_history = []
-    config.latent_dims_history.append(dict(res, step=step))
-    return res
+    return reports.run("latent_dims", model, test_batches, config, step)

@@ -13,9 +13,10 @@ mixture); gmvae the MI of z_g only.
 """
 import torch
 
-from . import ops
+from . import ops, reports
 from ._lib import LATENT_INFO_MAX_L, PHASE_FWD_ENCODERS, PHASE_PREP
 from .model import LGVae
+from .utils import images_of
 
 REPORT = 'Test latent information ({} images, log N = {:.4f}): z_g '
 CLIPPED = 'Note: --latent_info {} clipped to the test set\'s {} images'
@@ -66,7 +67,7 @@ def posteriors(model, batches, n=None):
     for batch in batches:
         if n is not None and have >= n:
             break
-        images = batch[0] if isinstance(batch, (tuple, list)) else batch
+        images = images_of(batch)
         mg, sg, ml, sl = batch_posterior(model, images)
         Lg, Ll = int(mg.shape[1]), (0 if ml is None else int(ml.shape[1]))
         take = images.shape[0] if n is None else min(images.shape[0], n - have)
@@ -121,15 +122,4 @@ def report_line(res):
 def report(model, test_batches, config, step=None):
     """--latent_info N behind an evaluation's report (trainer.py, evaluate.py): prints the line, keeps the figures in
     config.latent_info_history (one dict(step, ...) per evaluation) and returns them; None when the flag is off."""
-    n = int(config.get("latent_info") or 0)
-    if n <= 0:
-        return None
-    res = evaluate(model, test_batches, n)
-    if res["n_images"] < n and not config.get("latent_info_clipped"):
-        print(CLIPPED.format(n, res["n_images"]))
-        config.latent_info_clipped = True
-    print(report_line(res))
-    if config.get("latent_info_history") is None:
-        config.latent_info_history = []
-    config.latent_info_history.append(dict(res, step=step))
-    return res
+    return reports.run("latent_info", model, test_batches, config, step)

@@ -8,6 +8,7 @@ Extra flags (not in the reference): --synthetic, --dtype, --seed, --log_every, -
 """
 import argparse
 
+from . import reports
 from .utils import dotdict
 
 
@@ -45,31 +46,7 @@ def build_parser():
     ap.add_argument("--resident_data", action="store_true",
                     help="hold the on-disk dataset in device memory (SVHN as uint8, CelebA as fp32) and fetch, scramble and stage each "
                          "batch in one kernel from a host-side index list; same batches, same permutations, same losses")
-    ap.add_argument("--iw_samples", type=int, default=0,
-                    help="K > 0: after the report of every evaluation, the K-sample importance-weighted bound of the test log-likelihood "
-                         "(joint and x-only, nats) and the bits per dimension of x (split_vae_amd/iw.py); --model lgvae only")
-    ap.add_argument("--gm_iw_samples", type=int, default=0,
-                    help="K > 0: after the report of every evaluation, the K-sample importance-weighted bound of the mixture models' "
-                         "test log-likelihood, y marginalised (split_vae_amd/iw.py: mixture_evaluate); --model lggmvae / gmvae only")
-    ap.add_argument("--knn_probe", type=int, default=0,
-                    help="K > 0: after the report of every evaluation, the accuracy of a K-nearest-neighbour classifier of the test "
-                         "set's latent means over --knn_refs training images, for z_g and z_l separately (split_vae_amd/probe.py); "
-                         "needs labels; K <= 32")
-    ap.add_argument("--knn_refs", type=int, default=20000,
-                    help="--knn_probe: the number of reference images, the first N of the training set in file order")
-    ap.add_argument("--latent_info", type=int, default=0,
-                    help="N >= 2: after the report of every evaluation, the aggregate-posterior information report over the first N "
-                         "test images: per latent block the KL term split into index-code mutual information and marginal KL, and the "
-                         "mutual information of z_g and z_l (split_vae_amd/latent_info.py); needs no labels")
-    ap.add_argument("--recon_quality", type=int, default=0,
-                    help="N >= 1: after the report of every evaluation, the mean PSNR and SSIM against the original image, over the first "
-                         "N test images, of the reconstruction and of the decodes with z_l, then z_g, drawn from its prior "
-                         "(split_vae_amd/recon_quality.py); needs no labels")
-    ap.add_argument("--latent_dims", type=int, default=0,
-                    help="N >= 2: after the report of every evaluation, the per-dimension latent report over the first N test images: "
-                         "active units per block (Burda et al. 2016: variance of the posterior mean over the images above 0.01), the "
-                         "largest per-dimension KL, the total correlation and the dimension-wise KL of Chen et al. 2018's "
-                         "decomposition (split_vae_amd/latent_dims.py); needs no labels")
+    reports.add_arguments(ap)                        # the evaluation reports: --iw_samples ... --latent_dims (reports.py)
     return ap
 
 
@@ -141,17 +118,7 @@ def make_model(model_name, config, input_shape):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    from .iw import check_mixture_model_name, check_model_name
-    check_model_name(args.model, args.iw_samples)    # before any data or device work
-    check_mixture_model_name(args.model, args.gm_iw_samples)
-    from .probe import check_flags
-    check_flags(args.knn_probe, args.knn_refs, args.no_label)
-    from .latent_info import check_flags as check_latent_info
-    check_latent_info(args.latent_info, args.global_latent_dims, args.local_latent_dims if args.model != 'gmvae' else 0)
-    from .recon_quality import check_flags as check_recon_quality
-    check_recon_quality(args.recon_quality)
-    from .latent_dims import check_flags as check_latent_dims
-    check_latent_dims(args.latent_dims, args.global_latent_dims, args.local_latent_dims if args.model != 'gmvae' else 0)
+    reports.check_all(args)                          # before any data or device work
     from . import configure_hw_queues
     configure_hw_queues()                            # before the first HIP call (split_vae_amd/__init__.py)
     config = dotdict(vars(args))

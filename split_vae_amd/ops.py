@@ -51,6 +51,14 @@ def _p(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _workspace(nbytes, workspace, device):
+    """The caller's scratch tensor, or a fresh one of nbytes: a contiguous uint8 device tensor with any contents (the library checks its size)."""
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=device) if workspace is None else workspace
+    if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous():
+        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    return ws
+
+
 # ------------------------------------------------------------------ A1 scramble (augmentation.py:43-57)
 def random_perm(B, n_patch, seed, step=0, sample_offset=0, device="cuda", out=None):
     """out: an int32 buffer of at least B * n_patch elements to write instead of a fresh one (the rest of it is not touched)"""
@@ -604,10 +612,7 @@ def detect_ap_finish(rec_key, rec_tp, n_gt, n_records=None, workspace=None, out=
     assert rec_key.dtype == torch.int64 and rec_tp.dtype == torch.int16 and n_gt.dtype == torch.int32
     n = int(rec_key.numel() if n_records is None else n_records)
     assert 1 <= n <= min(rec_key.numel(), rec_tp.numel())
-    nbytes = detect_ap_workspace_bytes(n)
-    if workspace is None:
-        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=rec_key.device)
-    assert workspace.dtype == torch.uint8
+    workspace = _workspace(detect_ap_workspace_bytes(n), workspace, rec_key.device)
     if out is None:
         out = torch.empty((DETECT_AP_OUT,), dtype=torch.float64, device=rec_key.device)
     assert out.dtype == torch.float64 and out.numel() == DETECT_AP_OUT
@@ -975,10 +980,7 @@ def knn_classify(q, r, r_class, k, n_class, q_class=None, acc=None, want_neighbo
     pred = torch.empty((Nq,), dtype=torch.int32, device=q.device)
     nn_i = torch.empty((Nq, int(k)), dtype=torch.int32, device=q.device) if want_neighbours else None
     nn_d = torch.empty((Nq, int(k)), dtype=torch.float32, device=q.device) if want_neighbours else None
-    nbytes = knn_workspace_bytes(Nq, Nr, k)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=q.device) if workspace is None else workspace
-    if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous():
-        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    ws = _workspace(knn_workspace_bytes(Nq, Nr, k), workspace, q.device)
     check(_lib.load().sv_knn_classify(qp, ldq, rp, ldr, rc, Nq, Nr, L, int(k), int(n_class), _p(nn_i), _p(nn_d), _p(pred), qc, _p(acc),
                                       _p(ws), ws.numel(), _stream()), "sv_knn_classify")
     return (pred, nn_i, nn_d) if want_neighbours else pred
@@ -1042,10 +1044,7 @@ def latent_info_lse(z, mu, rsig, cst, Lg, lse=None, workspace=None):
         lse = torch.empty((3, Nq), dtype=torch.float64, device=dev)
     if lse.dtype != torch.float64 or tuple(lse.shape) != (3, Nq) or not lse.is_contiguous() or lse.device != dev:
         raise ValueError("lse must be a contiguous [3,%d] fp64 device tensor" % Nq)
-    nbytes = latent_info_workspace_bytes(Nq, Nr)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if workspace is None else workspace
-    if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous():
-        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    ws = _workspace(latent_info_workspace_bytes(Nq, Nr), workspace, dev)
     check(_lib.load().sv_latent_info_lse(zp, ldz, mp, ldm, rp, ldr, _p(cst), Nq, Nr, int(Lg), Lc - int(Lg), _p(lse), _p(ws), ws.numel(),
                                          _stream()), "sv_latent_info_lse")
     return lse
@@ -1123,10 +1122,7 @@ def latent_dims_lse(z, mu, rsig, lc, lse=None, workspace=None):
     if lse is None:
         lse = torch.empty((Nq, L), dtype=torch.float64, device=dev)
     lp, ldl = _rows_f64(lse, "lse", (Nq, L), dev)
-    nbytes = latent_dims_workspace_bytes(Nq, Nr, L)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if workspace is None else workspace
-    if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous():
-        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    ws = _workspace(latent_dims_workspace_bytes(Nq, Nr, L), workspace, dev)
     check(_lib.load().sv_latent_dims_lse(zp, ldz, mp, ldm, rp, ldr, cp, ldc, Nq, Nr, L, lp, ldl, _p(ws), ws.numel(), _stream()),
           "sv_latent_dims_lse")
     return lse
@@ -1217,10 +1213,7 @@ def recon_quality(a, b, off_a=0, off_b=0, clip_b=True, per_image=None, workspace
         per_image = torch.empty((B, 2), dtype=torch.float64, device=a.device)
     if per_image.dtype != torch.float64 or tuple(per_image.shape) != (B, 2) or not per_image.is_contiguous() or per_image.device != a.device:
         raise ValueError("per_image must be a contiguous [%d,2] fp64 device tensor" % B)
-    nbytes = recon_quality_workspace_bytes(B, H, W)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=a.device) if workspace is None else workspace
-    if ws.dtype != torch.uint8 or not ws.is_cuda or not ws.is_contiguous():
-        raise ValueError("workspace must be a contiguous uint8 device tensor")
+    ws = _workspace(recon_quality_workspace_bytes(B, H, W), workspace, a.device)
     check(_lib.load().sv_recon_quality(ap, pa, int(off_a), bp, pb, int(off_b), int(bool(clip_b)), B, H, W, _p(per_image), _p(ws), ws.numel(),
                                        _stream()), "sv_recon_quality")
     return per_image

@@ -8,8 +8,9 @@ k it has no parameters.  lgvae and lggmvae report both latents, gmvae z_g only.
 """
 import torch
 
-from . import ops
+from . import ops, reports
 from ._lib import KNN_MAX_K
+from .utils import images_of
 
 REPORT = 'Test k-NN probe (k={}, {} refs): z_g acc {:.4f}'
 REPORT_L = ', z_l acc {:.4f}'
@@ -42,7 +43,7 @@ def latent_means(model, batches):
     batch of one probe at the same counter.  Leaves model._calls alone."""
     zg, zl = [], []
     for batch in batches:
-        images = batch[0] if isinstance(batch, (tuple, list)) else batch
+        images = images_of(batch)
         g, l = _means(model, images)
         zg.append(g.clone())
         if l is not None:
@@ -101,3 +102,9 @@ def reference_batches(train_ds, n, augmentor, batch_size):
 def report_line(res):
     line = REPORT.format(res["k"], res["n_ref"], res["acc_g"])
     return line + (REPORT_L.format(res["acc_l"]) if res.get("acc_l") is not None else '')
+
+
+def report(model, test_batches, config, step=None):
+    """--knn_probe K behind an evaluation's report (trainer.py, evaluate.py): prints the line, keeps dict(step, knn_acc_g, knn_acc_l) in
+    config.knn_history and returns knn_probe's figures; None when the flag is off, the run has no labels or config.knn_ref_batches is empty."""
+    return reports.run("knn_probe", model, test_batches, config, step)

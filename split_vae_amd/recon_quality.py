@@ -23,9 +23,10 @@ Definitions (include/splitvae.h: sv_recon_draw / sv_recon_quality / sv_recon_fin
 """
 import torch
 
-from . import ops
+from . import ops, reports
 from ._lib import PHASE_FWD_DECODERS, PHASE_PREP, RECON_KEEP_G, RECON_KEEP_L, RECON_MEANS
 from .latent_info import batch_posterior
+from .utils import images_of
 
 REPORT = 'Test reconstruction quality ({} images): '
 FIGURES = 'PSNR {:.2f} dB, SSIM {:.4f}'
@@ -67,7 +68,7 @@ def evaluate(model, test_batches, n, eps=None, seed=None, comp=None):
     for batch in test_batches:
         if have >= n:
             break
-        images = batch[0] if isinstance(batch, (tuple, list)) else batch
+        images = images_of(batch)
         B, H, W = images.shape[:3]
         take = min(B, n - have)
         mg, _, ml, _ = batch_posterior(model, images)
@@ -107,15 +108,4 @@ def report_line(res):
 def report(model, test_batches, config, step=None):
     """--recon_quality N behind an evaluation's report (trainer.py, evaluate.py): prints the line, keeps the figures in
     config.recon_quality_history (one dict(step, ...) per evaluation) and returns them; None when the flag is off."""
-    n = int(config.get("recon_quality") or 0)
-    if n <= 0:
-        return None
-    res = evaluate(model, test_batches, n)
-    if res["n_images"] < n and not config.get("recon_quality_clipped"):
-        print(CLIPPED.format(n, res["n_images"]))
-        config.recon_quality_clipped = True
-    print(report_line(res))
-    if config.get("recon_quality_history") is None:
-        config.recon_quality_history = []
-    config.recon_quality_history.append(dict(res, step=step))
-    return res
+    return reports.run("recon_quality", model, test_batches, config, step)

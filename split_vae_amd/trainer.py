@@ -11,7 +11,7 @@ from datetime import datetime
 
 import torch
 
-from . import dist as svdist
+from . import dist as svdist, reports
 from ._lib import (PHASE_ADAM, PHASE_ALL, PHASE_BUCKET_EVENTS, PHASE_BWD_DECODERS, PHASE_BWD_ENC_CONVS, PHASE_BWD_ENC_HEADS,
                    PHASE_FORWARD, PHASE_INPUTS_STAGED, PHASE_LOSS, PHASE_NO_RECON, PHASE_PREP)
 from .model import LGVae
@@ -210,13 +210,7 @@ def train_local_global_autoencoder(model, optimizer, dataset, train_dataset, tes
                                   te["x_recon_loss"], te["x_kl_loss"], te["x_recon_loss"] + te["x_kl_loss"],
                                   te["x_hat_recon_loss"], te["x_hat_kl_loss"], te["x_hat_recon_loss"] + te["x_hat_kl_loss"],
                                   tr["total_kl_loss"], te["total_kl_loss"]))
-            if int(config.get("iw_samples") or 0) > 0:
-                from . import iw
-                print(iw.report_line(config.iw_samples, iw.evaluate(model, test_dataset, config.iw_samples)))
-            _knn_probe_report(model, test_dataset, config, step)
-            _latent_info_report(model, test_dataset, config, step)
-            _recon_quality_report(model, test_dataset, config, step)
-            _latent_dims_report(model, test_dataset, config, step)
+            reports.run_all(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             # vae/trainer.py:405-414 resets x_recon / x_kl / total_kl but never the x_hat_* means
             metrics.reset_states(["x_recon_loss", "x_kl_loss", "total_kl_loss"])
@@ -225,63 +219,6 @@ def train_local_global_autoencoder(model, optimizer, dataset, train_dataset, tes
             print('Training done!')
             break
     return _save(model, RUN_NAME)
-
-
-def _knn_probe_report(model, test_dataset, config, step):
-    """--knn_probe K: the k-NN label probe of the latent means (probe.py) behind an evaluation's report.  The loops return the path
-    of the saved weights, so the figures are kept in config.knn_history: one dict(step, knn_acc_g, knn_acc_l) per evaluation."""
-    k = int(config.get("knn_probe") or 0)
-    if k <= 0 or not config.label or not config.get("knn_ref_batches"):
-        return None
-    from . import probe
-    res = probe.knn_probe(model, config.knn_ref_batches, test_dataset, k)
-    print(probe.report_line(res))
-    if config.get("knn_history") is None:
-        config.knn_history = []
-    config.knn_history.append(dict(step=step, knn_acc_g=res["acc_g"], knn_acc_l=res["acc_l"]))
-    return res
-
-
-def _latent_info_report(model, test_dataset, config, step):
-    """--latent_info N: the aggregate-posterior information report (latent_info.py) behind an evaluation's report; the figures are
-    kept in config.latent_info_history: one dict per evaluation."""
-    if int(config.get("latent_info") or 0) <= 0:
-        return None
-    from . import latent_info
-    return latent_info.report(model, test_dataset, config, step)
-
-
-def _recon_quality_report(model, test_dataset, config, step):
-    """--recon_quality N: the label-free reconstruction quality report (recon_quality.py) behind an evaluation's report; the figures
-    are kept in config.recon_quality_history: one dict per evaluation."""
-    if int(config.get("recon_quality") or 0) <= 0:
-        return None
-    from . import recon_quality
-    return recon_quality.report(model, test_dataset, config, step)
-
-
-def _latent_dims_report(model, test_dataset, config, step):
-    """--latent_dims N: the per-dimension latent report (latent_dims.py) behind an evaluation's report; the figures are kept in
-    config.latent_dims_history: one dict per evaluation."""
-    if int(config.get("latent_dims") or 0) <= 0:
-        return None
-    from . import latent_dims
-    return latent_dims.report(model, test_dataset, config, step)
-
-
-def _gm_iw_report(model, test_dataset, config, step):
-    """--gm_iw_samples K: the mixture models' importance-weighted bound (iw.mixture_evaluate) behind an evaluation's report; the
-    figures are kept in config.gm_iw_history: one dict(step, gm_iw_joint, gm_iw_x, gm_bits_per_dim_x) per evaluation."""
-    k = int(config.get("gm_iw_samples") or 0)
-    if k <= 0:
-        return None
-    from . import iw
-    res = iw.mixture_evaluate(model, test_dataset, k)
-    print(iw.mixture_report_line(k, res))
-    if config.get("gm_iw_history") is None:
-        config.gm_iw_history = []
-    config.gm_iw_history.append(dict(step=step, **{key: res[key] for key in iw.MIXTURE_HISTORY_KEYS}))
-    return res
 
 
 def _save(model, run_name):
@@ -353,11 +290,7 @@ def _train_lggmvae(model, optimizer, train_dataset, test_dataset, config):
                       '{}Y KL loss: {:.4f}'.format(tag, v[0], tag, v[1], tag, v[2], tag, v[3], tag, v[4]))
             if cluster is not None:
                 print('            Classifier cluster acc: {:.4f}'.format(cluster.result()))
-            _gm_iw_report(model, test_dataset, config, step)
-            _knn_probe_report(model, test_dataset, config, step)
-            _latent_info_report(model, test_dataset, config, step)
-            _recon_quality_report(model, test_dataset, config, step)
-            _latent_dims_report(model, test_dataset, config, step)
+            reports.run_all(model, test_dataset, config, step)
             _write_grids(model, test_dataset, config, os.path.join("output", RUN_NAME), step)
             acc, n_acc = None, 0
             start = time.time()
@@ -413,11 +346,7 @@ def _train_gmvae(model, optimizer, train_dataset, test_dataset, config):
             if cluster is not None:
                 print('            Classifier cluster acc: {:.4f}'.format(cluster.result()))
             print('            Y KL train loss: {:.4f}, Y KL test loss: {:.4f}'.format(tr[2], te[2]))
-            _gm_iw_report(model, test_dataset, config, step)
-            _knn_probe_report(model, test_dataset, config, step)
-            _latent_info_report(model, test_dataset, config, step)
-            _recon_quality_report(model, test_dataset, config, step)
-            _latent_dims_report(model, test_dataset, config, step)
+            reports.run_all(model, test_dataset, config, step)
             acc, n_acc = None, 0
             start = time.time()
         if step >= config.training_steps:
