@@ -1178,6 +1178,55 @@ int sv_tape_tensor_info(const sv_tape* t, int32_t id, int64_t* offset, int64_t* 
 int sv_tape_loss_info(const sv_tape* t, int64_t* out_offset, int64_t* metric_offset, int32_t* n_loss);
 int sv_tape_run(sv_tape* t, const sv_tape_run_args* args, void* stream);
 
+/* ---------------------------------------------------------------- k-means cluster report of the latents (csrc/kmeans.hip)
+ * No reference counterpart: the unsupervised companion of the k-NN probe.  Lloyd's k-means on x [N, L] fp32 (row pitch ldx), R
+ * independent restarts in one pass, k-means++ seeding.  ALL INPUTS ARE FINITE.
+ *   norm, distance  exactly sv_knn_classify's: n(v) per row in that fixed order; d(x, c) = max(0, (n(x) + n(c)) - 2 (x . c)), fp32
+ *                operations in that order, the dot product over the whole of L in ascending order on v_mfma_f32_16x16x4_f32 (L
+ *                zero-padded, no split over L, no atomics): d is bit-identical wherever the row or the centroid sits;
+ *   assignment   a_i = the centroid smallest under the total order (d, centroid index): equal fp32 distances go to the lower index;
+ *                the padded columns of a tile never win;
+ *   seeding      k-means++ as an exponential race, per restart r.  Philox4x32-10 with the key seed ^ 0x1a7e3c105fe5 and the tag
+ *                'km' << 16: the first centre is the row (uint64(w) * N) >> 32, w the first word at counter (0, r, 0, tag).  With m_i
+ *                the fp32 distance of row i to the nearest centre chosen so far, centre k >= 1 is the row smallest under (key_i, i),
+ *                key_i = -logf(u_i) / m_i in fp32, u_i in (0, 1] from the first word at counter (i, r, k, tag) (((w >> 8) + 1) 2^-24),
+ *                key_i = +inf where m_i = 0; all keys +inf: row 0.  P(i) is proportional to m_i (the D^2 rule); the pick is an argmin
+ *                under a total order and does not depend on the grid.  A centre is a copy of its row;
+ *   update       per cluster count_k (int32) and sum_k in fp64 in one fixed order that depends on N and sv_kmeans_chunk_rows() alone:
+ *                a chunk is 8 runs of sv_kmeans_chunk_rows() / 8 rows; the rows of a run in ascending order, the runs of a chunk in
+ *                ascending order, then the chunks in ascending order.  c_k = (float)(sum_k / count_k); an
+ *                empty cluster keeps its centroid.  No floating-point atomics;
+ *   fit          from centroids C_0, for t = 0, 1, ...: assign against C_t; stop if t > 0 and no assignment changed, or if t == T;
+ *                otherwise update to C_{t+1}.  assign, counts and inertia are those of the last assign pass and the centroids are the
+ *                ones that pass was made against.  inertia = sum_i d(x_i, c_{a_i}), the fp32 distances summed in fp64 in a fixed order
+ *                (the rows of a 64-row tile ascending, then the tiles: lane l of a wave takes the tiles l, l + 64, ..., then the lanes
+ *                in lane order).  n_iter = the t at which the restart stopped.  Past a fixed point an iteration reproduces the same
+ *                bits, so a converged restart rides along until every restart has converged: only its n_iter is frozen.  From then on
+ *                the launches of the fit return at once;
+ *   best         the restart with the lowest inertia, ties to the lower r.
+ * sv_kmeans_seed: centroids [R, K, L] fp32 <- the K centres of every restart; picks [R, K] int32 (may be NULL) <- their rows.
+ * sv_kmeans_iterate: resume = 0 starts a fit at the given centroids: one assign pass (t = 0), then `iters` times update + assign, so
+ *   T = iters; resume = 1 continues the fit whose centroids / assign / counts / n_iter / state the previous call left, with `iters`
+ *   more update + assign steps: calls in groups give the bits of one call with the total.  iters = 0, resume = 0: one assign pass.
+ *   centroids [R, K, L] in-out; assign [R, N] int32; counts [R, K] int32; inertia [R] fp64; n_iter [R] int32; state [2 R + 1]
+ *   int32 (per restart: passes made, converged; then the number of converged restarts), written by resume = 0.
+ * sv_kmeans_best: best [1] int32.  sv_contingency: counts [Ka, Kb] int32 += the pairs (a_i, b_i) of two int32 label vectors [N]
+ *   (integer atomics; a label outside its range is skipped).
+ * The workspace (sv_kmeans_workspace_bytes; 16-byte aligned) may hold anything on entry.  Everything is enqueued on `stream`; no host
+ * synchronisation.  Accepted domain: 1 <= L <= 512, 2 <= K <= 64, 1 <= R <= 16, K <= N < 2^24, ldx >= L, iters >= 0, resume 0 / 1;
+ * sv_contingency: N >= 1, 1 <= Ka, Kb <= 64: anything else SV_E_UNSUPPORTED; a null pointer (picks may be NULL) or a misaligned one
+ * (4 bytes; fp64 8; workspace 16): SV_E_BADARG; workspace_bytes below sv_kmeans_workspace_bytes: SV_E_WORKSPACE.  All checked before
+ * anything is enqueued. */
+int sv_kmeans_chunk_rows(void);     /* rows per chunk of the segmented sum */
+int sv_kmeans_workspace_bytes(int32_t N, int32_t L, int32_t K, int32_t R, int64_t* bytes);
+int sv_kmeans_seed(const float* x, int32_t ldx, int32_t N, int32_t L, int32_t K, int32_t R, uint64_t seed, float* centroids,
+                   int32_t* picks /* [R,K] or NULL */, void* workspace, int64_t workspace_bytes, void* stream);
+int sv_kmeans_iterate(const float* x, int32_t ldx, int32_t N, int32_t L, int32_t K, int32_t R, int32_t iters, int32_t resume,
+                      float* centroids, int32_t* assign, int32_t* counts, double* inertia, int32_t* n_iter, int32_t* state,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int sv_kmeans_best(const double* inertia, int32_t R, int32_t* best, void* stream);
+int sv_contingency(const int32_t* a, const int32_t* b, int32_t N, int32_t Ka, int32_t Kb, int32_t* counts /* ADDED to */, void* stream);
+
 /* ---- K16 data-parallel gradient exchange: absent in the reference (single device) -----------
  * One process per GPU; gradients of the batch-mean loss (vae/trainer.py:13,:127-128,:137) are averaged over equal
  * shards by an in-place all-reduce(sum) of the flat fp32 gradient buffer; 1/world is sv_adam_step's grad_scale.

@@ -15,6 +15,8 @@ constexpr uint64_t IW_KEY = 0x1a7e17a11eedULL;     // sv_iw_advance / sv_iw_gm_a
 constexpr uint32_t IW_TAG = 0x69770000u;           // 'iw' | stream id (0: global latent, 1: local latent, 2: component pick)
 constexpr uint64_t LI_KEY = 0x1a7e27140f0ULL;      // sv_latent_info_draw; sv_latent_dims_prepare with eps = NULL reproduces its numbers
 constexpr uint32_t LI_TAG = 0x6c690000u;           // 'li' | block (0: global latent, 1: local latent)
+constexpr uint64_t KM_KEY = 0x1a7e3c105fe5ULL;     // sv_kmeans_seed: the first centre and the race keys of k-means++
+constexpr uint32_t KM_TAG = 0x6b6d0000u;           // 'km'
 
 // The eps sv_latent_info_draw draws for dimension j of latent block `block` of image `image` (sample_offset + row), ph = latent_info_stream(seed).
 // A macro and not a function around philox_normal: the second level of inlining changes li_draw_kernel's register allocation.

@@ -986,6 +986,67 @@ def knn_classify(q, r, r_class, k, n_class, q_class=None, acc=None, want_neighbo
     return (pred, nn_i, nn_d) if want_neighbours else pred
 
 
+# ------------------------------------------------------------------ k-means cluster report of the latents (include/splitvae.h)
+def kmeans_chunk_rows():
+    return int(_lib.load().sv_kmeans_chunk_rows())
+
+
+def kmeans_workspace_bytes(N, L, K, R):
+    n = C.c_int64()
+    check(_lib.load().sv_kmeans_workspace_bytes(int(N), int(L), int(K), int(R), C.byref(n)), "sv_kmeans_workspace_bytes")
+    return n.value
+
+
+def kmeans_seed(x, K, R, seed=0, want_picks=False, workspace=None):
+    """sv_kmeans_seed: the k-means++ centres of R restarts of x [N,L] -> centroids [R,K,L] fp32 (and picks [R,K] int32, their rows)."""
+    xp, ldx = _rows_f32(x, "x")
+    N, L = x.shape
+    cent = torch.empty((int(R), int(K), L), dtype=torch.float32, device=x.device)
+    picks = torch.empty((int(R), int(K)), dtype=torch.int32, device=x.device) if want_picks else None
+    ws = _workspace(kmeans_workspace_bytes(N, L, K, R), workspace, x.device)
+    check(_lib.load().sv_kmeans_seed(xp, ldx, N, L, int(K), int(R), int(seed) & (2 ** 64 - 1), _p(cent), _p(picks), _p(ws), ws.numel(),
+                                     _stream()), "sv_kmeans_seed")
+    return (cent, picks) if want_picks else cent
+
+
+def kmeans_state(x, centroids):
+    """The in-out buffers of a fit of x [N,L] from centroids [R,K,L]: dict(centroids (the tensor given: written in place), assign [R,N]
+    int32, counts [R,K] int32, inertia [R] fp64, n_iter [R] int32, state [2R + 1] int32), for kmeans_iterate."""
+    R, K, L = centroids.shape
+    if centroids.dtype != torch.float32 or not centroids.is_cuda or not centroids.is_contiguous() or L != x.shape[1]:
+        raise ValueError("centroids must be a contiguous [R,K,%d] fp32 device tensor" % x.shape[1])
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=x.device)      # noqa: E731
+    return dict(centroids=centroids, assign=e((R, x.shape[0]), torch.int32), counts=e((R, K), torch.int32), inertia=e((R,), torch.float64),
+                n_iter=e((R,), torch.int32), state=e((2 * R + 1,), torch.int32))
+
+
+def kmeans_iterate(x, fit, iters, resume=False, workspace=None):
+    """sv_kmeans_iterate on the buffers of kmeans_state: resume False starts the fit at fit["centroids"] (one assign pass, then `iters`
+    update + assign steps), True continues it by `iters` more.  Nothing is read back."""
+    xp, ldx = _rows_f32(x, "x")
+    N, L = x.shape
+    R, K, _ = fit["centroids"].shape
+    ws = _workspace(kmeans_workspace_bytes(N, L, K, R), workspace, x.device)
+    check(_lib.load().sv_kmeans_iterate(xp, ldx, N, L, K, R, int(iters), int(bool(resume)), _p(fit["centroids"]), _p(fit["assign"]),
+                                        _p(fit["counts"]), _p(fit["inertia"]), _p(fit["n_iter"]), _p(fit["state"]), _p(ws), ws.numel(),
+                                        _stream()), "sv_kmeans_iterate")
+    return fit
+
+
+def kmeans_best(inertia, out=None):
+    best = torch.empty((1,), dtype=torch.int32, device=inertia.device) if out is None else out
+    check(_lib.load().sv_kmeans_best(_p(inertia), inertia.numel(), _p(best), _stream()), "sv_kmeans_best")
+    return best
+
+
+def contingency(a, b, counts):
+    """counts [Ka,Kb] int32 (accumulated into) += the pairs (a_i, b_i) of two int32 label vectors (sv_contingency)."""
+    if a.dtype != torch.int32 or b.dtype != torch.int32 or counts.dtype != torch.int32 or a.numel() != b.numel() or counts.dim() != 2:
+        raise ValueError("contingency takes two int32 label vectors of one length and an int32 [Ka,Kb] table")
+    check(_lib.load().sv_contingency(_p(a), _p(b), a.numel(), counts.shape[0], counts.shape[1], _p(counts), _stream()), "sv_contingency")
+    return counts
+
+
 # ------------------------------------------------------------------ aggregate-posterior information report (include/splitvae.h)
 def latent_info_chunk_rows():
     return int(_lib.load().sv_latent_info_chunk_rows())
