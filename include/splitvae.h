@@ -1227,6 +1227,51 @@ int sv_kmeans_iterate(const float* x, int32_t ldx, int32_t N, int32_t L, int32_t
 int sv_kmeans_best(const double* inertia, int32_t R, int32_t* best, void* stream);
 int sv_contingency(const int32_t* a, const int32_t* b, int32_t N, int32_t Ka, int32_t Kb, int32_t* counts /* ADDED to */, void* stream);
 
+/* ---------------------------------------------------------------- linear label probe of the latents (csrc/linprobe.hip)
+ * No reference counterpart: the linear companion of the k-NN probe.  Softmax regression of the classes y [N] uint8 on the rows of
+ * x [N, L] fp32 (row pitch ldx), fitted by Boehning's fixed-Hessian majorise-minimise step.  ALL INPUTS ARE FINITE.  With A = [x 1]
+ * (N x (L + 1)), W [(L + 1), C] fp64 (row L is the bias) and W32 its fp32 rounding, a row whose class is >= C takes no part (its
+ * residual and its loss are 0; the divisor stays N):
+ *   logits       z_i = x_i . W32[:L] + W32[L]: the dot product over the whole of L in ascending order on v_mfma_f32_16x16x4_f32 (L
+ *                zero-padded, no split over L, no atomics -- sv_knn_classify's rule), then one fp32 addition of the bias;
+ *   softmax      in fp32: m = max_c z_c; e_c = expf(z_c - m); s = sum_c e_c in ascending c; p_c = e_c / s; r_c = p_c - [c == y_i];
+ *                loss_i = logf(s) - (z_y - m);
+ *   chunk sums   a chunk is sv_linprobe_chunk_rows() consecutive rows.  A^T M of a chunk (M = the residuals R, or A itself) is summed in
+ *                fp32 on the same MFMA, the reduction dimension being the chunk's rows in ascending order; the chunks are folded in fp64
+ *                in ascending chunk order.  The order depends on N and sv_linprobe_chunk_rows() alone.  No floating-point atomics;
+ *   loss         loss_t = (sum_i loss_i) / N + (l2 / 2) sum W[:L]^2, both sums in fp64: the fp32 loss_i of a 64-row tile in ascending
+ *                row order, then thread u of 256 takes the tiles u, u + 256, ... in ascending order, then the threads in ascending order;
+ *                the squares W_e^2 (e the flat index over [L, C]) likewise: thread u takes e = u, u + 256, ..., then the threads in order;
+ *   gradient     G = (A^T R) / N + l2 W on the rows < L, (A^T R) / N on the bias row: fp64 after the chunk fold; gmax_t = max |G|;
+ *   step         W <- W - P G in fp64: per element sum_j P[i][j] G[j][c] from 0 in ascending j (a product, then an addition), then
+ *                one subtraction.  P is the caller's: (A^T A / (2 N) + diag(l2 .. l2, 0))^-1 makes the step Boehning's, which never
+ *                increases the objective;
+ *   fit          from W_0, for t = 0 .. T: logits, softmax, loss_t, G, gmax_t against W_t; stop if t == T; otherwise step to W_{t+1}.
+ * sv_linprobe_gram: S [(L + 1), (L + 1)] fp64 <- A^T A (not divided by N) by the chunk sums above; the upper triangle is computed
+ *   and mirrored, so S is symmetric bit for bit.
+ * sv_linprobe_fit: resume = 0 starts at the given W and the trajectory index 0 and makes `iters` steps (T = iters; iters = 0: one
+ *   evaluation pass).  resume = 1 continues the fit whose W / state the previous call left with `iters` more steps: it makes the last
+ *   pass again (the same bits at the same index), then goes on; calls in groups give the bits of one call with the total.  W in-out;
+ *   loss, gmax [T_total + 1] fp64: the trajectories; grad [(L + 1), C] fp64 (may be NULL) <- the G of the last pass; state [1] int32:
+ *   the index of the next trajectory element, written by resume = 0.
+ * sv_linprobe_predict: pred [Nq] int32 <- the first maximum of the same logits of q [Nq, L] (ties to the lower class); acc [2] int64
+ *   (may be NULL) += (hits, Nq), the hits only with q_class (integer atomics); loss [1] fp64 (may be NULL; needs q_class) <- the mean
+ *   of loss_i by the same formulas and fold.
+ * The workspace (sv_linprobe_workspace_bytes; 16-byte aligned) may hold anything on entry.  Everything is enqueued on `stream`; no
+ * host synchronisation.  Accepted domain: 1 <= L <= 512, 2 <= C <= 64, 1 <= N < 2^24, ldx >= L, iters >= 0, resume 0 / 1, l2 >= 0 and
+ * finite: anything else SV_E_UNSUPPORTED; a null pointer (grad, q_class, acc and loss of predict may be NULL; loss without q_class may
+ * not) or a misaligned one (4 bytes; fp64 and acc 8; workspace 16): SV_E_BADARG; workspace_bytes below sv_linprobe_workspace_bytes:
+ * SV_E_WORKSPACE.  All checked before anything is enqueued. */
+int sv_linprobe_chunk_rows(void);     /* rows per fp32 partial of A^T M */
+int sv_linprobe_workspace_bytes(int32_t N, int32_t L, int32_t C, int64_t* bytes);   /* covers gram, fit and predict of these sizes */
+int sv_linprobe_gram(const float* x, int32_t ldx, int32_t N, int32_t L, double* S, void* workspace, int64_t workspace_bytes, void* stream);
+int sv_linprobe_fit(const float* x, int32_t ldx, const uint8_t* y, int32_t N, int32_t L, int32_t C, const double* P, double l2,
+                    int32_t iters, int32_t resume, double* W, double* loss, double* gmax, double* grad /* or NULL */, int32_t* state,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int sv_linprobe_predict(const float* q, int32_t ldq, int32_t Nq, int32_t L, int32_t C, const double* W, int32_t* pred,
+                        const uint8_t* q_class /* or NULL */, int64_t* acc /* ADDED to, or NULL */, double* loss /* or NULL */,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- K16 data-parallel gradient exchange: absent in the reference (single device) -----------
  * One process per GPU; gradients of the batch-mean loss (vae/trainer.py:13,:127-128,:137) are averaged over equal
  * shards by an in-place all-reduce(sum) of the flat fp32 gradient buffer; 1/world is sv_adam_step's grad_scale.

@@ -1047,6 +1047,78 @@ def contingency(a, b, counts):
     return counts
 
 
+# ------------------------------------------------------------------ linear label probe of the latents (include/splitvae.h)
+def linprobe_chunk_rows():
+    return int(_lib.load().sv_linprobe_chunk_rows())
+
+
+def linprobe_workspace_bytes(N, L, n_class):
+    n = C.c_int64()
+    check(_lib.load().sv_linprobe_workspace_bytes(int(N), int(L), int(n_class), C.byref(n)), "sv_linprobe_workspace_bytes")
+    return n.value
+
+
+def _f64(t, shape, name):
+    if not torch.is_tensor(t) or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be a contiguous fp64 device tensor of shape %s" % (name, tuple(shape)))
+    return t
+
+
+def linprobe_gram(x, workspace=None):
+    """sv_linprobe_gram: S [(L+1),(L+1)] fp64 = A^T A of A = [x 1], x [N,L] fp32 (not divided by N; symmetric bit for bit)."""
+    xp, ldx = _rows_f32(x, "x")
+    N, L = x.shape
+    S = torch.empty((L + 1, L + 1), dtype=torch.float64, device=x.device)
+    ws = _workspace(linprobe_workspace_bytes(N, L, 2), workspace, x.device)
+    check(_lib.load().sv_linprobe_gram(xp, ldx, N, L, _p(S), _p(ws), ws.numel(), _stream()), "sv_linprobe_gram")
+    return S
+
+
+def linprobe_state(x, n_class, total_iters, W=None):
+    """The in-out buffers of a fit of x [N,L] over `total_iters` steps in all: dict(W [(L+1),C] fp64 (zeros, or the tensor given: written
+    in place), loss / gmax [total_iters + 1] fp64, grad [(L+1),C] fp64, state [1] int32), for linprobe_fit."""
+    L = x.shape[1]
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=x.device)      # noqa: E731
+    W = torch.zeros((L + 1, int(n_class)), dtype=torch.float64, device=x.device) if W is None else _f64(W, (L + 1, int(n_class)), "W")
+    return dict(W=W, loss=e((int(total_iters) + 1,), torch.float64), gmax=e((int(total_iters) + 1,), torch.float64),
+                grad=e((L + 1, int(n_class)), torch.float64), state=e((1,), torch.int32))
+
+
+def linprobe_fit(x, y, P, fit, iters, l2, resume=False, workspace=None):
+    """sv_linprobe_fit on the buffers of linprobe_state: resume False starts at fit["W"] and the trajectory index 0 and makes `iters`
+    steps W <- W - P G, True continues by `iters` more.  y [N] uint8 class ids, P [(L+1),(L+1)] fp64.  Nothing is read back."""
+    xp, ldx = _rows_f32(x, "x")
+    N, L = x.shape
+    n_class = fit["W"].shape[1]
+    yp = _classes_u8(y, N, "y")
+    _f64(P, (L + 1, L + 1), "P")
+    _f64(fit["W"], (L + 1, n_class), "W")
+    ws = _workspace(linprobe_workspace_bytes(N, L, n_class), workspace, x.device)
+    check(_lib.load().sv_linprobe_fit(xp, ldx, yp, N, L, n_class, _p(P), float(l2), int(iters), int(bool(resume)), _p(fit["W"]),
+                                      _p(fit["loss"]), _p(fit["gmax"]), _p(fit["grad"]), _p(fit["state"]), _p(ws), ws.numel(), _stream()),
+          "sv_linprobe_fit")
+    return fit
+
+
+def linprobe_predict(q, W, q_class=None, acc=None, want_loss=False, workspace=None):
+    """sv_linprobe_predict: pred [Nq] int32 = the first maximum of the logits of q [Nq,L] under W [(L+1),C] fp64.  q_class [Nq] uint8
+    and acc [2] int64 (device): acc += (hits, Nq), without q_class the count only.  want_loss (needs q_class): returns (pred, loss
+    [1] fp64, the mean cross-entropy)."""
+    qp, ldq = _rows_f32(q, "q")
+    Nq, L = q.shape
+    n_class = W.shape[1] if torch.is_tensor(W) and W.dim() == 2 else 0
+    _f64(W, (L + 1, n_class), "W")
+    qc = None if q_class is None else _classes_u8(q_class, Nq, "q_class")
+    if acc is not None and (acc.dtype != torch.int64 or not acc.is_cuda or not acc.is_contiguous() or acc.numel() < 2):
+        raise ValueError("acc must be a contiguous int64 device tensor of >= 2 elements")
+    pred = torch.empty((Nq,), dtype=torch.int32, device=q.device)
+    loss = torch.empty((1,), dtype=torch.float64, device=q.device) if want_loss else None
+    ws = _workspace(linprobe_workspace_bytes(Nq, L, n_class), workspace, q.device)
+    check(_lib.load().sv_linprobe_predict(qp, ldq, Nq, L, n_class, _p(W), _p(pred), qc, _p(acc), _p(loss), _p(ws), ws.numel(), _stream()),
+          "sv_linprobe_predict")
+    return (pred, loss) if want_loss else pred
+
+
 # ------------------------------------------------------------------ aggregate-posterior information report (include/splitvae.h)
 def latent_info_chunk_rows():
     return int(_lib.load().sv_latent_info_chunk_rows())
