@@ -5,13 +5,17 @@ against a traced run in a child process (the knob is read once per process).
 
 Beyond the values, every call checks the header's buffer contract: write-only outputs are prefilled with NaN and must come back with
 their pad channels [C, r8(C)) exactly zero and the channels beyond r8(C) untouched or zero; accumulators (dw, dbias, the fp32-atomic dx)
-are prefilled with a non-zero pattern and must come back as pattern + gradient; refused calls leave every buffer as it was."""
+are prefilled with a non-zero pattern and must come back as pattern + gradient; refused calls leave every buffer as it was.
+
+Every case runs its whole call sequence on two input families (tests/conv_ref.py).  Gaussian: the tolerances below, and on top of them the
+derived per-element `gauss_bound` against the reference that rounds where the form rounds.  Integer: small integer operands, for which fp32
+accumulation is exact in any order -- real channels are compared BIT FOR BIT with the float64 reference cast once to the output type,
+accumulators with prefill + gradient (the sign of a zero aside: a sum of signed zeros has no order-independent sign).  BOUND_NOT_BITS names
+the forms that round an intermediate the lemma does not cover; they are compared by the bound, on both families."""
 import ctypes as C
-import math
 import os
 import subprocess
 import sys
-import zlib
 from collections import namedtuple
 
 import numpy as np
@@ -20,6 +24,9 @@ import torch
 import torch.nn.functional as F
 
 from oracle import torch_ref
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import conv_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -37,6 +44,24 @@ FORMS = {
     "dgrad_lowres": {"lowres_row", "lowres_polyd", "lowres_unsupported"},
     "wgrad": {"wgrad_tile", "wgrad_tile_f32", "wgrad_roll", "wgrad_e1", "wgrad_e2", "polyc_wgrad", "poly_wgrad", "wgrad_im2col"},
     "wgrad_poly": {"wgrad_tile", "wgrad_p5"},
+}
+
+# what a call must return: the float64 reference with the form's rounding points, |a| . |b| of the same contraction, its length n, the folds S on top
+# of it (gauss_bound), whether the output is typed bf16, whether the form rounds mid-chain, and a bound added on top (a composed first stage)
+Exp = namedtuple("Exp", "ref ab n S out_bf16 two_stage extra")
+# forms that contract the LOW-RES tensor with composite polyphase weights (combined in fp32, then converted once): no staged hi-res pixel
+COMPOSITE = {"poly_ws", "poly_atomic", "polyc", "lowres_polyd", "polyc_wgrad", "poly_wgrad", "wgrad_p5", "wgrad_poly"}
+POLY_HEAD_FWD = {"poly_ws", "poly_atomic"}
+SPLIT_FORMS = {"dense_splitk", "conv_splitk", "atomic_splitk"}
+# S of gauss_bound.  A composite weight is at most 3 x 3 products cy cx w, two roundings each, summed (9 more), its border terms fold twice more and
+# the staged lines carry their lerp: 32 covers it.  Split-K forwards, the atomic input gradient and the weight-gradient slabs / m-split atomics fold at
+# most 64 partial sums onto an element (svg_choose_splitk: at most 512 workgroups over at least 8 tiles; SV_POLY_WGRAD_NWG slabs go through a tree).
+S_COMPOSITE, S_SPLIT = 32, 64
+# Forms compared by the bound and not by bits on the integer family: each rounds an intermediate whose value the lemma does not cover.
+BOUND_NOT_BITS = {
+    ("dgrad_lowres", "lowres_row", "bf16"): "the row-ring kernel's fused epilogue rounds the hi-res gradient to bf16 before the resize adjoint "
+                                            "(adj2x_row_bf16 reads packed bf16): a sum of up to 36 x 64 integer products need not fit 8 bits",
+    ("dgrad + sv_upsample2x_bwd", "per_class", "bf16"): "dgrad stores the hi-res gradient as bf16, sv_upsample2x_bwd reads it: the same rounding point",
 }
 
 # name, B, H, W, Cin, Cout, KH, KW, stride, act, dtype, ldx (0: r8(Cin)), ldy (0: r8(Cout), or Cout with y_f32), y_f32, ups_in,
@@ -184,25 +209,19 @@ class Layer:
     """one case: seeded operands (P distinct images; image b = scale_b * image b % P, scale_b a power of two so that rounding commutes
     with it), device tensors, prepared weights and the fp64 references"""
 
-    SCALES = (1.0, 2.0, 0.5, 4.0)
+    SCALES = R.SCALES
 
-    def __init__(self, c, refs=True):
+    def __init__(self, c, refs=True, family="gauss"):
         from split_vae_amd import _lib
         self.c, self.lib, self.d = c, _lib.load(), _desc(c)
         self.ldx, self.ldy, self.OH, self.OW, self.hin, self.win = _geom(c)
         self.gdy = _r8(c.Cout)
         dt = _tdt(c)
-        g = torch.Generator().manual_seed(zlib.crc32(c.name.encode()))
-        P = c.P or c.B
-        X = torch.randn(P, self.hin, self.win, c.Cin, generator=g).to(dt)
-        DY = torch.randn(P, self.OH, self.OW, c.Cout, generator=g).to(dt)
-        M = torch.randn(P, c.H, c.W, c.Cin, generator=g).to(dt)
-        ML = torch.randn(P, self.hin, self.win, c.Cin, generator=g).to(dt)
-        fan = c.KH * c.KW * (c.Cin + c.Cout)
-        self.w = ((torch.rand(c.KH, c.KW, c.Cin, c.Cout, generator=g) * 2 - 1) * math.sqrt(6.0 / fan)).contiguous()
-        self.bias = (torch.randn(c.Cout, generator=g) * 0.1) if c.bias else None
-        self.pidx = torch.arange(c.B) % P
-        sidx = (torch.arange(c.B) // P) % 4 if P < c.B else torch.zeros(c.B, dtype=torch.long)
+        self.family, self.ops = family, R.operands(c, family)       # (the Gaussian family: the draws this test always made)
+        self.ratios = {}                                            # what -> worst error / bound of the comparisons by gauss_bound
+        self._exp = {}
+        X, DY, M, ML = (self.ops[k] for k in ("X", "DY", "M", "ML"))
+        self.w, self.bias, self.pidx, sidx = (self.ops[k] for k in ("w", "bias", "pidx", "sidx"))
         sc = torch.tensor(self.SCALES, dtype=torch.float32)[sidx]
 
         def dev(t, ld, scale=None):
@@ -227,7 +246,7 @@ class Layer:
         assert self.lib.sv_conv2d_prep_weights(C.byref(self.d), _p(self.w_dev), _p(self.wf), _p(self.wd), _st()) == 0
         self.rtol, self.atol = (F32_RTOL, F32_ATOL) if c.dt == "f32" else (BF16_RTOL, BF16_ATOL)
         if refs:
-            self._refs(X, DY, M, ML, sidx, dt)
+            self._refs(X, DY, M, ML, sidx, dt)                      # (autograd's references: what the blanket tolerances of the Gaussian pass compare with)
 
     def _refs(self, X, DY, M, ML, sidx, dt):
         c = self.c
@@ -257,21 +276,110 @@ class Layer:
         self.M, self.ML = M, ML
 
     # ---------------------------------------------------------------- checks
-    def check_write_only(self, got, ref, C_, ld, what, tol=None):
+    # ---------------------------------------------------------------- what a call must return (tests/conv_ref.py)
+    def expect(self, key, form=None, mask=None):
+        """Exp of one call: key y | dx | dxlo | dw | db, form: the dispatch form the call takes (which rounding points the reference takes)"""
+        c, ops, dt = self.c, self.ops, _tdt(self.c)
+        composite = form in COMPOSITE
+        # the hi-res gradient is rounded to bf16 before the resize adjoint: the forms of BOUND_NOT_BITS, and only those
+        two_stage = key == "dxlo" and any((op, form, c.dt) in BOUND_NOT_BITS for op in ("dgrad_lowres", "dgrad + sv_upsample2x_bwd"))
+        k = (key, composite, form in POLY_HEAD_FWD, mask, two_stage)
+        if k in self._exp:
+            return self._exp[k]
+        keys, uidx, count, _ = R.unique_images(ops)
+        xu, wr = R.x_unique(ops), R.rnd(ops["w"], dt)
+        b = None if ops["bias"] is None else ops["bias"].double()
+        DY = ops["DY"].double()
+        stage = None if composite else dt                # the polyphase forms read the low-res tensor: no staged hi-res pixel
+        S = S_COMPOSITE if composite else S_SPLIT if form in SPLIT_FORMS else 0
+        extra = None
+        out_bf16 = c.dt == "bf16" and not (key == "y" and c.yf32) and key in ("y", "dx", "dxlo")
+        if key == "y":
+            if form in POLY_HEAD_FWD and c.dt == "bf16":
+                ref = R.poly_head_fwd(xu, ops["w"], b, dt)
+            else:
+                ref = R.conv(xu, wr, b, c.s, c.act, bool(c.ups), stage)
+            if composite:                                # (the border terms are added and taken out again: conv_ref.ab_fwd_composite)
+                ab = R.ab_fwd_composite(xu.abs(), wr.abs()) + (0.0 if b is None else b.abs())
+            else:
+                ab = R.conv(xu.abs(), wr.abs(), None if b is None else b.abs(), c.s, None, bool(c.ups))
+            ref, ab, n = ref[uidx], ab[uidx], c.KH * c.KW * c.Cin
+        elif key == "dx":
+            ref, ab = R.dgrad(DY, wr, c.s, c.H, c.W), R.dgrad(DY.abs(), wr.abs(), c.s, c.H, c.W)
+            if mask == "hi":
+                ref = R.gate(ref, ops["M"])
+            ref, ab, n = ref[self.pidx], ab[self.pidx], -(-c.KH // c.s) * -(-c.KW // c.s) * c.Cout
+        elif key == "dxlo":
+            g_hi = R.dgrad(DY, wr, 1, c.H, c.W)
+            ab1 = R.dgrad(DY.abs(), wr.abs(), 1, c.H, c.W)
+            if two_stage and self.family == "int":
+                # (exact operands: the kernel's fp32 value is g_hi itself, so its rounding is this one, and the bound is the second stage's)
+                mid = R.rnd(g_hi, dt)
+                ref, ab, n = R.gate(R.resize2x_adjoint(mid), ops["ML"]), R.resize2x_adjoint(mid.abs()), 16
+            elif two_stage:
+                # the two stages composed and their bounds added: the first stage's bound and the rounding of ITS result (2^-8 |g|) travel through the adjoint
+                ref = R.gate(R.resize2x_adjoint(g_hi), ops["ML"])
+                e1 = R.gauss_bound(ab1, c.KH * c.KW * c.Cout) + 2.0 ** -8 * g_hi.abs()
+                ab, n = R.resize2x_adjoint(g_hi.abs() + e1), 16
+                extra = R.resize2x_adjoint(e1)[self.pidx]
+            else:
+                ab = R.ab_lowres_composite(DY.abs(), wr.abs(), c.H, c.W) if composite else R.resize2x_adjoint(ab1)
+                ref, n = R.gate(R.resize2x_adjoint(g_hi), ops["ML"]), c.KH * c.KW * c.Cout + 16
+            ref, ab = ref[self.pidx], ab[self.pidx]
+        else:
+            dyu = torch.stack([DY[p] for p, _ in keys])
+            dw, db = R.wgrad(xu, dyu, c.KH, c.KW, c.s, bool(c.ups), stage, count)
+            aw, ab_ = R.wgrad(xu.abs(), dyu.abs(), c.KH, c.KW, c.s, bool(c.ups), None, count)
+            if composite:
+                aw = R.ab_wgrad_composite(xu.abs(), dyu.abs(), c.KH, c.KW, count)
+            ref, ab, n = (dw, aw, c.B * self.OH * self.OW) if key == "dw" else (db, ab_, c.B * self.OH * self.OW)
+            S = max(S, S_SPLIT)                          # slabs / m-split atomics of the weight-gradient kernels
+        e = Exp(ref, ab, n, S, out_bf16, two_stage, extra)
+        self._exp[k] = e
+        return e
+
+    def judge(self, g, e, what, prefill=None):
+        """g: the real channels as float64 (accumulators: what came back); e: Exp.  Integer family: bit for bit (BOUND_NOT_BITS forms: the bound);
+        Gaussian family: gauss_bound."""
+        out_dt = torch.bfloat16 if e.out_bf16 else torch.float32
+        want = e.ref if prefill is None else e.ref + prefill
+        ab = e.ab if prefill is None else e.ab + prefill.abs()
+        if self.family == "int" and not e.two_stage:
+            w, h = want.to(out_dt) + 0.0, g.to(out_dt) + 0.0                 # (+ 0.0: -0 -> +0)
+            bad = _bits(w) != _bits(h)
+            assert not bool(bad.any()), (f"{self.c.name} {what}: {int(bad.sum())} of {bad.numel()} elements differ from the exact result, first at "
+                                         f"{tuple(bad.nonzero()[0].tolist())}: got {float(h[tuple(bad.nonzero()[0])])}, exact {float(w[tuple(bad.nonzero()[0])])}")
+            return
+        bound = R.gauss_bound(ab, e.n, S=e.S + (1 if prefill is not None else 0), ref=want, bf16_out=e.out_bf16)
+        if e.extra is not None:
+            bound = bound + e.extra
+        err = (g - want).abs()
+        ratio = float((err / bound.clamp_min(1e-300)).max())
+        self.ratios[what] = max(self.ratios.get(what, 0.0), ratio)
+        print(f"conv_api {self.c.name} {self.family} {what}: worst error / bound = {ratio:.3f}")
+        assert ratio <= 1.0, f"{self.c.name} {what}: error / gauss_bound = {ratio:.3f} at {tuple((err / bound.clamp_min(1e-300)).flatten().argmax().unsqueeze(0).tolist())}"
+
+    def check_write_only(self, got, ref, C_, ld, what, tol=None, exp=None):
         """real channels against fp64; pad channels [C, r8(C)) exactly zero; beyond r8(C): untouched (NaN) or zero"""
         rtol, atol = tol or (self.rtol, self.atol)
         g = got.double().cpu()
-        scale = max(float(ref.abs().max()), 1e-6)
-        torch.testing.assert_close(g[..., :C_], ref, rtol=rtol, atol=atol * scale, msg=lambda m: f"{self.c.name} {what}: {m}")
+        if self.family == "gauss":
+            scale = max(float(ref.abs().max()), 1e-6)
+            torch.testing.assert_close(g[..., :C_], ref, rtol=rtol, atol=atol * scale, msg=lambda m: f"{self.c.name} {what}: {m}")
+        if exp is not None:
+            self.judge(g[..., :C_], exp, what)
         pad = g[..., C_:min(ld, _r8(C_))]
         assert bool((pad == 0).all()), f"{self.c.name} {what}: pad channels [{C_}, {min(ld, _r8(C_))}) not zero ({int((pad != 0).sum())} elements)"
         beyond = g[..., _r8(C_):ld]
         assert bool((torch.isnan(beyond) | (beyond == 0)).all()), f"{self.c.name} {what}: channels beyond r8(C) written"
 
-    def check_accum(self, got, pat, ref, what):
+    def check_accum(self, got, pat, ref, what, exp=None):
         g, pt = got.double().cpu(), pat.double().cpu()
-        scale = max(float(ref.abs().max()), 1e-6)
-        torch.testing.assert_close(g - pt, ref, rtol=self.rtol, atol=self.atol * scale + 1e-6, msg=lambda m: f"{self.c.name} {what}: {m}")
+        if self.family == "gauss":
+            scale = max(float(ref.abs().max()), 1e-6)
+            torch.testing.assert_close(g - pt, ref, rtol=self.rtol, atol=self.atol * scale + 1e-6, msg=lambda m: f"{self.c.name} {what}: {m}")
+        if exp is not None:
+            self.judge(g, exp, what, prefill=pt)
 
     # ---------------------------------------------------------------- calls
     def fwd(self, ws=None, nbytes=0):
@@ -329,9 +437,11 @@ def _ref_at(L, ref_u):
     return ref_u[L.uidx]
 
 
-def _check_case(c):
-    L = Layer(c)
+def _check_case(c, family="gauss"):
+    L = Layer(c, family=family)
     lib = L.lib
+    # the form a call takes (CASES): with a workspace that is too small a call runs as without one
+    form = lambda call, det, label="none": _expected(c, call + "_ws" if label in ("exact", "0xff") else call, det)
     ws_f = lib.sv_conv2d_fwd_workspace_bytes(C.byref(L.d))
     ws_l = lib.sv_conv2d_dgrad_lowres_workspace_bytes(C.byref(L.d)) if c.ups else 0
     ws_w = lib.sv_conv2d_wgrad_workspace_bytes(C.byref(L.d))
@@ -349,7 +459,7 @@ def _check_case(c):
             for label, ws, nb, guard_at in L.workspaces(ws_f):
                 rc, y = L.fwd(ws, nb)
                 assert rc == 0, (c.name, mode, label, rc)
-                L.check_write_only(y, y_ref, c.Cout, L.ldy, f"fwd[{mode},{label}]")
+                L.check_write_only(y, y_ref, c.Cout, L.ldy, f"fwd[{mode},{label}]", exp=L.expect("y", form("fwd", det, label)))
                 if guard_at is not None:
                     assert bool((ws[guard_at:] == 0xA5).all()), f"{c.name}: forward wrote past the end of a too-small workspace"
                 if first is None:
@@ -370,15 +480,15 @@ def _check_case(c):
                 assert rc == SV_E_UNSUPPORTED and torch.equal(dx, before)
             else:
                 assert rc == 0, (c.name, mode, rc)
-                L.check_write_only(dx, dx_ref, c.Cin, L.ldx, f"dgrad[{mode}]")
+                L.check_write_only(dx, dx_ref, c.Cin, L.ldx, f"dgrad[{mode}]", exp=L.expect("dx", want))
                 if det:
                     assert torch.equal(_bits(L.dgrad()[1]), _bits(dx)), f"{c.name}: deterministic dgrad not bitwise reproducible"
                 rc, dxm, _ = L.dgrad(mask=L.mask)
                 assert rc == 0
-                L.check_write_only(dxm, dx_ref * (L.M[L.pidx].double() > 0), c.Cin, L.ldx, f"dgrad masked[{mode}]")
+                L.check_write_only(dxm, dx_ref * (L.M[L.pidx].double() > 0), c.Cin, L.ldx, f"dgrad masked[{mode}]", exp=L.expect("dx", want, mask="hi"))
                 rc, dxa, pat = L.dgrad(atomic=True)
                 assert rc == 0
-                L.check_accum(dxa[..., :c.Cin], pat[..., :c.Cin], dx_ref, f"dgrad atomic[{mode}]")
+                L.check_accum(dxa[..., :c.Cin], pat[..., :c.Cin], dx_ref, f"dgrad atomic[{mode}]", exp=L.expect("dx", "atomic_splitk"))
                 assert torch.equal(dxa[..., c.Cin:], pat[..., c.Cin:]), f"{c.name}: fp32-atomic dgrad wrote channels >= Cin"
                 if det:
                     assert torch.equal(L.dgrad(atomic=True)[1], dxa), f"{c.name}: deterministic atomic dgrad not reproducible"
@@ -397,10 +507,10 @@ def _check_case(c):
                         assert lib.sv_upsample2x_bwd(_p(dxh), _p(L.mask_lo), _p(dxl), L.d.dtype, c.B, L.hin, L.win, L.ldx, _st()) == 0
                         # (the hi-res gradient is rounded to the activation dtype before the adjoint)
                         L.check_write_only(dxl, lo_ref, c.Cin, L.ldx, f"dgrad+upsample2x_bwd[{mode},{label}]",
-                                           tol=(L.rtol, L.atol if c.dt == "f32" else 2 * L.atol))
+                                           tol=(L.rtol, L.atol if c.dt == "f32" else 2 * L.atol), exp=L.expect("dxlo", "per_class"))
                     else:
                         assert rc == 0, (c.name, label, rc)
-                        L.check_write_only(dxl, lo_ref, c.Cin, L.ldx, f"dgrad_lowres[{mode},{label}]")
+                        L.check_write_only(dxl, lo_ref, c.Cin, L.ldx, f"dgrad_lowres[{mode},{label}]", exp=L.expect("dxlo", form("lowres", det, label)))
             # weight gradient: accumulated into prefilled dw / dbias, with every workspace variant; SV_E_UNSUPPORTED leaves both untouched
             results = []
             for label, ws, nb, guard_at in [("entry", None, 0, None)] + L.workspaces(ws_w):
@@ -411,9 +521,10 @@ def _check_case(c):
                     assert torch.equal(dw, pw) and torch.equal(db, pb), f"{c.name}: refused wgrad[{label}] wrote dw / dbias"
                     continue
                 assert rc == 0, (c.name, mode, label, rc)
-                L.check_accum(dw, pw, L.dw_ref, f"wgrad dw[{mode},{label}]")
+                wform = form("wgrad", det, label)
+                L.check_accum(dw, pw, L.dw_ref, f"wgrad dw[{mode},{label}]", exp=L.expect("dw", wform))
                 if c.bias:
-                    L.check_accum(db, pb, L.db_ref, f"wgrad dbias[{mode},{label}]")
+                    L.check_accum(db, pb, L.db_ref, f"wgrad dbias[{mode},{label}]", exp=L.expect("db", wform))
                 results.append((label, ws, nb, dw))
             assert results or c.forms.get("wgrad_ws") == "unsupported", f"{c.name}: no weight-gradient call succeeded"
             if det and not c.fold:                   # (reproducible with a workspace: without one the tile kernels add atomically, header)
@@ -427,17 +538,26 @@ def _check_case(c):
                 ws = torch.zeros((ws_p,), dtype=torch.uint8, device="cuda")
                 rc, dw, db, pw, pb = L.wgrad_poly(ws, ws_p)
                 assert rc == 0, (c.name, rc)
-                L.check_accum(dw, pw, L.dw_ref, f"wgrad_poly dw[{mode}]")
-                L.check_accum(db, pb, L.db_ref, f"wgrad_poly dbias[{mode}]")
+                L.check_accum(dw, pw, L.dw_ref, f"wgrad_poly dw[{mode}]", exp=L.expect("dw", "wgrad_poly"))
+                L.check_accum(db, pb, L.db_ref, f"wgrad_poly dbias[{mode}]", exp=L.expect("db", "wgrad_poly"))
                 rc, dw, db, pw, pb = L.wgrad_poly(ws, ws_p // 2)
                 assert rc == SV_E_BADARG and torch.equal(dw, pw) and torch.equal(db, pb)
         finally:
             assert lib.sv_set_deterministic(-1) == 0
+    return L.ratios
 
 
 @pytest.mark.parametrize("c", CASES, ids=[c.name for c in CASES])
 def test_descriptor_against_fp64(lib_built, c):
     _check_case(c)
+
+
+@pytest.mark.parametrize("c", CASES, ids=[c.name for c in CASES])
+def test_descriptor_bit_for_bit_on_integer_operands(lib_built, c):
+    """the same call sequence on the integer family: every real channel of every form is the float64 result cast once (BOUND_NOT_BITS aside)"""
+    for call in R.calls_of(c):
+        R.conv_exact_property(c, call)
+    _check_case(c, family="int")
 
 
 # ---------------------------------------------------------------- refusals
