@@ -1272,6 +1272,72 @@ int sv_linprobe_predict(const float* q, int32_t ldq, int32_t Nq, int32_t L, int3
                         const uint8_t* q_class /* or NULL */, int64_t* acc /* ADDED to, or NULL */, double* loss /* or NULL */,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- exact t-SNE map of the latents (csrc/tsne.hip)
+ * No reference counterpart: the 2-D map of the latent means (van der Maaten & Hinton 2008, the exact O(N^2) form) of x [N, L] fp32
+ * (row pitch ldx).  ALL INPUTS ARE FINITE.
+ *   distance     d(i, j) = sv_knn_classify's distance of rows i and j, bit for bit: the same norms, the same fp32 MFMA chain over the
+ *                whole of L, max(0, .).  In the row search a d that is NaN or +inf (an overflowed norm) counts as FLT_MAX;
+ *   conditional  per row i, in fp64 over the fp32 distances: dmin_i = min_{k != i} d_ik, dd_j = d_ij - dmin_i (exact),
+ *                e_j = exp(-beta_i dd_j), S = sum_{j != i} e_j, T = sum_{j != i} e_j dd_j, H(beta) = log S + beta T / S (the Shannon
+ *                entropy in nats), p(j|i) = (float)(e_j / S), p(i|i) = 0.  The sums: thread u of 256 takes j = u, u + 256, ... in
+ *                ascending order, then the threads in thread order;
+ *   search       beta_i by bisection on H(beta) = log(perplexity), H being decreasing in beta: beta = 1, both sides unbounded; then
+ *                exactly 100 steps, no early exit: if H(beta) > log(perplexity) then lo = beta and beta <- (lo + hi) / 2, or 2 beta
+ *                while hi is unbounded; else hi = beta and beta <- (lo + hi) / 2, or beta / 2 while lo is unbounded; after each step
+ *                beta is clamped to [2^-60, 2^60].  beta_i is the value after step 100, row_entropy_i = H(beta_i), and the row is
+ *                the formula above at beta_i.  A row without a root -- H(inf) = log(the number of minimisers of d_i.) >= log
+ *                (perplexity): all distances equal, or more exact duplicates of point i than the perplexity -- ends at beta = 2^60,
+ *                where the formula gives 1 / m on the m minimisers (and what exp(-2^60 dd) leaves elsewhere: 0 for dd > 2^-50).  S >= 1
+ *                always (a minimiser contributes 1), so no row holds a NaN or an inf;
+ *   joint        P_ij = P_ji = (float)(((double)p(j|i) + (double)p(i|j)) / (2 N)), P_ii = 0: dense fp32 [N, N], symmetric bit for
+ *                bit, in the buffer that held the distances and the conditional rows.  p_const [2] fp64 = (sum P, sum_{P > 0} P log P):
+ *                per row lane l of 64 takes j = l, l + 64, ... ascending in fp64, then the lanes in lane order; then thread u of 256
+ *                takes the rows u, u + 256, ..., then the threads in thread order;
+ *   initial map  Y0 [N, 2] = 1e-4f * n(i, c): Philox4x32-10 with the key seed ^ 0x1a7e475e3a9, the standard normal of the counter
+ *                (c, i, 'ts' << 16, 0) by the library's Box-Muller (cosine branch of the first two words); inc = 0, gain = 1,
+ *                state[0] = 0 (the iteration counter; state is int32 [4]);
+ *   pair sums    with w_ij = rcp(q_ij), q_ij = (1 + dx^2) + dy^2, dx = y_i0 - y_j0, dy = y_i1 - y_j1 in fp32 (v_rcp_f32), and w_ii = 0:
+ *                A_ic = sum_j (P_ij w_ij) d_c, R_ic = sum_j (w_ij w_ij) d_c, z_i = sum_j w_ij, l_i = sum_{P_ij > 0} P_ij log2 q_ij
+ *                (v_log_f32).  fp32 partials per (row, chunk of sv_tsne_chunk_rows() columns): lane l of 64 takes the columns
+ *                l, l + 64, ... of the chunk ascending, then the xor butterfly 32, 16, ..., 1; the chunks of a row are folded in
+ *                chunk order in fp64 (l_i then times ln 2).  Z = sum_i z_i and Lw = sum_i l_i in fp64: thread u of a 256-row group
+ *                in thread order, then the groups in order.  The order depends on N and sv_tsne_chunk_rows() alone.  No
+ *                floating-point atomics;
+ *   objective    KL_t = p_const[1] + Lw + log(Z) p_const[0] = sum_{P > 0} P log(P / (w / Z)) of the unexaggerated P, fp64;
+ *   gradient     g_ic = (float)(4 (e A_ic - R_ic / Z)) from the fp64 folds; e = exaggeration while t < exag_iters, else 1;
+ *   update       the original delta-bar-delta rule, fp32 per component: gain <- gain + 0.2 if (g > 0) != (inc > 0) else gain * 0.8;
+ *                gain <- max(gain, 0.01); inc <- m inc - (eta gain) g; y <- y + inc; m = 0.5 while t < exag_iters, else 0.8; then
+ *                y <- y - (float)(column sum / N), the column sums in fp64 in the order of Z; then t <- t + 1.
+ * sv_tsne_affinities: stages = 3 runs all of it; 1 stops behind the distances (P holds d), 2 behind the conditional rows (P holds
+ *   p(j|i) in row i; beta, row_entropy written): for tests.  beta, row_entropy [N] fp64; p_const written by stage 3 only.
+ * sv_tsne_init: Y, inc, gain [N, 2] fp32 and state [4] int32 as above.
+ * sv_tsne_iterate: `iters` iterations from the caller's (Y, inc, gain, state[0] = t) -- sv_tsne_init's, a previous call's, or the
+ *   caller's own -- enqueued without a host round trip.  Exaggeration and momentum switch on state[0], so calls in groups give the bits
+ *   of one call with the total.  kl_trace [trace_len] fp64: iteration t writes kl_trace[t] = KL of the map it STARTED from, when
+ *   t < trace_len; z_last [1] fp64 (may be NULL) <- that iteration's Z.
+ * sv_tsne_neighbour_scores: nn_latent, nn_map [N, k + 1] int32: the neighbour lists sv_knn_classify returns for the latent rows and
+ *   the map rows with queries = references.  Per row "self" is the first entry with index i if the list has it, else the last entry;
+ *   the other k entries are the row's neighbours.  counts [3] int64 += (the number of latent neighbours that are map neighbours too,
+ *   summed over rows; rows whose label equals the majority label of its map neighbours; the same for the latent neighbours); vote ties
+ *   go to the lowest class id; labels NULL: only counts[0].  Integer atomics.  Entries outside [0, N) are no neighbours.
+ * The workspace (sv_tsne_workspace_bytes; 16-byte aligned) may hold anything on entry.  Everything is enqueued on `stream`; no host
+ * synchronisation.  Accepted domain: 4 <= N <= 32768, 1 <= L <= 512, ldx >= L, 1 < perplexity < N - 1, stages 1 .. 3, iters >= 0,
+ * trace_len >= 0, exag_iters >= 0, 1 <= exaggeration <= 1e6, 0 < eta <= 1e9, 1 <= k, k + 1 <= min(32, N), 2 <= n_class <= 64 with
+ * labels: anything else SV_E_UNSUPPORTED; a null pointer (z_last and labels may be NULL) or a misaligned one (4 bytes; fp64 and counts
+ * 8; workspace 16): SV_E_BADARG; workspace_bytes below sv_tsne_workspace_bytes: SV_E_WORKSPACE.  All checked before anything is
+ * enqueued. */
+int sv_tsne_chunk_rows(void);     /* columns per fp32 partial of the pair sums */
+int sv_tsne_workspace_bytes(int32_t N, int64_t* bytes);   /* covers affinities and iterate */
+int sv_tsne_affinities(const float* x, int32_t ldx, int32_t N, int32_t L, double perplexity, int32_t stages, float* P /* [N,N] */,
+                       double* beta /* [N] */, double* row_entropy /* [N] */, double* p_const /* [2] */, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int sv_tsne_init(int32_t N, uint64_t seed, float* Y, float* inc, float* gain, int32_t* state /* [4] */, void* stream);
+int sv_tsne_iterate(const float* P, const double* p_const, int32_t N, int32_t iters, float exaggeration, int32_t exag_iters, float eta,
+                    float* Y, float* inc, float* gain, int32_t* state, double* kl_trace, int32_t trace_len, double* z_last /* or NULL */,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int sv_tsne_neighbour_scores(const int32_t* nn_latent, const int32_t* nn_map, const uint8_t* labels /* [N] or NULL */, int32_t N, int32_t k,
+                             int32_t n_class, int64_t* counts /* [3]: ADDED to */, void* stream);
+
 /* ---- K16 data-parallel gradient exchange: absent in the reference (single device) -----------
  * One process per GPU; gradients of the batch-mean loss (vae/trainer.py:13,:127-128,:137) are averaged over equal
  * shards by an in-place all-reduce(sum) of the flat fp32 gradient buffer; 1/world is sv_adam_step's grad_scale.

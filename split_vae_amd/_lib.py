@@ -23,6 +23,7 @@ KNN_MAX_K, KNN_MAX_L, KNN_MAX_CLASSES = 32, 512, 64      # accepted domain of sv
 LATENT_INFO_MAX_L = 512            # accepted width of either latent block of sv_latent_info_* (include/splitvae.h)
 KMEANS_MAX_L, KMEANS_MAX_K, KMEANS_MAX_R, KMEANS_MAX_N = 512, 64, 16, (1 << 24) - 1      # accepted domain of sv_kmeans_* (include/splitvae.h)
 LINPROBE_MAX_L, LINPROBE_MAX_C, LINPROBE_MAX_N = 512, 64, (1 << 24) - 1      # accepted domain of sv_linprobe_* (include/splitvae.h)
+TSNE_MIN_N, TSNE_MAX_N, TSNE_MAX_L, TSNE_MAX_K = 4, 32768, 512, 31      # accepted domain of sv_tsne_* (include/splitvae.h)
 RECON_MEANS, RECON_KEEP_G, RECON_KEEP_L = 0, 1, 2        # sv_recon_draw modes (include/splitvae.h)
 
 STATUS = {0: "SV_OK", -1: "SV_E_BADARG", -2: "SV_E_UNSUPPORTED", -3: "SV_E_WORKSPACE", -4: "SV_E_STATE"}
@@ -317,6 +318,13 @@ SYMBOLS = {
     "sv_linprobe_gram": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
     "sv_linprobe_fit": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _vp, C.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sv_linprobe_predict": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # t-SNE map of the latents
+    "sv_tsne_chunk_rows": (C.c_int, []),
+    "sv_tsne_workspace_bytes": (C.c_int, [_i32, C.POINTER(_i64)]),
+    "sv_tsne_affinities": (C.c_int, [_vp, _i32, _i32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sv_tsne_init": (C.c_int, [_i32, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "sv_tsne_iterate": (C.c_int, [_vp, _vp, _i32, _i32, C.c_float, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "sv_tsne_neighbour_scores": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
 }
 
 _lib = None

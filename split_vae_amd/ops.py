@@ -1119,6 +1119,83 @@ def linprobe_predict(q, W, q_class=None, acc=None, want_loss=False, workspace=No
     return (pred, loss) if want_loss else pred
 
 
+# ------------------------------------------------------------------ exact t-SNE map of the latents (include/splitvae.h)
+def tsne_chunk_rows():
+    return int(_lib.load().sv_tsne_chunk_rows())
+
+
+def tsne_workspace_bytes(N):
+    n = C.c_int64()
+    check(_lib.load().sv_tsne_workspace_bytes(int(N), C.byref(n)), "sv_tsne_workspace_bytes")
+    return n.value
+
+
+def tsne_affinities(x, perplexity, stages=3, P=None, workspace=None):
+    """sv_tsne_affinities of x [N,L] -> dict(P [N,N] fp32, beta [N] fp64, row_entropy [N] fp64, p_const [2] fp64 (sum P, sum P log P)).
+    stages 1 / 2 stop behind the distances / the conditional rows (P holds those).  P: an [N,N] fp32 buffer to fill instead of a fresh one."""
+    xp, ldx = _rows_f32(x, "x")
+    N, L = x.shape
+    if P is None:
+        P = torch.empty((N, N), dtype=torch.float32, device=x.device)
+    if P.dtype != torch.float32 or not P.is_cuda or not P.is_contiguous() or tuple(P.shape) != (N, N):
+        raise ValueError("P must be a contiguous [%d,%d] fp32 device tensor" % (N, N))
+    e = lambda n: torch.empty((n,), dtype=torch.float64, device=x.device)      # noqa: E731
+    out = dict(P=P, beta=e(N), row_entropy=e(N), p_const=e(2))
+    ws = _workspace(tsne_workspace_bytes(N), workspace, x.device)
+    check(_lib.load().sv_tsne_affinities(xp, ldx, N, L, float(perplexity), int(stages), _p(P), _p(out["beta"]), _p(out["row_entropy"]),
+                                         _p(out["p_const"]), _p(ws), ws.numel(), _stream()), "sv_tsne_affinities")
+    return out
+
+
+def tsne_state(N, total_iters, device="cuda", Y=None, inc=None, gain=None, counter=0):
+    """The in-out buffers of a run: dict(Y, inc, gain [N,2] fp32, state [4] int32, kl [total_iters] fp64 (NaN until written), z [1] fp64).
+    Without Y this is storage only (tsne_init fills it); with Y (and optionally inc, gain, counter) it is a caller's state."""
+    def take(t, fill):
+        if t is None:
+            return torch.full((N, 2), fill, dtype=torch.float32, device=device)
+        if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (N, 2):
+            raise ValueError("Y, inc and gain must be [%d,2] fp32 device tensors" % N)
+        return t.contiguous()
+    state = torch.zeros((4,), dtype=torch.int32, device=device)
+    state[0] = int(counter)
+    return dict(Y=take(Y, 0.0), inc=take(inc, 0.0), gain=take(gain, 1.0), state=state,
+                kl=torch.full((max(int(total_iters), 1),), float("nan"), dtype=torch.float64, device=device),
+                z=torch.zeros((1,), dtype=torch.float64, device=device))
+
+
+def tsne_init(st, seed=0):
+    """sv_tsne_init on the buffers of tsne_state: the Philox initial map, inc = 0, gain = 1, counter = 0."""
+    N = st["Y"].shape[0]
+    check(_lib.load().sv_tsne_init(N, int(seed) & (2 ** 64 - 1), _p(st["Y"]), _p(st["inc"]), _p(st["gain"]), _p(st["state"]), _stream()), "sv_tsne_init")
+    return st
+
+
+def tsne_iterate(aff, st, iters, exaggeration=12.0, exag_iters=250, eta=200.0, workspace=None):
+    """sv_tsne_iterate: `iters` more iterations of the run in `st` against aff["P"]; nothing is read back."""
+    P = aff["P"]
+    N = P.shape[0]
+    ws = _workspace(tsne_workspace_bytes(N), workspace, P.device)
+    check(_lib.load().sv_tsne_iterate(_p(P), _p(aff["p_const"]), N, int(iters), float(exaggeration), int(exag_iters), float(eta), _p(st["Y"]),
+                                      _p(st["inc"]), _p(st["gain"]), _p(st["state"]), _p(st["kl"]), st["kl"].numel(), _p(st["z"]), _p(ws),
+                                      ws.numel(), _stream()), "sv_tsne_iterate")
+    return st
+
+
+def tsne_neighbour_scores(nn_latent, nn_map, labels=None, n_class=0, counts=None):
+    """sv_tsne_neighbour_scores: counts [3] int64 += (latent neighbours kept in the map, map k-NN hits, latent k-NN hits) from the two
+    [N,k+1] int32 neighbour lists of knn_classify(x, x, ..., k + 1, want_neighbours=True); labels [N] uint8 or None."""
+    N, k1 = nn_latent.shape
+    for t in (nn_latent, nn_map):
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (N, k1):
+            raise ValueError("the neighbour lists must be contiguous [N,k+1] int32 device tensors of one shape")
+    lab = None if labels is None else _classes_u8(labels, N, "labels")
+    if counts is None:
+        counts = torch.zeros((3,), dtype=torch.int64, device=nn_latent.device)
+    check(_lib.load().sv_tsne_neighbour_scores(_p(nn_latent), _p(nn_map), lab, N, k1 - 1, int(n_class), _p(counts), _stream()),
+          "sv_tsne_neighbour_scores")
+    return counts
+
+
 # ------------------------------------------------------------------ aggregate-posterior information report (include/splitvae.h)
 def latent_info_chunk_rows():
     return int(_lib.load().sv_latent_info_chunk_rows())
