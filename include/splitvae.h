@@ -1338,6 +1338,46 @@ int sv_tsne_iterate(const float* P, const double* p_const, int32_t N, int32_t it
 int sv_tsne_neighbour_scores(const int32_t* nn_latent, const int32_t* nn_map, const uint8_t* labels /* [N] or NULL */, int32_t N, int32_t k,
                              int32_t n_class, int64_t* counts /* [3]: ADDED to */, void* stream);
 
+/* ---------------------------------------------------------------- swap-consistency report of the latents (csrc/swap.hip)
+ * No reference counterpart.  decode(z_g of image A, z_l of image B) is re-encoded as the image it is, and the originals are ranked by
+ * their distance from the re-encoded latents: does each block come back from its own source?  (split_vae_amd/swap.py)
+ * sv_swap_pair: zcat [B, Lg + Ll] (contiguous, `dtype` of sv_dtype) <- [ mu[ig[b], 0:Lg] | mu[il[b], Lg:Lg+Ll] ], one rounding to the
+ *   dtype.  mu [N, Lg + Ll] fp32 with row pitch ldmu >= Lg + Ll; ig, il [B] int32 on the device.  An index outside [0, N) is clamped
+ *   (nothing is read outside mu; the host layer refuses such an index).  SV_E_BADARG: a null or misaligned pointer, N, B, Lg or Ll <= 0,
+ *   ldmu below the width, a dtype outside sv_dtype.
+ * sv_swap_requantise: a decode as the image it is, and the encoders' six-channel batch of it, in one pass.  out6 [B,H,W,6] fp32 (the
+ *   plan's out6_x, read in place): channels 0..2 are the mean m; channels 3..5 are NEVER READ.  Per value, in fp32:
+ *   v = fminf(fmaxf(m, -1), 1); level = (int) rintf(fmaf(v, 127.5, 127.5)) (one rounding, ties to even), clamped to 0 .. 255; the
+ *   pixel is lut[level], lut [256] fp32 = data.ResidentDataset.make_lut(): the data's own values x / 255 * 2 - 1.  A NaN MEAN MAPS TO
+ *   LEVEL 0.  images6 [B,H,W,6] fp32: channels 0..2 the requantised image, channels 3..5 its patch scramble by perm [B, (H/patch)^2]
+ *   int32 with sv_scramble_gather's index rule (x_aug[r s + i, c s + j] = x[pr s + i, pc s + j], (pr, pc) = divmod(perm[r G + c], G));
+ *   a perm entry outside [0, G^2) is clamped.  Every output element is written exactly once; no workspace; out6 and images6 must not
+ *   be the same buffer.  SV_E_BADARG: a null or misaligned (4 bytes) pointer, out6 == images6, B, H, W or patch <= 0;
+ *   SV_E_UNSUPPORTED: H != W or patch does not divide H.
+ * sv_swap_rank: queries q [Nq, L] and references r [Nr, L] fp32 (row pitches ldq, ldr >= L), two target lists t0, t1 [Nq] int32 in
+ *   [0, Nr) on the device (clamped; the host layer refuses others).  rank [Nq, 2] int32:
+ *     rank[q][s] = #{ j != t_s[q] : d(q, j) < d(q, t_s[q])  or  (d(q, j) == d(q, t_s[q]) and j < t_s[q]) }
+ *   with d sv_knn_classify's squared distance, bit for bit (the same norms, the same fp32 MFMA chain over the whole of L, d = max(0,
+ *   (n(q) + n(r)) - 2 dot)); ALL INPUTS ARE FINITE.  The thresholds d(q, t_s[q]) come from the same tile code on the gathered target
+ *   rows, so they are the bits the count sees in column t_s[q]; that column is excluded by index.  The references are cut into chunks
+ *   of sv_swap_chunk_rows() rows; integer partial counts per (chunk, query) are folded in chunk order: no atomics, no floating-point
+ *   sums, the same bits on a repeat.  The Nq x Nr matrix never exists.  Nothing outside rank [Nq, 2] and the workspace is written; the
+ *   workspace (sv_swap_rank_workspace_bytes; 16-byte aligned) may hold anything on entry.  Everything is enqueued on `stream`; no host
+ *   synchronisation.  SV_E_BADARG: a null or misaligned pointer (4 bytes; workspace 16), Nq, Nr or L <= 0, a pitch below L;
+ *   SV_E_UNSUPPORTED: Nq > 8 * 65536, Nr > 2^24 or L > 512; SV_E_WORKSPACE: workspace_bytes below sv_swap_rank_workspace_bytes.  All
+ *   checked before anything is enqueued.
+ * sv_swap_shift_word_host: the 32-bit Philox word the report draws its partner shifts from, keyed by (seed, a tag of this report's own,
+ *   partner p, attempt); host only. */
+int sv_swap_pair(const float* mu, int32_t ldmu, const int32_t* ig, const int32_t* il, void* zcat, int32_t dtype, int32_t N, int32_t B,
+                 int32_t Lg, int32_t Ll, void* stream);
+int sv_swap_requantise(const float* out6, const float* lut /* [256] */, const int32_t* perm, float* images6, int32_t B, int32_t H,
+                       int32_t W, int32_t patch, void* stream);
+int sv_swap_chunk_rows(void);     /* reference rows per chunk of the count pass: lets callers and tests size Nr */
+int sv_swap_rank_workspace_bytes(int32_t Nq, int32_t Nr, int32_t L, int64_t* bytes);
+int sv_swap_rank(const float* q, int32_t ldq, const float* r, int32_t ldr, const int32_t* t0, const int32_t* t1, int32_t Nq, int32_t Nr,
+                 int32_t L, int32_t* rank /* [Nq,2] */, void* workspace, int64_t workspace_bytes, void* stream);
+uint32_t sv_swap_shift_word_host(uint64_t seed, int32_t p, int32_t attempt);
+
 /* ---- K16 data-parallel gradient exchange: absent in the reference (single device) -----------
  * One process per GPU; gradients of the batch-mean loss (vae/trainer.py:13,:127-128,:137) are averaged over equal
  * shards by an in-place all-reduce(sum) of the flat fp32 gradient buffer; 1/world is sv_adam_step's grad_scale.

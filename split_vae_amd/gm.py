@@ -306,10 +306,11 @@ class LGGMVae(LGVae):
             s = _SIDE_STREAMS[dev] = torch.cuda.ExternalStream(h.value, device=dev)
         return s
 
-    def __call__(self, inputs, training=False, eps=None, noise=None, copy=True):
-        """vae/model.py:236-246 -> the 14-tuple (the LGVae 10-tuple, then y, y_logits, z_prior_mean, z_prior_sig)."""
+    def __call__(self, inputs, training=False, eps=None, noise=None, copy=True, sample_offset=0):
+        """vae/model.py:236-246 -> the 14-tuple (the LGVae 10-tuple, then y, y_logits, z_prior_mean, z_prior_sig).  sample_offset: row b draws
+        its noise as global sample sample_offset + b (the train step's key); 0 keys a row by its place in the batch, as always."""
         B = inputs.shape[0]
-        plan, enc, _ = self._forward(inputs, training, eps, noise, False, {})
+        plan, enc, _ = self._forward(inputs, training, eps, noise, False, {"sample_offset": int(sample_offset)} if sample_offset else {})
         self._calls += 1
         o = list(self._outputs(plan, B, copy))
         b = enc.buf

@@ -148,11 +148,12 @@ class GMVae:
         plan.step(PHASE_FWD_DECODERS | (PHASE_LOSS if want_loss else 0), **kw)
         return plan, enc, kw
 
-    def __call__(self, inputs, training=False, eps=None, noise=None, copy=True):
-        """vae/model.py:288-298 -> (x_mean, x_log_scale, z_x, z_mean_x, z_sig_x, y, y_logits, z_prior_mean, z_prior_sig)."""
+    def __call__(self, inputs, training=False, eps=None, noise=None, copy=True, sample_offset=0):
+        """vae/model.py:288-298 -> (x_mean, x_log_scale, z_x, z_mean_x, z_sig_x, y, y_logits, z_prior_mean, z_prior_sig).  sample_offset: row b
+        draws its noise as global sample sample_offset + b (the train step's key); 0 keys a row by its place in the batch, as always."""
         B = inputs.shape[0]
         with ops.hold_stream():
-            plan, enc, _ = self._forward(inputs, training, eps, noise, False, {})
+            plan, enc, _ = self._forward(inputs, training, eps, noise, False, {"sample_offset": int(sample_offset)} if sample_offset else {})
         self._calls += 1
         o6 = plan.buffer("out6_x", torch.float32, (B, self.H, self.W, 6))
         b = enc.buf

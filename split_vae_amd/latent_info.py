@@ -31,10 +31,13 @@ def check_flags(latent_info, global_latent_dims=1, local_latent_dims=0):
         raise SystemExit("--latent_info covers latent blocks of at most %d dimensions" % LATENT_INFO_MAX_L)
 
 
-def batch_posterior(model, images):
+def batch_posterior(model, images, sample_offset=0):
     """(z_mean_x, z_sig_x, z_mean_x_hat or None, z_sig_x_hat or None) of one batch, as views of buffers the next batch overwrites:
     the encoder passes probe.latent_means reads its means from.  LGVae runs its encoders only; LGGMVae / GMVae run the model's forward
-    (their z_mean_x is computed behind the relaxed categorical sample y, drawn at the model's current call counter)."""
+    (their z_mean_x is computed behind the relaxed categorical sample y, drawn at the model's current call counter).  That sample is
+    keyed by the row's global sample index sample_offset + b: the default 0 keys a row by its place in the batch (every report so far);
+    a caller that passes the batch's first global image index gets means that do not depend on how the images are batched.  LGVae's means
+    depend on no noise."""
     from .gm import LGGMVae
     from .gmvae import GMVae, _images6
     B = images.shape[0]
@@ -51,7 +54,7 @@ def batch_posterior(model, images):
         raise TypeError("latent posteriors are read from LGVae, LGGMVae and GMVae models, got %s" % type(model).__name__)
     calls = model._calls
     try:
-        out = model(_images6(images) if isinstance(model, GMVae) else images, copy=False)
+        out = model(_images6(images) if isinstance(model, GMVae) else images, copy=False, **({"sample_offset": int(sample_offset)} if sample_offset else {}))
     finally:
         model._calls = calls                       # a report between training steps does not move the training noise
     if isinstance(model, LGGMVae):
@@ -59,16 +62,17 @@ def batch_posterior(model, images):
     return out[3], out[4], None, None
 
 
-def posteriors(model, batches, n=None):
+def posteriors(model, batches, n=None, keyed=False):
     """The encoders' means and standard deviations of the first `n` images of `batches` ([B,H,W,6] device batches, or (images,
-    labels) pairs; n None: all) -> (mu, sig [N, Lg+Ll] fp32 device tensors: columns 0 .. Lg-1 z_g, the rest z_l; Lg, Ll).  Leaves
-    model._calls alone."""
+    labels) pairs; n None: all) -> (mu, sig [N, Lg+Ll] fp32 device tensors: columns 0 .. Lg-1 z_g, the rest z_l; Lg, Ll).  keyed: image i
+    draws the mixture models' noise as global sample i (batch_posterior's sample_offset), whatever the batch size.  Leaves model._calls
+    alone."""
     mus, sigs, have, Lg, Ll = [], [], 0, 0, 0
     for batch in batches:
         if n is not None and have >= n:
             break
         images = images_of(batch)
-        mg, sg, ml, sl = batch_posterior(model, images)
+        mg, sg, ml, sl = batch_posterior(model, images, have if keyed else 0)
         Lg, Ll = int(mg.shape[1]), (0 if ml is None else int(ml.shape[1]))
         take = images.shape[0] if n is None else min(images.shape[0], n - have)
         mus.append(torch.cat([mg[:take]] + ([ml[:take]] if Ll else []), dim=1))

@@ -1196,6 +1196,94 @@ def tsne_neighbour_scores(nn_latent, nn_map, labels=None, n_class=0, counts=None
     return counts
 
 
+# ------------------------------------------------------------------ swap-consistency report of the latents (include/splitvae.h)
+def swap_chunk_rows():
+    return int(_lib.load().sv_swap_chunk_rows())
+
+
+def swap_rank_workspace_bytes(Nq, Nr, L):
+    n = C.c_int64()
+    check(_lib.load().sv_swap_rank_workspace_bytes(int(Nq), int(Nr), int(L), C.byref(n)), "sv_swap_rank_workspace_bytes")
+    return n.value
+
+
+def swap_shift_word_host(seed, p, attempt=0):
+    """The 32-bit Philox word of (seed, partner p, attempt) the report's partner shifts come from; host only."""
+    return int(_lib.load().sv_swap_shift_word_host(int(seed) & (2 ** 64 - 1), int(p), int(attempt)))
+
+
+def _index_i32(t, n, name, limit=None):
+    """A contiguous int32 device tensor [n]; with `limit`, one host read checks every entry against [0, limit)."""
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (n,):
+        raise ValueError("%s must be a contiguous int32 device tensor of %d indices" % (name, n))
+    if limit is not None and n:
+        lo, hi = torch.stack([t.min(), t.max()]).tolist()
+        if lo < 0 or hi >= limit:
+            raise ValueError("%s: an index outside [0, %d): min %d, max %d" % (name, limit, lo, hi))
+    return C.c_void_p(t.data_ptr())
+
+
+def swap_pair(mu, ig, il, Lg, zcat, check_range=True):
+    """sv_swap_pair: zcat [B, Lg+Ll] (fp32 or bf16, contiguous) <- [mu[ig, :Lg] | mu[il, Lg:]] of mu [N, Lg+Ll] fp32 (a row pitch above
+    the width is allowed); ig, il [B] int32 device tensors in [0, N) (check_range: checked here with one read-back)."""
+    mp, ldmu = _rows_f32(mu, "mu")
+    N, Lc = mu.shape
+    B = int(ig.shape[0]) if torch.is_tensor(ig) and ig.dim() == 1 else -1
+    if not 0 < int(Lg) < Lc:
+        raise ValueError("swap_pair needs two latent blocks: 0 < Lg < %d, got %r" % (Lc, Lg))
+    if B < 1:
+        raise ValueError("ig must be a contiguous int32 device tensor of B >= 1 indices")
+    lim = N if check_range else None
+    gp, lp = _index_i32(ig, B, "ig", lim), _index_i32(il, B, "il", lim)
+    if (not torch.is_tensor(zcat) or zcat.dtype not in _SV_DT or not zcat.is_cuda or not zcat.is_contiguous()
+            or tuple(zcat.shape) != (B, Lc)):
+        raise ValueError("zcat must be a contiguous [%d,%d] fp32 or bf16 device tensor" % (B, Lc))
+    check(_lib.load().sv_swap_pair(mp, ldmu, gp, lp, _p(zcat), sv_dtype(zcat.dtype), N, B, int(Lg), Lc - int(Lg), _stream()), "sv_swap_pair")
+    return zcat
+
+
+def swap_requantise(out6, lut, perm, patch, out=None):
+    """sv_swap_requantise: out6 [B,H,W,6] fp32 (channels 0..2 read) -> images6 [B,H,W,6] fp32: the decode's mean as pixel levels
+    through lut [256] fp32 in channels 0..2, its patch scramble by perm [B,(H/patch)^2] int32 in channels 3..5."""
+    if not torch.is_tensor(out6) or out6.dim() != 4 or out6.shape[3] != 6 or out6.dtype != torch.float32 or not out6.is_cuda or not out6.is_contiguous():
+        raise ValueError("out6 must be a contiguous [B,H,W,6] fp32 device tensor")
+    B, H, W, _ = out6.shape
+    if not torch.is_tensor(lut) or lut.dtype != torch.float32 or not lut.is_cuda or not lut.is_contiguous() or tuple(lut.shape) != (256,):
+        raise ValueError("lut must be a contiguous [256] fp32 device tensor")
+    if H != W or patch < 1 or H % patch:
+        raise ValueError("swap_requantise assumes square images and patch | H, got %dx%d, patch %r" % (H, W, patch))
+    G2 = (H // patch) * (W // patch)
+    if not torch.is_tensor(perm) or perm.dtype != torch.int32 or not perm.is_cuda or not perm.is_contiguous() or tuple(perm.shape) != (B, G2):
+        raise ValueError("perm must be a contiguous [%d,%d] int32 device tensor" % (B, G2))
+    if out is None:
+        out = torch.empty((B, H, W, 6), dtype=torch.float32, device=out6.device)
+    if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (B, H, W, 6) or out.data_ptr() == out6.data_ptr():
+        raise ValueError("out must be a contiguous [%d,%d,%d,6] fp32 device tensor other than out6" % (B, H, W))
+    check(_lib.load().sv_swap_requantise(_p(out6), _p(lut), _p(perm), _p(out), B, H, W, int(patch), _stream()), "sv_swap_requantise")
+    return out
+
+
+def swap_rank(q, r, t0, t1, rank=None, workspace=None, check_range=True):
+    """sv_swap_rank: rank [Nq,2] int32 = per query row of q [Nq,L] the number of rows of r [Nr,L] that come before row t0[q] / t1[q]
+    of r under the order (squared distance of sv_knn_classify, index).  t0, t1 [Nq] int32 device tensors in [0, Nr) (check_range:
+    checked here with one read-back).  workspace: a uint8 device tensor of at least swap_rank_workspace_bytes(Nq, Nr, L) bytes."""
+    qp, ldq = _rows_f32(q, "q")
+    rp, ldr = _rows_f32(r, "r")
+    Nq, L = q.shape
+    Nr = r.shape[0]
+    if r.shape[1] != L or r.device != q.device:
+        raise ValueError("q [%d,%d] and r [%d,%d] must have one width and one device" % (Nq, L, Nr, r.shape[1]))
+    lim = Nr if check_range else None
+    p0, p1 = _index_i32(t0, Nq, "t0", lim), _index_i32(t1, Nq, "t1", lim)
+    if rank is None:
+        rank = torch.empty((Nq, 2), dtype=torch.int32, device=q.device)
+    if rank.dtype != torch.int32 or not rank.is_cuda or not rank.is_contiguous() or tuple(rank.shape) != (Nq, 2):
+        raise ValueError("rank must be a contiguous [%d,2] int32 device tensor" % Nq)
+    ws = _workspace(swap_rank_workspace_bytes(Nq, Nr, L), workspace, q.device)
+    check(_lib.load().sv_swap_rank(qp, ldq, rp, ldr, p0, p1, Nq, Nr, L, _p(rank), _p(ws), ws.numel(), _stream()), "sv_swap_rank")
+    return rank
+
+
 # ------------------------------------------------------------------ aggregate-posterior information report (include/splitvae.h)
 def latent_info_chunk_rows():
     return int(_lib.load().sv_latent_info_chunk_rows())
