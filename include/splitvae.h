@@ -1378,6 +1378,38 @@ int sv_swap_rank(const float* q, int32_t ldq, const float* r, int32_t ldr, const
                  int32_t L, int32_t* rank /* [Nq,2] */, void* workspace, int64_t workspace_bytes, void* stream);
 uint32_t sv_swap_shift_word_host(uint64_t seed, int32_t p, int32_t attempt);
 
+/* ---------------------------------------------------------------- sample-quality report of prior draws (csrc/prdc.hip)
+ * No reference counterpart.  Improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) ask "is
+ * query q inside reference j's k-NN ball": a compare against a per-COLUMN radius, a count and a row minimum behind the distance tile,
+ * and the k-NN radius of a set against itself.  (split_vae_amd/sample_quality.py)
+ *   distance  d(q, r) = sv_knn_classify's squared distance, bit for bit (the same norms, the same fp32 MFMA chain over the whole of L in
+ *             ascending order, d = max(0, (n(q) + n(r)) - 2 q . r)); ALL INPUTS ARE FINITE.
+ * sv_prdc_radius: x [N, L] fp32 (row pitch ldx >= L).  rad [N] fp32: rad[i] = the k-th smallest element of { d(i, j) : j != i } under the
+ *   total order (d, j).  SELF IS EXCLUDED BY INDEX, NOT BY A ZERO DISTANCE: a duplicate of row i at another index is a neighbour at
+ *   distance 0.  Computed from sv_knn_classify's (k + 1)-list of x against itself: index i is dropped from the list if it is there, the
+ *   k-th of what remains is the radius (self is missing from the list only when k + 1 other rows precede it under (d, j), and then the
+ *   k-th entry is the answer as well).  Domain: 1 <= k <= 31, k + 1 <= N <= 8 * 65536, 1 <= L <= 512.
+ * sv_prdc_count: queries q [Nq, L] and references r [Nr, L] fp32 (row pitches ldq, ldr >= L), rad [Nr] fp32, the radius of each
+ *   REFERENCE.    cnt[q]  = #{ j : d(q, j) <= rad[j] }          (note <=)                         int32 [Nq]
+ *                 dmin[q] = min_j d(q, j)                                                          fp32 [Nq] or NULL
+ *                 imin[q] = the lowest j that attains the minimum                                  int32 [Nq] or NULL
+ *   The references are cut into chunks of sv_prdc_chunk_rows() rows; one (cnt, dmin, imin) partial per (chunk, query) is folded in
+ *   ascending chunk order, a strict < keeping the lower index: integer counts and minima, no atomics, no floating-point sums, the same
+ *   bits on a repeat.  The Nq x Nr matrix never exists.
+ * Both: nothing outside the outputs and the workspace is written; the workspace (sv_prdc_workspace_bytes; 16-byte aligned) may hold
+ *   anything on entry.  sv_prdc_workspace_bytes(Nq, Nr, L, k) covers sv_prdc_count at (Nq, Nr, L) and, where Nq == Nr >= k + 1,
+ *   sv_prdc_radius at (N = Nr, L, k) too; it wants 1 <= k <= 31 either way.  Everything is enqueued on `stream`; no host
+ *   synchronisation.  SV_E_BADARG: a null or misaligned pointer (4 bytes; workspace 16), N, Nq, Nr or L <= 0, a pitch below L;
+ *   SV_E_UNSUPPORTED: Nq > 8 * 65536, Nr > 2^24, L > 512, k outside 1 .. 31, N < k + 1 or N > 8 * 65536; SV_E_WORKSPACE:
+ *   workspace_bytes below what the call needs.  All checked before anything is enqueued. */
+int sv_prdc_chunk_rows(void);     /* reference rows per chunk of the count pass: lets callers and tests size Nr */
+int sv_prdc_workspace_bytes(int32_t Nq, int32_t Nr, int32_t L, int32_t k, int64_t* bytes);
+int sv_prdc_radius(const float* x, int32_t ldx, int32_t N, int32_t L, int32_t k, float* rad /* [N] */, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+int sv_prdc_count(const float* q, int32_t ldq, const float* r, int32_t ldr, const float* rad /* [Nr] */, int32_t Nq, int32_t Nr, int32_t L,
+                  int32_t* cnt /* [Nq] */, float* dmin /* [Nq] or NULL */, int32_t* imin /* [Nq] or NULL */, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+
 /* ---- K16 data-parallel gradient exchange: absent in the reference (single device) -----------
  * One process per GPU; gradients of the batch-mean loss (vae/trainer.py:13,:127-128,:137) are averaged over equal
  * shards by an in-place all-reduce(sum) of the flat fp32 gradient buffer; 1/world is sv_adam_step's grad_scale.

@@ -25,6 +25,7 @@ KMEANS_MAX_L, KMEANS_MAX_K, KMEANS_MAX_R, KMEANS_MAX_N = 512, 64, 16, (1 << 24) 
 LINPROBE_MAX_L, LINPROBE_MAX_C, LINPROBE_MAX_N = 512, 64, (1 << 24) - 1      # accepted domain of sv_linprobe_* (include/splitvae.h)
 TSNE_MIN_N, TSNE_MAX_N, TSNE_MAX_L, TSNE_MAX_K = 4, 32768, 512, 31      # accepted domain of sv_tsne_* (include/splitvae.h)
 SWAP_MAX_L, SWAP_MAX_NQ, SWAP_MAX_NR = 512, 8 * 65536, 1 << 24      # accepted domain of sv_swap_rank (include/splitvae.h)
+PRDC_MAX_K, PRDC_MAX_L, PRDC_MAX_NQ, PRDC_MAX_NR = 31, 512, 8 * 65536, 1 << 24      # accepted domain of sv_prdc_radius / sv_prdc_count (include/splitvae.h)
 RECON_MEANS, RECON_KEEP_G, RECON_KEEP_L = 0, 1, 2        # sv_recon_draw modes (include/splitvae.h)
 
 STATUS = {0: "SV_OK", -1: "SV_E_BADARG", -2: "SV_E_UNSUPPORTED", -3: "SV_E_WORKSPACE", -4: "SV_E_STATE"}
@@ -333,6 +334,11 @@ SYMBOLS = {
     "sv_swap_rank_workspace_bytes": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i64)]),
     "sv_swap_rank": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
     "sv_swap_shift_word_host": (C.c_uint32, [_u64, _i32, _i32]),
+    # sample-quality report of prior draws
+    "sv_prdc_chunk_rows": (C.c_int, []),
+    "sv_prdc_workspace_bytes": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_i64)]),
+    "sv_prdc_radius": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "sv_prdc_count": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

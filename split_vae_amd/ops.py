@@ -1284,6 +1284,62 @@ def swap_rank(q, r, t0, t1, rank=None, workspace=None, check_range=True):
     return rank
 
 
+# ------------------------------------------------------------------ sample-quality report of prior draws (include/splitvae.h)
+def prdc_chunk_rows():
+    return int(_lib.load().sv_prdc_chunk_rows())
+
+
+def prdc_workspace_bytes(Nq, Nr, L, k):
+    n = C.c_int64()
+    check(_lib.load().sv_prdc_workspace_bytes(int(Nq), int(Nr), int(L), int(k), C.byref(n)), "sv_prdc_workspace_bytes")
+    return n.value
+
+
+def _vec(t, n, dtype, name):
+    if not torch.is_tensor(t) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (n,):
+        raise ValueError("%s must be a contiguous %s device tensor of %d elements" % (name, str(dtype).replace("torch.", ""), n))
+    return t
+
+
+def prdc_radius(x, k, rad=None, workspace=None):
+    """sv_prdc_radius: rad [N] fp32 = per row i of x [N,L] the k-th smallest squared distance (sv_knn_classify's, ties to the lower
+    index) to the OTHER rows: self is excluded by index, a duplicate at another index is a neighbour at distance 0.  1 <= k <= 31,
+    N >= k + 1.  workspace: a uint8 device tensor of at least prdc_workspace_bytes(N, N, L, k) bytes."""
+    xp, ldx = _rows_f32(x, "x")
+    N, L = x.shape
+    if not 1 <= int(k) <= _lib.PRDC_MAX_K or N < int(k) + 1:
+        raise ValueError("prdc_radius needs 1 <= k <= %d and N >= k + 1, got k = %r, N = %d" % (_lib.PRDC_MAX_K, k, N))
+    rad = torch.empty((N,), dtype=torch.float32, device=x.device) if rad is None else _vec(rad, N, torch.float32, "rad")
+    ws = _workspace(prdc_workspace_bytes(N, N, L, k), workspace, x.device)
+    check(_lib.load().sv_prdc_radius(xp, ldx, N, L, int(k), _p(rad), _p(ws), ws.numel(), _stream()), "sv_prdc_radius")
+    return rad
+
+
+def prdc_count(q, r, rad, cnt=None, dmin=None, imin=None, want_min=True, workspace=None):
+    """sv_prdc_count: per query row of q [Nq,L] against r [Nr,L] with the references' radii rad [Nr] fp32: cnt [Nq] int32 =
+    #{j : d(q,j) <= rad[j]}, dmin [Nq] fp32 = min_j d(q,j), imin [Nq] int32 = the lowest j that attains it (d sv_knn_classify's squared
+    distance).  -> (cnt, dmin, imin), or cnt alone with want_min False.  workspace: a uint8 device tensor of at least
+    prdc_workspace_bytes(Nq, Nr, L, 1) bytes."""
+    qp, ldq = _rows_f32(q, "q")
+    rp, ldr = _rows_f32(r, "r")
+    Nq, L = q.shape
+    Nr = r.shape[0]
+    if r.shape[1] != L or r.device != q.device:
+        raise ValueError("q [%d,%d] and r [%d,%d] must have one width and one device" % (Nq, L, Nr, r.shape[1]))
+    _vec(rad, Nr, torch.float32, "rad")
+    e = lambda dt: torch.empty((Nq,), dtype=dt, device=q.device)      # noqa: E731
+    cnt = e(torch.int32) if cnt is None else _vec(cnt, Nq, torch.int32, "cnt")
+    if want_min:
+        dmin = e(torch.float32) if dmin is None else _vec(dmin, Nq, torch.float32, "dmin")
+        imin = e(torch.int32) if imin is None else _vec(imin, Nq, torch.int32, "imin")
+    elif dmin is not None or imin is not None:
+        raise ValueError("prdc_count: dmin / imin given with want_min False")
+    ws = _workspace(prdc_workspace_bytes(Nq, Nr, L, 1), workspace, q.device)
+    check(_lib.load().sv_prdc_count(qp, ldq, rp, ldr, _p(rad), Nq, Nr, L, _p(cnt), _p(dmin), _p(imin), _p(ws), ws.numel(), _stream()),
+          "sv_prdc_count")
+    return (cnt, dmin, imin) if want_min else cnt
+
+
 # ------------------------------------------------------------------ aggregate-posterior information report (include/splitvae.h)
 def latent_info_chunk_rows():
     return int(_lib.load().sv_latent_info_chunk_rows())
